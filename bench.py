@@ -3,7 +3,12 @@
 per GPU per step (BASELINE.json metric), synthetic 800x800 scene, random-init weights of the
 shipped architecture.
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, or spawned here)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N>1: launched by torch.distributed.run, or spawned here)
+
+Every leg times exactly K steps (after W untimed ones); `ms_per_step` is their total time / K. --dump-outputs DIR writes
+what the last of them handed back and left behind, as DIR/<name>.npy (rank 0; float32 / float64, a few MB): `step_stats`, the
+step's [loss, color_loss, psnr, eikonal, depth_loss, mask_loss], and `parameters`, every network parameter after its update.
+Inputs (seeded weights, rays, jitter) are the same on every run with the same arguments, so two builds compare array by array.
 
 One JSON line on rank 0 with the driver's contract plus
   roofline      the fused SDF kernel as the timed step launches it (HIP events on the launch stream, in situ; `schedule` says on which
@@ -16,8 +21,8 @@ One JSON line on rank 0 with the driver's contract plus
   parity_path   the SAME step on the fp32 kernels (the path that holds the 1e-4 tolerance), driver-timed in this run;
   wdepth        the womsk_white_wdepth step (VDN head + depth-feature loss);
   all_samples_evaluated  the step with the zero-weight work lists off;
-  trials        every timed region is K steps bracketed by barrier + synchronize; `value` is the median region of at
-                least 5 regions / 1 s of timed GPU work, the spread is reported;
+  trials        every leg times exactly K steps, in min(5, K) regions bracketed by barrier + synchronize; `value` is their
+                total, the spread of the regions is reported;
   cpu_baseline  the oracle (CPU restatement of the reference) timed on this host.
 """
 import argparse
@@ -273,14 +278,24 @@ class Leg:
         self.last = out
         return dt
 
-    def measure(self, warmup, steps, min_trials=5, min_seconds=1.0, max_trials=2000):
+    def measure(self, warmup, steps, keep_outputs=False):
+        """`warmup` untimed steps, then exactly `steps` timed ones in min(5, steps) regions of (nearly) equal length; `value` /
+        `ms_per_step` are their total. keep_outputs: self.outputs = what the last timed step handed back (its statistics) and
+        left behind (the parameters after its update), copied to the host before anything else runs."""
         for i in range(warmup):
             self.step(i)
+        n = min(5, steps)
+        sizes = [steps // n + (1 if j < steps % n else 0) for j in range(n)]
         regions = []
-        # (the loop condition only uses max-reduced times, so every rank runs the same number of regions)
-        while len(regions) < min_trials or (sum(regions) < min_seconds and len(regions) < max_trials):
-            regions.append(self.region(warmup + len(regions) * steps, steps))
-        med = float(np.median(regions))
+        for k in sizes:
+            regions.append(self.region(warmup + sum(sizes[:len(regions)]), k))
+        per_step = [t / k for t, k in zip(regions, sizes)]
+        step_s = sum(regions) / steps
+        if keep_outputs:
+            self.fence()
+            self.outputs = {"step_stats": self.last.detach().double().cpu().numpy(),
+                            "parameters": self.trainer.param_flat.detach().float().cpu().numpy()}
+        first_untimed = warmup + steps
         eng = self.trainer.engine
         # mean work-list rows of the steady state: one more (untimed) pass over ALL resident batches - the lists differ by +-10 %
         # between images, and every mean that is compared with another (the kernel statistics under profiles/ quote this one:
@@ -289,22 +304,23 @@ class Leg:
         counts = []
         n_cycle = len(self.batches)
         for i in range(n_cycle):
-            self.step(warmup + len(regions) * steps + i)
+            self.step(first_untimed + i)
             counts.append((eng.w["fg_active"][1].clone(), eng.w["bg_active"][1].clone() if "bg_active" in eng.w else None))
         self.fence()
         rows_fg = float(np.mean([int(a.item()) for a, _ in counts]))
         rows_bg = float(np.mean([int(b.item()) for _, b in counts])) if counts[0][1] is not None else 0.0
         fg = int(eng.w["fg_active"][1].item())
         bg = int(eng.w["bg_active"][1].item()) if "bg_active" in eng.w else 0
-        rays = self.world * self.B * steps
+        rays = self.world * self.B
         fpr = flop_per_ray(self.wdepth, fg / float(eng.P), bg / float(eng.Q) if eng.Q else 1.0)
-        return {"value": rays / med, "ms_per_step": med / steps * 1e3,
-                "trials": {"regions": len(regions), "steps_per_region": steps, "timed_seconds": float(sum(regions)),
-                           "ms_per_step_min": min(regions) / steps * 1e3, "ms_per_step_max": max(regions) / steps * 1e3},
+        return {"value": rays / step_s, "ms_per_step": step_s * 1e3,
+                "trials": {"regions": len(regions), "steps_per_region": sizes, "timed_steps": steps,
+                           "timed_seconds": float(sum(regions)),
+                           "ms_per_step_min": min(per_step) * 1e3, "ms_per_step_max": max(per_step) * 1e3},
                 "work_list_rows_mean": {"foreground": rows_fg, "background": rows_bg, "over_steps": n_cycle},
                 "foreground_points_evaluated_last_step": fg, "foreground_points_total": eng.P,
                 "background_points_evaluated_last_step": bg, "background_points_total": eng.Q,
-                "executed_flop_per_ray": fpr, "executed_model_flops_per_s": rays / med * fpr,
+                "executed_flop_per_ray": fpr, "executed_model_flops_per_s": rays / step_s * fpr,
                 "final_loss": float(self.last[0].item())}
 
     def sdf_kernel_roofline(self, n_lists=6, one_stream=None, in_situ_steps=60):
@@ -561,6 +577,21 @@ def real_cameras():
     return d[tag + "__c2w"].astype(np.float64), float(d[tag + "__fx"]) ** 2 * 800.0         # poses.py:80-84: focal = fx^2 * W
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """arrays {name: float32 / float64 ndarray} -> out_dir/<name>.npy. An array over its share of `budget` bytes is replaced by a
+    fixed sample of its flattened entries (indices from a seeded generator, ascending)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -581,7 +612,11 @@ def main():
                     help="womsk_white = BASELINE.json configs[1] (the headline); womsk_white_wdepth = configs[4] (VDN head + depth-feature loss)")
     ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16",
                     help="bf16 = BASELINE.json's headline config (bf16 MFMA, fp32 accumulate); fp32 = the parity path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (step statistics, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start N fresh ranks BEFORE anything touches the GPU (a process that
@@ -610,8 +645,12 @@ def main():
     wdepth = args.config == "womsk_white_wdepth"
     K, W = args.steps, args.warmup
     nb = W + K                                          # distinct resident batches; regions cycle through them
+    # torch's generators (the step's jitter) from one fixed seed, whatever ran before: same inputs on every run
+    torch.manual_seed(0)
     head = Leg(args, dev, world, rank, args.precision, wdepth, nb, crop=args.crop)
-    res = head.measure(W, K)
+    res = head.measure(W, K, keep_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, head.outputs)
     extras = {}
     if world > 1:
         # K more steps with HIP events around every collective (dp.Collectives.sum_now / finish): how long each stream actually
@@ -693,7 +732,7 @@ def main():
         for i in range(head.steps_done):             # to the same training state (the work lists shrink over the first ~600 steps)
             one.step(i)
         one.fence()
-        r1 = one.measure(0, K, min_trials=3, min_seconds=0.3)      # the one-stream schedule's own step time, beside its kernel figure
+        r1 = one.measure(0, K)      # the one-stream schedule's own step time, beside its kernel figure
         roof = head.sdf_kernel_roofline(one_stream=one)   # every rank takes part (steps hold collectives); rank 0 gets the numbers
         if roof is not None:
             roof["schedule"] = ("one stream (VDN_SIDE_STREAM=0 VDN_OVERLAP=0: every launch of the step in order; the schedule of the committed "

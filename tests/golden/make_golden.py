@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz by running the REFERENCE (read-only at /root/reference) on CPU.
+"""Generate tests/golden/*.npz by running the REFERENCE (a checkout of the original project: --reference DIR, or the
+environment variable VDN_REFERENCE) on CPU.
 
-Runs only in the build container (the reference does not travel to the GPU box). It
+Runs only where that checkout is present (it does not travel with this repository). It
   1. stubs the two absent third-party imports of dpt_models/renderer.py:6-7 (mcubes, icecream),
   2. builds the reference's own SDFNetwork / RenderingNetwork / NeRF / SingleVarianceNetwork /
      NeuSRenderer at the shipped config shapes and loads this repo's deterministic synthetic
@@ -11,8 +12,13 @@ Runs only in the build container (the reference does not travel to the GPU box).
      regenerated from (seed, name) by vdn_train.synth),
   5. cross-checks the oracle (oracle/neus_oracle.py) against the reference and prints the errors.
 
-Usage:  python tests/golden/make_golden.py [--check-only]
+Usage:  python tests/golden/make_golden.py --reference DIR [--check-only | --digests] [--only a,b]
+
+--digests writes tests/golden/reference_digests.json: one SHA-256 digest per fixture the reference generated, which
+tests/test_golden_pin_cpu.py holds the committed fixtures to without the reference.
 """
+import hashlib
+import json
 import argparse
 import os
 import sys
@@ -29,7 +35,25 @@ sys.path.insert(0, ROOT)
 warnings.filterwarnings("ignore")
 
 
-REFERENCE = "/root/reference"
+REFERENCE = os.path.abspath(os.environ.get("VDN_REFERENCE", "reference"))
+DIGESTS = os.path.join(HERE, "reference_digests.json")
+
+
+def array_digest(a):
+    """SHA-256 of an array's dtype, shape and bytes (C order): equal digests = bit-identical arrays."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256()
+    h.update(("%s|%s|" % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def fixture_digest(arrays):
+    """SHA-256 over a fixture's sorted `key digest` lines ({npz key: array}): equal digests = the same keys, bit-identical arrays."""
+    h = hashlib.sha256()
+    for k in sorted(arrays):
+        h.update(("%s %s\n" % (k, array_digest(np.asarray(arrays[k])))).encode())
+    return h.hexdigest()
 
 
 def import_reference():
@@ -756,8 +780,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check-only", action="store_true",
                     help="regenerate from the reference, compare with the committed fixtures bit for bit, write nothing")
+    ap.add_argument("--digests", action="store_true",
+                    help="write the digests of the regenerated arrays to reference_digests.json (merged with those of other fixtures)")
     ap.add_argument("--only", default=None, help="comma-separated fixture names (default: all)")
+    ap.add_argument("--reference", default=None, help="checkout of the reference project (default: $VDN_REFERENCE)")
     args = ap.parse_args()
+    global REFERENCE
+    if args.reference:
+        REFERENCE = os.path.abspath(args.reference)
     out = generate(None if args.only is None else set(args.only.split(",")))
     if args.check_only:
         bad = compare_with_committed(out)
@@ -765,6 +795,15 @@ def main():
             print("MISMATCH %s: %s" % (name, key))
         print("checked %d fixtures against the reference: %s" % (len(out), "all bit-identical" if not bad else "%d differences" % len(bad)))
         sys.exit(1 if bad else 0)
+    if args.digests:
+        have = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
+        for name, fx in out.items():
+            have[name] = fixture_digest({k.replace("/", "__"): v for k, v in fx.items()})
+        with open(DIGESTS, "w") as f:
+            json.dump(dict(sorted(have.items())), f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("wrote", DIGESTS, "(%d fixtures)" % len(have))
+        return
     for name, fx in out.items():
         path = os.path.join(HERE, name + ".npz")
         np.savez_compressed(path, **{k.replace("/", "__"): np.asarray(v) for k, v in fx.items()})

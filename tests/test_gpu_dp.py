@@ -285,7 +285,8 @@ def test_bench_two_rank_control_flow():
         d, err = _bench(cmd, env, with_stderr=True)
         assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak" and d["value"] > 0
         assert d["config"]["parallelism"] == "dp2" and d["roofline"]["frac"] > 0 and d["cpu_baseline"] is None
-        assert d["trials"]["regions"] >= 5 and d["trials"]["steps_per_region"] == 3
+        # --steps is the number of timed steps: 3, one per region
+        assert d["trials"]["timed_steps"] == 3 and d["trials"]["regions"] == 3 and d["trials"]["steps_per_region"] == [1, 1, 1]
         # one leg: no fp32 / wdepth / object-centric / runner legs at N > 1, and the collectives' exposed time is in the line
         assert not {"parity_path", "wdepth", "object_centric", "runner_flow", "all_samples_evaluated", "real_cameras"} & set(d)
         assert set(d["allreduce_exposed_ms"]) >= {"grad_sdf", "grad_nerf", "grad_heads"}
@@ -298,17 +299,24 @@ def test_bench_two_rank_control_flow():
     assert bad.returncode != 0 and not [l for l in bad.stdout.splitlines() if l.startswith("{")]
 
 
-def test_bench_line_carries_every_leg():
+def test_bench_line_carries_every_leg(tmp_path):
     """One default-shaped run (shortened): the driver's contract keys, the executed-FLOP accounting, the trial spread and the
-    fp32 parity-path / wdepth / all-samples legs in the same line."""
+    fp32 parity-path / wdepth / all-samples legs in the same line; --steps timed steps exactly, and --dump-outputs."""
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    d = _bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    dump = str(tmp_path / "dump")
+    d = _bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", dump])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline", "trials", "parity_path", "wdepth", "all_samples_evaluated", "object_centric"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["dtype"] == "bf16" and d["vs_baseline"] is None and "workload" in d["config"]
-    assert d["trials"]["regions"] >= 5 and d["trials"]["timed_seconds"] >= 1.0
+    assert d["trials"]["timed_steps"] == 2 and d["trials"]["steps_per_region"] == [1, 1] and d["trials"]["timed_seconds"] > 0
+    assert abs(d["ms_per_step"] - d["trials"]["timed_seconds"] / 2 * 1e3) < 1e-6 * d["ms_per_step"]
+    # the last timed step's outputs: its statistics [loss, color_loss, psnr, eikonal, depth_loss, mask_loss] and the parameters it
+    # left (final_loss is read after the untimed pass that follows, from the same reused buffer: a later step's loss)
+    stats, params = np.load(os.path.join(dump, "step_stats.npy")), np.load(os.path.join(dump, "parameters.npy"))
+    assert stats.shape == (6,) and stats.dtype == np.float64 and np.isfinite(stats).all() and stats[0] > 0
+    assert params.dtype == np.float32 and params.size * 4 == d["config"]["allreduce_bytes"] and np.isfinite(params).all()
     assert d["parity_path"]["dtype"] == "f32" and d["parity_path"]["value"] > 0 and d["parity_path"]["roofline"]["frac"] > 0
     assert d["wdepth"]["value"] > 0 and d["wdepth"]["value"] < d["value"]
     # model FLOP/s counts executed points only: never above the all-samples convention

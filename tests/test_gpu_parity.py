@@ -588,7 +588,10 @@ def test_full_size_batch_vs_oracle(dev, wdepth):
     """BASELINE.json's full size directly against the oracle: 512 rays x (64 + 64 + 32) samples, fp32 kernels, both shipped
     configurations (renderer.py:332-439). End to end (own sampler) the per-ray outputs hold 1e-4 of the largest entry; with the
     oracle's z injected - the inverse-CDF sampler is ill-conditioned where the CDF is flat, which is sampling
-    noise, not arithmetic - they hold it element by element: |delta| <= 1e-4 |ref| + 1e-6 max|ref|."""
+    noise, not arithmetic - they hold it element by element against the EXACT values (the oracle in fp64 on the same z):
+    |delta| <= 1e-4 |ref| + 2e-6 max|ref|. The floor is the fp32 round-off of the sums behind an entry: the oracle's own fp32
+    evaluation misses 1e-6 max|ref| on render_feats (1.07 - 1.55 x the bound, by host BLAS), so an fp32 reference at that floor
+    would only test whether two fp32 evaluations happen to round alike."""
     import oracle.neus_oracle as orc
     from vdn_train import synth, factory
     B, seed = 512, 5
@@ -604,6 +607,10 @@ def test_full_size_batch_vs_oracle(dev, wdepth):
     with torch.no_grad():
         ref = orc.render(nets, tt(o), tt(d), tt(near), tt(far), background_rgb=torch.ones(1, 3), cos_anneal_ratio=0.5,
                          t_rand=tt(t1), t_rand_out=tt(t2), record=rec)
+        t64 = lambda x: torch.tensor(np.asarray(x), dtype=torch.float64)
+        ref64 = orc.render(orc.nets_from_numpy(st, dtype=torch.float64), t64(o), t64(d), t64(near), t64(far),
+                           background_rgb=torch.ones(1, 3, dtype=torch.float64), cos_anneal_ratio=0.5, t_rand=t64(t1),
+                           t_rand_out=t64(t2), z_vals_inject=rec["z_vals_inside"].double())
         args = [g(x, dev) for x in (o, d, near, far)]
         kw = dict(background_rgb=torch.ones(1, 3, device=dev), cos_anneal_ratio=0.5, t_rand=g(t1, dev), t_rand_out=g(t2, dev))
         out = rend.render(*args, **kw)
@@ -612,10 +619,10 @@ def test_full_size_batch_vs_oracle(dev, wdepth):
     for k in keys:
         assert tuple(out[k].shape) == tuple(ref[k].shape), k
         assert relmax(out[k].cpu().numpy(), ref[k].numpy()) < 1e-4, (k, "end to end")
-        e = relelem(inj[k].cpu().numpy(), ref[k].numpy())
+        e = relelem(inj[k].cpu().numpy(), ref64[k].numpy(), floor=2e-6)
         assert e <= 1.0, (k, "injected z, element-wise", e)
     for k in ("weights", "gradients", "cdf_fine"):
-        assert relmax(inj[k].cpu().numpy(), ref[k].numpy()) < 1e-4, k
+        assert relmax(inj[k].cpu().numpy(), ref64[k].numpy()) < 1e-4, k
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

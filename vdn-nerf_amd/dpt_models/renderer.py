@@ -190,6 +190,26 @@ _PLAN_STATE = ("_ctx", "_fg_compact", "_bg_compact", "_composite_bwd_done", "_bw
                "_car_dev", "_fwd_rays", "_fused_keep")
 
 
+class _OneStreamCapture:
+    """Inside a capture: the engine's side-stream roles point at the capturing stream, so the graph is one chain of the same
+    launches, in the order they were issued, instead of forking into parallel branches. The HIP runtime can fail replaying a
+    graph with parallel branches when the process has few hardware queues; the kernels, their arguments and the launch
+    selection (TrainEngine._tail_wanted, split_dw, ...) stay exactly those of the eager schedule."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def __enter__(self):
+        eng, cur = self.eng, torch.cuda.current_stream()
+        self.saved = eng._side, eng._side2
+        eng._side = cur if eng._side is not None else None
+        eng._side2 = cur if eng._side2 is not None else None
+
+    def __exit__(self, *exc):
+        self.eng._side, self.eng._side2 = self.saved
+        return False
+
+
 class _TrainPlan:
     """render() under grad of one batch size as HIP graphs (round 6; what RenderPlan is for the inference path). An unchanged
     dpt_runner.py spends more host time per step than the device needs: ~0.5 ms of Python in render() and ~0.25 ms in
@@ -199,7 +219,7 @@ class _TrainPlan:
         fixed input buffers; the annealing ratio comes from a device scalar (VdnCompositeArgs.cos_anneal_dev), so the runner's
         schedule (dpt_runner.py:304-308) needs no re-capture;
       * backward, per pattern of present adjoints: TrainEngine.backward on staged adjoints, side-stream work included
-        (fork / join events become graph dependencies).
+        (captured on the capturing stream in issue order: _OneStreamCapture).
     A step is then: one multi-tensor copy of the inputs, one replay, one copy of the outputs' arena; in backward one copy per
     adjoint, one replay, one multi-tensor copy of the gradients. Row counts of the work lists are device-side and every grid is
     sized for the full batch, so the graphs are independent of the data. Built by NeuSRenderer at the SECOND call with a key (the
@@ -220,7 +240,7 @@ class _TrainPlan:
         self.bwd = {}
         skip = os.environ.get("VDN_RENDER_FG_COMPACT", "1") != "0"
         g = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(g):
+        with torch.no_grad(), torch.cuda.graph(g), _OneStreamCapture(eng):
             z, z_out = rend._sample(self.rays_o, self.rays_d, self.near, self.far, perturb, self.t_rand, self.t_rand_out, None)
             z = z.contiguous()
             eng.forward(self.rays_o, self.rays_d, z, z_out, self.bgc, 0.0, skip_far=skip, rest_normals=skip, cos_anneal_dev=self.car)
@@ -259,7 +279,7 @@ class _TrainPlan:
             bufs = (f(B, 3) if pat[0] else None, f(B, 96) if pat[1] else None, f(B, eng.T) if pat[2] else None, f(1) if pat[3] else None)
             g = torch.cuda.CUDAGraph()
             try:
-                with torch.no_grad(), torch.cuda.graph(g):
+                with torch.no_grad(), torch.cuda.graph(g), _OneStreamCapture(eng):
                     eng.backward(bufs[0], bufs[1], bufs[2], bufs[3])
             except Exception as e:                           # (as for the forward: report once, this pattern stays eager)
                 import warnings

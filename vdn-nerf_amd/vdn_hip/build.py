@@ -118,7 +118,8 @@ def build(force=False, jobs=None, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     srcs = _sources()
     hm = _headers_mtime()
-    jobs = jobs or min(len(srcs), max(1, (os.cpu_count() or 2) - 1))
+    # (MAX_JOBS: the CPUs this process may use, where that is fewer than the host has)
+    jobs = jobs or int(os.environ.get("MAX_JOBS", "0")) or min(len(srcs), max(1, (os.cpu_count() or 2) - 1))
     rebuilt = False
     with cf.ThreadPoolExecutor(jobs) as ex:
         for src, dt, _ in ex.map(lambda s: _compile(s, force, hm), srcs):
