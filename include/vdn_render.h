@@ -406,6 +406,19 @@ typedef struct {
 } VdnNerfBwdArgs;
 int vdn_nerf_mlp_bwd_f32(const VdnNerfBwdArgs* args_host, void* stream);
 int vdn_nerf_mlp_bwd_bf16(const VdnNerfBwdArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */
+/* Input adjoint for EXPLICIT inputs (standalone NeRF.forward under autograd, fields.py:324-353): the forward ran on the given
+ * pts4 / dirs (VdnNerfArgs.pts4 / .dirs); the backward of VdnNerfBwdArgs runs as above and also writes d loss / d pts4 and
+ * d loss / d dirs as they are (no map back through the inverted-sphere parameterisation). The ray-regenerated adjoint of
+ * VdnNerfBwdArgs (d_pts / d_dirs) must be off (-3). Rows are addressed by the dense point id, as g_density. */
+typedef struct {
+    const float* pts4;         /* [P,4] the forward's input_pts */
+    const float* dirs;         /* [P,3] the forward's input_views */
+    float* d_pts4;             /* [P,4] out */
+    float* d_dirs;             /* [P,3] out */
+    int32_t accumulate;        /* 0: overwrite d_pts4 / d_dirs, 1: add into them */
+} VdnNerfInputGradArgs;
+int vdn_nerf_mlp_bwd_input_f32(const VdnNerfBwdArgs* args_host, const VdnNerfInputGradArgs* in_host, void* stream);
+int vdn_nerf_mlp_bwd_input_bf16(const VdnNerfBwdArgs* args_host, const VdnNerfInputGradArgs* in_host, void* stream);
 
 /* backward of SDFNetwork.forward + .gradient (fields.py:72-108), i.e. including the double backward
  * through the input-gradient. Two chains (DESIGN.md 'Backward'):

@@ -1,5 +1,8 @@
 // Backward of the background NeRF MLP on gfx950, shared body for both policies: delta chain through
 // the transposed layers with ReLU masks from the saved activations. Adjoint of fields.py:324-353.
+// EXPL (standalone NeRF.forward under autograd): the inputs are the given pts4 [P,4] / dirs [P,3] (NerfInputGradArgs)
+// instead of points regenerated from rays, and their adjoints d_pts4 / d_dirs are written as they are - no map back
+// through the inverted-sphere parameterisation.
 #pragma once
 #include <type_traits>
 #include "mlp_engine.h"
@@ -7,13 +10,13 @@
 
 namespace vdn {
 
-template <class P, bool DPT>
-__global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_kernel(NerfBwdArgs a) {
+template <class P, bool DPT, bool EXPL>
+__global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_kernel(NerfBwdArgs a, NerfInputGradArgs in) {
     using ST = typename P::store_t;
     constexpr int kSlot = P::stride(9);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     WStream<P::kWaves, kSlot> ws;
-    const bool want_pts = a.d_pts != nullptr;      // differentiable rays: three more chunks (W0^T) and the encodings' adjoints
+    const bool want_pts = EXPL || a.d_pts != nullptr;      // input adjoints: three more chunks (W0^T) and the encodings' adjoints
     ws.init(a.blob, smem, want_pts ? 83 : 80);
     const int lane = ws.lane, c = lane & 31, h = lane >> 5;
     // p = row in the (possibly compacted) work list = row of the saves and deltas; pd = dense point id of the upstream grads
@@ -38,7 +41,12 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
     // inverted-sphere point and view direction of this lane's sample, as the forward builds them (renderer.py:112-115)
     float x4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, dir[3] = {0.0f, 0.0f, 0.0f}, pw[3] = {0.0f, 0.0f, 0.0f}, nrm = 1.0f;
     float dx4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ddir[3] = {0.0f, 0.0f, 0.0f};
-    if (want_pts) {
+    if (EXPL) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) x4[d] = in.pts4[pd * 4 + d];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) dir[d] = in.dirs[pd * 3 + d];
+    } else if (want_pts) {
         const long r = pd / a.n_per_ray;
         const float z = a.z[pd];
 #pragma unroll
@@ -130,6 +138,15 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
             else if (nt == 1) pe_adjoint_tile<4, 10, 1, P::kAccurateTrig>(acc, h, x4, dx4);
             else pe_adjoint_tile<4, 10, 2, P::kAccurateTrig>(acc, h, x4, dx4);
         });
+        if (EXPL) {
+            if (ok && h == 0) {
+#pragma unroll
+                for (int d = 0; d < 4; ++d) in.d_pts4[pd * 4 + d] = (in.accumulate ? in.d_pts4[pd * 4 + d] : 0.0f) + dx4[d];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) in.d_dirs[pd * 3 + d] = (in.accumulate ? in.d_dirs[pd * 3 + d] : 0.0f) + ddir[d];
+            }
+            return;
+        }
         // pts4 = [p / r, 1 / r], r = clip(|p|, 1, 1e10): inside the clip r = |p| (d r / d p = p / r), outside it is a constant
         if (ok && h == 0) {
             const bool free_r = nrm >= 1.0f && nrm <= 1e10f;
@@ -146,22 +163,40 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
     }
 }
 
-template <class P>
-int launch_nerf_bwd(const VdnNerfBwdArgs* args, void* stream_) {
+template <class P, bool EXPL>
+int launch_nerf_bwd_impl(const VdnNerfBwdArgs* args, const NerfInputGradArgs& in, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!args || args->P <= 0 || !args->blob || !args->g_density || !args->g_rgb || !args->save_h || !args->save_hv ||
-        !args->delta_o || !args->delta_v || !args->delta_head || !args->delta_h) return -1;
-    if (args->d_pts && (!args->d_dirs || !args->rays_o || !args->rays_d || !args->z || args->n_per_ray <= 0)) return -2;
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     const size_t lds = 3 * P::stride(9);
-    static bool once = (allow_big_lds(nerf_bwd_kernel<P, false>, lds), allow_big_lds(nerf_bwd_kernel<P, true>, lds), true);
+    static bool once = (allow_big_lds(nerf_bwd_kernel<P, false, EXPL>, lds), allow_big_lds(nerf_bwd_kernel<P, true, EXPL>, lds), true);
     (void)once;
     if (args->g_feat != nullptr)
-        hipLaunchKernelGGL((nerf_bwd_kernel<P, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args);
+        hipLaunchKernelGGL((nerf_bwd_kernel<P, true, EXPL>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args, in);
     else
-        hipLaunchKernelGGL((nerf_bwd_kernel<P, false>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args);
+        hipLaunchKernelGGL((nerf_bwd_kernel<P, false, EXPL>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args, in);
     return (int)hipGetLastError();
+}
+
+inline bool nerf_bwd_args_ok(const VdnNerfBwdArgs* args) {
+    return args && args->P > 0 && args->blob && args->g_density && args->g_rgb && args->save_h && args->save_hv &&
+           args->delta_o && args->delta_v && args->delta_head && args->delta_h;
+}
+
+template <class P>
+int launch_nerf_bwd(const VdnNerfBwdArgs* args, void* stream) {
+    if (!nerf_bwd_args_ok(args)) return -1;
+    if (args->d_pts && (!args->d_dirs || !args->rays_o || !args->rays_d || !args->z || args->n_per_ray <= 0)) return -2;
+    return launch_nerf_bwd_impl<P, false>(args, NerfInputGradArgs{}, stream);
+}
+
+// explicit inputs (vdn_nerf_mlp_bwd_input_*): the ray-regenerated input adjoint of VdnNerfBwdArgs (d_pts) must be off
+template <class P>
+int launch_nerf_bwd_input(const VdnNerfBwdArgs* args, const VdnNerfInputGradArgs* in, void* stream) {
+    if (!nerf_bwd_args_ok(args)) return -1;
+    if (!in || !in->pts4 || !in->dirs || !in->d_pts4 || !in->d_dirs) return -2;
+    if (args->d_pts || args->d_dirs) return -3;
+    return launch_nerf_bwd_impl<P, true>(args, *in, stream);
 }
 
 }  // namespace vdn

@@ -26,6 +26,7 @@ using LossArgs = ::VdnLossArgs;
 using RayAdjointArgs = ::VdnRayAdjointArgs;
 using TrainPrepArgs = ::VdnTrainPrepArgs;
 using GenRaysArgs = ::VdnGenRaysArgs;
+using NerfInputGradArgs = ::VdnNerfInputGradArgs;
 
 // Kernels needing more than 64 KiB of dynamic LDS opt in once per process.
 template <class K>

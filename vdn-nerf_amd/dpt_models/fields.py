@@ -10,7 +10,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from vdn_hip import images, layout, lib
+from vdn_hip import images, layout, lib, points
 from dpt_models.embedder import get_embedder
 
 
@@ -23,6 +23,102 @@ def _require_gpu(t, what):
 
 
 _stream = lib.stream_handle          # the HIP handle of torch's current stream
+
+
+# The standalone networks' autograd nodes (one per public call). Their backward is hand-derived (vdn_hip/points.py) and has no
+# backward of its own: once_differentiable, so a second differentiation through a node raises.
+_once = torch.autograd.function.once_differentiable
+
+
+class _SdfFn(torch.autograd.Function):
+    """SDFNetwork.forward / .sdf / .gradient: a saving mode-1 forward; the backward takes the adjoints of sdf, feature and
+    normal (rbar + fbar chains) to every parameter and, when it requires grad, to x."""
+
+    @staticmethod
+    def forward(ctx, module, what, x, *params):
+        want_x = x.requires_grad
+        sv = points.sdf_saves(module, x.shape[0], x.device, want_x)
+        xd = x.detach().contiguous()
+        sdf, feat, normals = module._run(1, pts=xd, saves=sv)
+        ctx.module, ctx.what, ctx.sv, ctx.want_x = module, what, sv, want_x
+        ctx.save_for_backward(xd, *params)
+        if what == "sdf":
+            out = sdf[:, None]
+        elif what == "gradient":
+            out = normals.unsqueeze(1)
+        else:
+            if module.precision == "bf16":
+                feat = layout.from_pt32(feat, x.shape[0], 256)
+            out = torch.cat([sdf[:, None], feat], dim=-1)
+        return out
+
+    @staticmethod
+    @_once
+    def backward(ctx, g):
+        xd, *params = ctx.saved_tensors            # (unpacking checks that no parameter was modified in place since the forward)
+        P, dev = xd.shape[0], xd.device
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        g_sdf, g_feat, g_normals = z(P), None, None
+        if g is not None:
+            if ctx.what == "sdf":
+                g_sdf = g[:, 0]
+            elif ctx.what == "gradient":
+                g_normals = g[:, 0]
+            else:
+                g_sdf, g_feat = g[:, 0], g[:, 1:]
+        dx, grads = points.sdf_backward(ctx.module, xd, ctx.sv, g_sdf, z(P, 256) if g_feat is None else g_feat,
+                                        z(P, 3) if g_normals is None else g_normals, ctx.want_x)
+        ctx.sv = None
+        return (None, None, dx) + tuple(grads)
+
+
+class _RenderingFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, pts, normals, dirs, fvec, *params):
+        want_in = any(t.requires_grad for t in (pts, normals, dirs, fvec))
+        P = pts.shape[0]
+        sv = points.rendering_saves(module, P, pts.device)
+        ins = tuple(t.detach().contiguous() for t in (pts, normals, dirs))
+        fv, extra = module._feature_planes(fvec.detach())
+        out = module._run(ins[1], fv, pts=ins[0], dirs=ins[2], extra=extra, saves=sv)
+        ctx.module, ctx.sv, ctx.fv, ctx.want_in = module, sv, fv, want_in
+        ctx.needs = tuple(t.requires_grad for t in (pts, normals, dirs, fvec))
+        ctx.save_for_backward(*ins, out, *params)
+        return out
+
+    @staticmethod
+    @_once
+    def backward(ctx, g):
+        pts, normals, dirs, out, *params = ctx.saved_tensors
+        d_pts, d_nrm, d_dirs, d_fv, grads = points.rendering_backward(ctx.module, (pts, normals, dirs), ctx.fv, out, ctx.sv, g,
+                                                                      ctx.want_in)
+        ctx.sv = ctx.fv = None
+        ins = tuple(d if need else None for d, need in zip((d_pts, d_nrm, d_dirs, d_fv), ctx.needs))
+        return (None,) + ins + tuple(grads)
+
+
+class _NerfFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, pts4, dirs, *params):
+        want_in = pts4.requires_grad or dirs.requires_grad
+        sv = points.nerf_saves(module, pts4.shape[0], pts4.device)
+        p4, dd = pts4.detach().contiguous(), dirs.detach().contiguous()
+        density, rgb, feat = module._run(pts4=p4, dirs=dd, saves=sv)
+        ctx.module, ctx.sv, ctx.want_in = module, sv, want_in
+        ctx.needs = (pts4.requires_grad, dirs.requires_grad)
+        ctx.save_for_backward(p4, dd, *params)
+        return density[:, None], rgb, feat
+
+    @staticmethod
+    @_once
+    def backward(ctx, g_density, g_rgb, g_feat):
+        p4, dd, *params = ctx.saved_tensors
+        P, dev = p4.shape[0], p4.device
+        g_density = torch.zeros(P, dtype=torch.float32, device=dev) if g_density is None else g_density[:, 0]
+        g_rgb = torch.zeros(P, 3, dtype=torch.float32, device=dev) if g_rgb is None else g_rgb
+        d_p4, d_dirs, grads = points.nerf_backward(ctx.module, p4, dd, ctx.sv, g_density, g_rgb, g_feat, ctx.want_in)
+        ctx.sv = None
+        return (None, d_p4 if ctx.needs[0] else None, d_dirs if ctx.needs[1] else None) + tuple(grads)
 
 
 class _WNLinear(nn.Module):
@@ -57,6 +153,14 @@ class _HipNet(nn.Module):
       "bf16" - bf16-operand / fp32-accumulate MFMA kernels, bf16 activation workspaces: the throughput path.
     """
     precision = "fp32"
+    # True: every forward under torch.is_grad_enabled() builds an autograd node (gradients to the parameters and to the inputs
+    # that require them: vdn_hip/points.py). False (default): only when a floating-point input requires grad.
+    differentiable = False
+
+    def _graph_wanted(self, *inputs):
+        if not torch.is_grad_enabled():
+            return False
+        return bool(self.differentiable) or any(t is not None and t.is_floating_point() and t.requires_grad for t in inputs)
 
     def _sfx(self):
         if self.precision not in ("fp32", "bf16"):
@@ -101,7 +205,7 @@ class _HipNet(nn.Module):
     def __getstate__(self):
         # device state and Trainer hooks are per-process / per-object: copy.deepcopy and torch.save(module) rebuild them lazily
         st = dict(self.__dict__)
-        for k in ("_img", "_stream_join", "_scratch", "_cold_start"):
+        for k in ("_img", "_stream_join", "_scratch", "_cold_start", "_pt_plans"):
             st.pop(k, None)
         return st
 
@@ -182,8 +286,9 @@ class SDFNetwork(_HipNet):
         a.blob = img.blobs["sdf"].data_ptr()
         return lib.try_call("vdn_sdf_upsample_bf16", a, upsample, _stream())
 
-    def _run(self, mode, pts=None, rays=None, workspace=None, sdf_out=None):
-        """mode 0 -> sdf [P]; mode 1 -> (sdf [P], feat [P,256], normals [P,3]). `rays` = (rays_o, rays_d, z[B,n])."""
+    def _run(self, mode, pts=None, rays=None, workspace=None, sdf_out=None, saves=None):
+        """mode 0 -> sdf [P]; mode 1 -> (sdf [P], feat [P,256], normals [P,3]). `rays` = (rays_o, rays_d, z[B,n]).
+        saves (mode 1): training saves H / V / PE (+ U_pe) of vdn_hip/points.py; with fp32 the S planes join them."""
         img = self._images()
         a = lib.VdnSdfArgs()
         if pts is not None:
@@ -217,14 +322,26 @@ class SDFNetwork(_HipNet):
         if self.precision == "fp32":                 # the bf16 kernel keeps softplus' on the chip
             S = torch.empty(8, Pr, 256, dtype=self._store_dtype(), device=dev)
             a.S = S.data_ptr()
+        if saves is not None:
+            a.H, a.V, a.PE = saves["H"].data_ptr(), saves["V"].data_ptr(), saves["PE"].data_ptr()
+            if "U_pe" in saves:
+                a.U_pe = saves["U_pe"].data_ptr()
+            if S is not None:
+                saves["S"] = S
         lib.call("vdn_sdf_mlp_fwd" + self._sfx(), 1, a, _stream())
         if workspace is not None and S is not None:
             workspace["S"] = S
         return sdf, feat, normals
 
+    def _params(self):
+        return lib.module_params(self)
+
     def forward(self, inputs):
         if inputs.numel() == 0:
             return inputs.new_zeros(0, self.conf["d_out"])
+        if self._graph_wanted(inputs):
+            _require_gpu(inputs, "SDFNetwork input")
+            return _SdfFn.apply(self, "forward", inputs, *self._params())
         sdf, feat, _ = self._run(1, pts=inputs.detach())
         if self.precision == "bf16":
             feat = layout.from_pt32(feat, inputs.shape[0], 256)
@@ -233,6 +350,9 @@ class SDFNetwork(_HipNet):
     def sdf(self, x):
         if x.numel() == 0:
             return x.new_zeros(0, 1)
+        if self._graph_wanted(x):
+            _require_gpu(x, "SDFNetwork input")
+            return _SdfFn.apply(self, "sdf", x, *self._params())
         return self._run(0, pts=x.detach())[:, None]
 
     def sdf_hidden_appearance(self, x):
@@ -241,6 +361,10 @@ class SDFNetwork(_HipNet):
     def gradient(self, x):
         if x.numel() == 0:
             return x.new_zeros(0, 1, 3)
+        if self._graph_wanted(x):
+            # (the reference sets x.requires_grad_(True) on the caller's tensor, fields.py:98; this node does not need to)
+            _require_gpu(x, "SDFNetwork input")
+            return _SdfFn.apply(self, "gradient", x, *self._params())
         _, _, n = self._run(1, pts=x.detach())
         return n.unsqueeze(1)
 
@@ -269,8 +393,9 @@ class RenderingNetwork(_HipNet):
     def _streams(self):
         return images.rendering_streams(**self.conf)
 
-    def _run(self, normals, feat, pts=None, dirs=None, rays=None, extra=None):
-        """`extra` [P,96]: the VDN channels appended to the feature vector (d_feature = 352, renderer.py:247-248)."""
+    def _run(self, normals, feat, pts=None, dirs=None, rays=None, extra=None, saves=None):
+        """`extra` [P,96]: the VDN channels appended to the feature vector (d_feature = 352, renderer.py:247-248).
+        saves: training saves h / small (/ extra) of vdn_hip/points.py."""
         if (extra is not None) != (self.conf["d_feature"] == 352):
             raise ValueError("a d_feature = %d network %s the 96 appended VDN channels" %
                              (self.conf["d_feature"], "needs" if extra is None else "does not take"))
@@ -289,6 +414,10 @@ class RenderingNetwork(_HipNet):
         d_out = self.conf["d_out"]
         out = torch.empty(P, d_out, dtype=torch.float32, device=dev)
         a.out, a.P, a.d_out, a.squeeze_out = out.data_ptr(), P, d_out, int(self.squeeze_out)
+        if saves is not None:
+            a.save_h, a.save_small = saves["h"].data_ptr(), saves["small"].data_ptr()
+            if "extra" in saves:
+                a.save_extra = saves["extra"].data_ptr()
         lib.call("vdn_rendernet_fwd" + self._sfx(), a, _stream())
         return out
 
@@ -297,14 +426,20 @@ class RenderingNetwork(_HipNet):
             _require_gpu(t, "RenderingNetwork " + n)
         if points.shape[0] == 0:
             return points.new_zeros(0, self.conf["d_out"])
-        fv = feature_vectors.detach()
+        if self._graph_wanted(points, normals, view_dirs, feature_vectors):
+            return _RenderingFn.apply(self, points, normals, view_dirs, feature_vectors, *lib.module_params(self))
+        fv, extra = self._feature_planes(feature_vectors.detach())
+        return self._run(normals.detach().contiguous(), fv, pts=points.detach().contiguous(), dirs=view_dirs.detach().contiguous(), extra=extra)
+
+    def _feature_planes(self, fv):
+        """feature_vectors [P, d_feature] -> (the kernel's feature plane, the appended 96 VDN channels or None)."""
         extra = None
         if self.conf["d_feature"] == 352:
             fv, extra = fv[:, :256], fv[:, 256:].contiguous()
         fv = fv.contiguous()
         if self.precision == "bf16":
             fv = layout.to_pt32(fv)
-        return self._run(normals.detach().contiguous(), fv, pts=points.detach().contiguous(), dirs=view_dirs.detach().contiguous(), extra=extra)
+        return fv, extra
 
 
 class NeRF(_HipNet):
@@ -348,7 +483,7 @@ class NeRF(_HipNet):
     def _streams(self):
         return images.nerf_streams(**self.conf)
 
-    def _run(self, pts4=None, dirs=None, rays=None, active=None, scratch=False):
+    def _run(self, pts4=None, dirs=None, rays=None, active=None, scratch=False, saves=None):
         """`active` = (idx int32 [P], n int32 [1]) from vdn_background_active: only those points are evaluated, the other
         outputs stay zero - or, with `scratch`, finite (render_core multiplies them by zero)."""
         img = self._images()
@@ -387,12 +522,16 @@ class NeRF(_HipNet):
         a.density, a.rgb, a.feat, a.P = density.data_ptr(), rgb.data_ptr(), (feat.data_ptr() if feat is not None else None), P
         if active is not None:
             a.active_idx, a.n_active = active[0].data_ptr(), active[1].data_ptr()
+        if saves is not None:         # training saves of vdn_hip/points.py
+            a.save_h, a.save_pe, a.save_feature, a.save_vpe, a.save_hv = (saves[k].data_ptr() for k in ("h", "pe", "feature", "vpe", "hv"))
         lib.call("vdn_nerf_mlp_fwd" + self._sfx(), a, _stream())
         return density, rgb, feat
 
     def forward(self, input_pts, input_views):
         _require_gpu(input_pts, "NeRF input_pts")
         _require_gpu(input_views, "NeRF input_views")
+        if self._graph_wanted(input_pts, input_views):
+            return _NerfFn.apply(self, input_pts, input_views, *lib.module_params(self))
         density, rgb, feat = self._run(pts4=input_pts.detach().contiguous(), dirs=input_views.detach().contiguous())
         return density[:, None], rgb, feat
 

@@ -85,6 +85,180 @@ class _Net:
         return None if b is None else self.grads[id(b)]
 
 
+# ------------------------------------------------------------------------------------------
+# weight-gradient plan: per-network entry builders and the table layout, shared by the ray engine (TrainEngine) and the
+# point engine of the standalone networks (vdn_hip/points.py)
+# ------------------------------------------------------------------------------------------
+# An entry is dict(net, name, rmap, cmap, scale, A, A2, B, B2, bias(bool), Pn, extra_row0); an operand spec is
+# (tensor, element offset of the plane inside the tensor, first column, ld of the plane).
+
+def _sl(t, l, ld=256):
+    return (t, l * t.shape[1] * t.shape[2], 0, ld)           # layer plane of a [L, rows, ld] tensor
+
+
+def _whole(t, c0=0):
+    return (t, 0, c0, t.shape[1])
+
+
+def sdf_dw_entries(H, V, PE, UB, AB, P, Pp, precision):
+    """Entries of the SDF network over P rows (planes of Pp rows): H / V [8,Pp,256] and PE [Pp,64] from the saving forward,
+    UB [Pp*2144] / AB [Pp*2336] from the rbar / fbar chains."""
+    ub_off, off = {}, 0
+    for l, cols in enumerate((64, 256, 256, 256, 288, 256, 256, 256, 256)):
+        ub_off[l] = (off, cols)
+        off += Pp * cols
+    ub = lambda l, c0=0: (UB, ub_off[l][0], c0, ub_off[l][1])
+    ab = lambda l: (AB, 0, 0, 288) if l == 8 else (AB, Pp * 288 + (7 - l) * Pp * 256, 0, 256)
+    maps = images.sdf_layer_maps()
+    # bf16: the SDF forward saves H, V and PE in units of 1/(100 log2 e) (include/vdn_render.h: VdnSdfArgs), so both
+    # segments of every entry below come out 100 log2(e) too large: the finalize scale takes it out
+    unit = 1.0 / images.SDF_UNIT if precision == "bf16" else 1.0
+    maps = [(name, km, nm, sc * unit) for (name, km, nm, sc) in maps]
+    ent = []
+    for l, (name, km, nm, sc) in enumerate(maps):
+        if l == 8:
+            ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=ab(8), B=_sl(H, 7), bias=True, Pn=P))
+            continue
+        A, A2 = ab(l), _sl(V, l)
+        if l == 0:
+            ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=A, B=_whole(PE), A2=A2, B2=ub(0), bias=True, Pn=P))
+        elif l == 4:
+            ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km[:224], scale=sc, A=A, B=_sl(H, 3), A2=A2, B2=ub(4), bias=True, Pn=P))
+            ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km[224:], scale=sc, A=A, B=_whole(PE), A2=A2, B2=ub(4, 224), bias=False, Pn=P))
+        else:
+            ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=A, B=_sl(H, l - 1), A2=A2, B2=ub(l), bias=True, Pn=P))
+    # d W8[row 0, :] += colsum(ub_8) / scale   (u_8 = W8[0,:] / scale)
+    ent.append(dict(net="sdf", name="lin8", rmap=images.ident_map(256), cmap=None, scale=1.0, A=ub(8), B=None, bias=False, Pn=P,
+                    extra_row0=True))
+    return ent
+
+
+def rendering_dw_entries(net, km0, dh, dout, save_h, small, feat, extra, P, d_out):
+    """Entries of one RenderingNetwork (key `net`) over P rows: km0 = k-map of its first forward layer, dh [4,Pp,256] /
+    dout the backward's deltas, save_h [4,Pp,256] / small [Pp,64] the forward's saves, feat [Pp,256] the feature plane it
+    read, extra [Pp,96] the saved appended channels of a d_feature = 352 network (else unused)."""
+    pad = 96 if d_out == 96 else 32
+    I256 = images.ident_map(256)
+    ent = [dict(net=net, name="lin0", rmap=I256, cmap=km0[:256], scale=1.0, A=_sl(dh, 0), B=_whole(feat), bias=True, Pn=P),
+           dict(net=net, name="lin0", rmap=I256, cmap=km0[256:320], scale=1.0, A=_sl(dh, 0), B=_whole(small), bias=False, Pn=P)]
+    if len(km0) > 320:        # d_feature = 352: the appended VDN channels
+        ent.append(dict(net=net, name="lin0", rmap=I256, cmap=km0[320:], scale=1.0, A=_sl(dh, 0), B=_whole(extra), bias=False, Pn=P))
+    for l in (1, 2, 3):
+        ent.append(dict(net=net, name="lin%d" % l, rmap=I256, cmap=I256, scale=1.0, A=_sl(dh, l), B=_sl(save_h, l - 1), bias=True, Pn=P))
+    ent.append(dict(net=net, name="lin4", rmap=images.ident_map(d_out, pad), cmap=I256, scale=1.0, A=_whole(dout), B=_sl(save_h, 3),
+                    bias=True, Pn=P))
+    return ent
+
+
+def nerf_dw_entries(streams, dh, h, pe, dhead, dv, feature, vpe, do, hv, Q, with_dpt):
+    """Entries of the background NeRF over Q rows: the forward's saves (h, pe, feature, vpe, hv) and the backward's deltas
+    (dh, dhead, dv, do); with_dpt: the network has the 96-channel dpt head."""
+    km5, kmv = streams["_km5"], streams["_kmv"]
+    I256 = images.ident_map(256)
+    ent = [dict(net="nerf", name="pts_linears.0", rmap=I256, cmap=images.ident_map(84, 96), scale=1.0, A=_sl(dh, 0), B=_whole(pe), bias=True, Pn=Q)]
+    for i in (1, 2, 3, 4, 6, 7):
+        ent.append(dict(net="nerf", name="pts_linears.%d" % i, rmap=I256, cmap=I256, scale=1.0, A=_sl(dh, i), B=_sl(h, i - 1), bias=True, Pn=Q))
+    ent.append(dict(net="nerf", name="pts_linears.5", rmap=I256, cmap=km5[:96], scale=1.0, A=_sl(dh, 5), B=_whole(pe), bias=True, Pn=Q))
+    ent.append(dict(net="nerf", name="pts_linears.5", rmap=I256, cmap=km5[96:], scale=1.0, A=_sl(dh, 5), B=_sl(h, 4), bias=False, Pn=Q))
+    ent.append(dict(net="nerf", name="feature_linear", rmap=I256, cmap=I256, scale=1.0, A=(dhead, 0, 0, 288), B=_sl(h, 7), bias=True, Pn=Q))
+    ent.append(dict(net="nerf", name="alpha_linear", rmap=images.ident_map(1, 32), cmap=I256, scale=1.0, A=(dhead, 0, 256, 288), B=_sl(h, 7), bias=True, Pn=Q))
+    ent.append(dict(net="nerf", name="views_linears.0", rmap=images.ident_map(128), cmap=kmv[:256], scale=1.0, A=_whole(dv), B=_whole(feature), bias=True, Pn=Q))
+    ent.append(dict(net="nerf", name="views_linears.0", rmap=images.ident_map(128), cmap=kmv[256:], scale=1.0, A=_whole(dv), B=_whole(vpe), bias=False, Pn=Q))
+    ldo = do.shape[1]
+    ent.append(dict(net="nerf", name="rgb_linear", rmap=images.ident_map(3, 32), cmap=images.ident_map(128), scale=1.0, A=(do, 0, 0, ldo), B=_whole(hv), bias=True, Pn=Q))
+    if with_dpt:
+        ent.append(dict(net="nerf", name="dpt_linear", rmap=images.ident_map(96), cmap=images.ident_map(128), scale=1.0, A=(do, 0, 32, ldo), B=_whole(hv), bias=True, Pn=Q))
+    return ent
+
+
+def dw_layout(ent, precision):
+    """K splits, slab / column-sum / map offsets and first workgroup of every entry -> (lay, maps, slab_elems, cs_elems, wgs)."""
+    sfx = "_f32" if precision == "fp32" else "_bf16"
+    all_maps, moff = [], 0
+    slab_elems, cs_elems, wg = 0, 0, 0
+    lay = []
+    for e in ent:
+        mt = len(e["rmap"]) // 32
+        nt = 0 if e["cmap"] is None else len(e["cmap"]) // 32
+        # K splits are sized on the static row counts (the work lists shrink them at run time: ~2.3 K foreground and
+        # ~3.4 K background rows per workgroup on the bench scene). Measured alternatives: equal BYTES per workgroup
+        # (long row ranges for narrow operands) is 15-40 % slower - a stage of a narrow entry is latency-, not
+        # bandwidth-bound - and 2048 / 8192 rows per split are 10 % slower (more slab traffic / a coarser tail).
+        segs = 2 if e.get("A2") is not None else 1
+        K = e["Pn"] * segs
+        pps = _pts_per_split(e["net"], precision)
+        splits = max(1, (K + pps - 1) // pps)
+        if segs == 2:
+            splits += splits % 2          # first half of the splits = segment 1, second half = segment 2
+        lay.append((mt, nt, splits, slab_elems, cs_elems, moff, wg))
+        all_maps.append(np.asarray(e["rmap"], np.int32))
+        moff += mt * 32
+        if nt:
+            all_maps.append(np.asarray(e["cmap"], np.int32))
+            moff += nt * 32
+        slab_elems += splits * mt * 32 * nt * 32
+        cs_elems += splits * mt * 32
+        wg += lib.call_value("vdn_dw_entry_wgs" + sfx, mt, nt, splits)
+    return lay, all_maps, slab_elems, cs_elems, wg
+
+
+def dw_tables(ent, lay, nets, precision, slab, colsum, maps, p_dev, sdf_scale):
+    """GEMM and finalize descriptors of `ent` (numpy arrays with the C layouts). nets: {key: _Net} (the gradient targets);
+    p_dev: per entry, the device row count the GEMM contracts over (0 = all Pn rows); sdf_scale: SDFNetwork.scale."""
+    dw = np.zeros(len(ent), dtype=lib.struct_dtype("VdnDwDesc"))
+    fin = np.zeros(len(ent), dtype=lib.struct_dtype("VdnDwFinalizeDesc"))
+    P4 = lambda spec: spec[0].data_ptr() + spec[0].element_size() * (spec[1] + layout.col_offset_elems(spec[2], precision))
+    for i, e in enumerate(ent):
+        mt, nt, splits, so, co, mo, wg0 = lay[i]
+        d = dw[i]
+        d["A1"], d["lda1"] = P4(e["A"]), e["A"][3]
+        if e["B"] is not None:
+            d["B1"], d["ldb1"] = P4(e["B"]), e["B"][3]
+        if e.get("A2") is not None:
+            d["A2"], d["lda2"], d["B2"], d["ldb2"] = P4(e["A2"]), e["A2"][3], P4(e["B2"]), e["B2"][3]
+        d["P"], d["m_tiles"], d["n_tiles"], d["splits"], d["wg_begin"] = e["Pn"], mt, nt, splits, wg0
+        d["P_dev"] = p_dev[i]
+        d["slab"] = slab.data_ptr() + 4 * so
+        want_cs = e["bias"] or e.get("extra_row0")
+        d["colsum"] = colsum.data_ptr() + 4 * co if want_cs else 0
+        net = nets[e["net"]]
+        fd = fin[i]
+        fd["slab"], fd["colsum"] = d["slab"], d["colsum"]
+        fd["rmap"] = maps.data_ptr() + 4 * mo
+        fd["cmap"] = maps.data_ptr() + 4 * (mo + mt * 32)
+        fd["splits"], fd["M"], fd["N"] = splits, mt * 32, nt * 32
+        fd["scale"] = e["scale"]
+        if e.get("extra_row0"):
+            # colsum(ub_8) / scale joins row 0 of d W8 inside the lin8 entry's own finalize (VdnDwFinalizeDesc.xsum): no
+            # '+=' descriptor, no second finalize launch. (The sums are indexed by the image row = the target column.)
+            main = next(k for k, x in enumerate(ent) if x["net"] == e["net"] and x["name"] == e["name"] and not x.get("extra_row0"))
+            fm = fin[main]
+            fm["xsum"], fm["xsplits"], fm["xM"], fm["xrow"] = d["colsum"], splits, mt * 32, 0
+            fm["xscale"] = 1.0 / sdf_scale
+            fd["slab"], fd["colsum"] = 0, 0
+        else:
+            tgt = net.dw_target(e["name"])
+            fd["target"], fd["t_stride"] = tgt.data_ptr(), tgt.shape[1]
+            if e["bias"]:
+                bt = net.bias_target(e["name"])
+                fd["btarget"], fd["bscale"] = bt.data_ptr(), 1.0
+    return dw, fin
+
+
+def weightnorm_table(nets):
+    """Weight-norm backward descriptors of every weight-normed matrix of `nets` (_Net objects, in order) -> (table, rows)."""
+    rows = []
+    for net in nets:
+        for name, (g, v, b) in net.img.matrices.items():
+            if g is not None:
+                rows.append((g, v, net.img.inv_norm[net.img.r_off[name]:], net.dweff_view(name), net.grads[id(g)], net.grads[id(v)]))
+    wn = np.zeros(len(rows), dtype=lib.struct_dtype("VdnWeightNormBwdDesc"))
+    for i, (g, v, inv, dwe, dg, dv) in enumerate(rows):
+        wn[i]["g"], wn[i]["v"], wn[i]["inv_norm"], wn[i]["dw_eff"] = g.data_ptr(), v.data_ptr(), inv.data_ptr(), dwe.data_ptr()
+        wn[i]["dg"], wn[i]["dv"], wn[i]["rows"], wn[i]["cols"] = dg.data_ptr(), dv.data_ptr(), v.shape[0], v.shape[1]
+    return wn, rows
+
+
 class TrainEngine:
     def __init__(self, renderer, B, dev):
         self.r = renderer
@@ -204,149 +378,33 @@ class TrainEngine:
     # ------------------------------------------------------------------------------------------
     def _build_dw_plan(self):
         w, P, Q = self.w, self.P, self.Q
-        ent = []    # dict(net, name, rmap, cmap, scale, A, A2, B, B2, bias(bool), Pn, extra)
-        # operand spec = (tensor, element offset of the plane inside the tensor, first column, ld of the plane)
         Pp, Qp, prec = self.Pp, self.Qp, self.precision
-        ub_off, off = {}, 0
-        for l, cols in enumerate((64, 256, 256, 256, 288, 256, 256, 256, 256)):
-            ub_off[l] = (off, cols)
-            off += Pp * cols
-        UB = lambda l, c0=0: (w["UB"], ub_off[l][0], c0, ub_off[l][1])
-        AB = lambda l: (w["AB"], 0, 0, 288) if l == 8 else (w["AB"], Pp * 288 + (7 - l) * Pp * 256, 0, 256)
-        sl = lambda t, l, ld=256: (t, l * t.shape[1] * t.shape[2], 0, ld)          # layer plane of a [L, rows, ld] tensor
-        whole = lambda t, c0=0: (t, 0, c0, t.shape[1])
-        maps = images.sdf_layer_maps()
-        # bf16: the SDF forward saves H, V and PE in units of 1/(100 log2 e) (include/vdn_render.h: VdnSdfArgs), so both
-        # segments of every entry below come out 100 log2(e) too large: the finalize scale takes it out
-        unit = 1.0 / images.SDF_UNIT if prec == "bf16" else 1.0
-        maps = [(name, km, nm, sc * unit) for (name, km, nm, sc) in maps]
-        for l, (name, km, nm, sc) in enumerate(maps):
-            if l == 8:
-                ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=AB(8), B=sl(w["H"], 7), bias=True, Pn=P))
-                continue
-            A, A2 = AB(l), sl(w["V"], l)
-            if l == 0:
-                ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=A, B=whole(w["PE"]), A2=A2, B2=UB(0), bias=True, Pn=P))
-            elif l == 4:
-                ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km[:224], scale=sc, A=A, B=sl(w["H"], 3), A2=A2, B2=UB(4), bias=True, Pn=P))
-                ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km[224:], scale=sc, A=A, B=whole(w["PE"]), A2=A2, B2=UB(4, 224), bias=False, Pn=P))
-            else:
-                ent.append(dict(net="sdf", name=name, rmap=nm, cmap=km, scale=sc, A=A, B=sl(w["H"], l - 1), A2=A2, B2=UB(l), bias=True, Pn=P))
-        # d W8[row 0, :] += colsum(ub_8) / scale   (u_8 = W8[0,:] / scale)
-        ent.append(dict(net="sdf", name="lin8", rmap=images.ident_map(256), cmap=None, scale=1.0, A=UB(8), B=None, bias=False, Pn=P,
-                        extra_row0=True))
-
-        def rendering(net, dh, dout, save_h, small, d_out):
-            km0 = self.nets[net].img.streams["fwd"][0].kmap
-            pad = 96 if d_out == 96 else 32
-            ent.append(dict(net=net, name="lin0", rmap=images.ident_map(256), cmap=km0[:256], scale=1.0, A=sl(dh, 0), B=whole(w["feat"]), bias=True, Pn=P))
-            ent.append(dict(net=net, name="lin0", rmap=images.ident_map(256), cmap=km0[256:320], scale=1.0, A=sl(dh, 0), B=whole(small), bias=False, Pn=P))
-            if len(km0) > 320:        # d_feature = 352: the appended VDN channels
-                ent.append(dict(net=net, name="lin0", rmap=images.ident_map(256), cmap=km0[320:], scale=1.0, A=sl(dh, 0), B=whole(w["col_extra"]), bias=False, Pn=P))
-            for l in (1, 2, 3):
-                ent.append(dict(net=net, name="lin%d" % l, rmap=images.ident_map(256), cmap=images.ident_map(256), scale=1.0,
-                                A=sl(dh, l), B=sl(save_h, l - 1), bias=True, Pn=P))
-            ent.append(dict(net=net, name="lin4", rmap=images.ident_map(d_out, pad), cmap=images.ident_map(256), scale=1.0,
-                            A=whole(dout), B=sl(save_h, 3), bias=True, Pn=P))
-        rendering("color", w["col_dh"], w["col_dout"], w["col_h"], w["col_small"], 3)
+        ent = sdf_dw_entries(w["H"], w["V"], w["PE"], w["UB"], w["AB"], P, Pp, prec)
+        ent += rendering_dw_entries("color", self.nets["color"].img.streams["fwd"][0].kmap, w["col_dh"], w["col_dout"], w["col_h"],
+                                    w["col_small"], w["feat"], w.get("col_extra"), P, 3)
         if self.wdepth:
-            rendering("vdn", w["vdn_dh"], w["vdn_dout"], w["vdn_h"], w["vdn_small"], 96)
+            ent += rendering_dw_entries("vdn", self.nets["vdn"].img.streams["fwd"][0].kmap, w["vdn_dh"], w["vdn_dout"], w["vdn_h"],
+                                        w["vdn_small"], w["feat"], None, P, 96)
         if "nerf" in self.nets:
-            st = self.nets["nerf"].img.streams
-            km5, kmv = st["_km5"], st["_kmv"]
-            I256 = images.ident_map(256)
-            dh, h = w["nf_dh"], w["nf_h"]
-            ent.append(dict(net="nerf", name="pts_linears.0", rmap=I256, cmap=images.ident_map(84, 96), scale=1.0, A=sl(dh, 0), B=whole(w["nf_pe"]), bias=True, Pn=Q))
-            for i in (1, 2, 3, 4, 6, 7):
-                ent.append(dict(net="nerf", name="pts_linears.%d" % i, rmap=I256, cmap=I256, scale=1.0, A=sl(dh, i), B=sl(h, i - 1), bias=True, Pn=Q))
-            ent.append(dict(net="nerf", name="pts_linears.5", rmap=I256, cmap=km5[:96], scale=1.0, A=sl(dh, 5), B=whole(w["nf_pe"]), bias=True, Pn=Q))
-            ent.append(dict(net="nerf", name="pts_linears.5", rmap=I256, cmap=km5[96:], scale=1.0, A=sl(dh, 5), B=sl(h, 4), bias=False, Pn=Q))
-            ent.append(dict(net="nerf", name="feature_linear", rmap=I256, cmap=I256, scale=1.0, A=(w["nf_dhead"], 0, 0, 288), B=sl(h, 7), bias=True, Pn=Q))
-            ent.append(dict(net="nerf", name="alpha_linear", rmap=images.ident_map(1, 32), cmap=I256, scale=1.0, A=(w["nf_dhead"], 0, 256, 288), B=sl(h, 7), bias=True, Pn=Q))
-            ent.append(dict(net="nerf", name="views_linears.0", rmap=images.ident_map(128), cmap=kmv[:256], scale=1.0, A=whole(w["nf_dv"]), B=whole(w["nf_feature"]), bias=True, Pn=Q))
-            ent.append(dict(net="nerf", name="views_linears.0", rmap=images.ident_map(128), cmap=kmv[256:], scale=1.0, A=whole(w["nf_dv"]), B=whole(w["nf_vpe"]), bias=False, Pn=Q))
-            ldo = w["nf_do"].shape[1]
-            ent.append(dict(net="nerf", name="rgb_linear", rmap=images.ident_map(3, 32), cmap=images.ident_map(128), scale=1.0, A=(w["nf_do"], 0, 0, ldo), B=whole(w["nf_hv"]), bias=True, Pn=Q))
-            if self.wdepth:
-                ent.append(dict(net="nerf", name="dpt_linear", rmap=images.ident_map(96), cmap=images.ident_map(128), scale=1.0, A=(w["nf_do"], 0, 32, ldo), B=whole(w["nf_hv"]), bias=True, Pn=Q))
+            ent += nerf_dw_entries(self.nets["nerf"].img.streams, w["nf_dh"], w["nf_h"], w["nf_pe"], w["nf_dhead"], w["nf_dv"],
+                                   w["nf_feature"], w["nf_vpe"], w["nf_do"], w["nf_hv"], Q, self.wdepth)
 
         # ---- tables
         dev = self.dev
-        all_maps, moff = [], 0
-        dw = np.zeros(len(ent), dtype=lib.struct_dtype("VdnDwDesc"))
-        fin = np.zeros(len(ent), dtype=lib.struct_dtype("VdnDwFinalizeDesc"))
-        slab_elems, cs_elems, wg = 0, 0, 0
-        lay = []
         # Two launch groups: the SDF network's entries (the critical path into the next step: its sampler only needs the SDF
         # weights) and the rest (colour / VDN heads, background network). `ent` lists the SDF entries first, so the group
         # tables are a prefix and a suffix of the full table; the suffix copy numbers its workgroups from its own zero.
         n_sdf = sum(1 for e in ent if e["net"] == "sdf")
         assert all(e["net"] == "sdf" for e in ent[:n_sdf]) and all(e["net"] != "sdf" for e in ent[n_sdf:])
-        for i, e in enumerate(ent):
-            mt = len(e["rmap"]) // 32
-            nt = 0 if e["cmap"] is None else len(e["cmap"]) // 32
-            # K splits are sized on the static row counts (the work lists shrink them at run time: ~2.3 K foreground and
-            # ~3.4 K background rows per workgroup on the bench scene). Measured alternatives: equal BYTES per workgroup
-            # (long row ranges for narrow operands) is 15-40 % slower - a stage of a narrow entry is latency-, not
-            # bandwidth-bound - and 2048 / 8192 rows per split are 10 % slower (more slab traffic / a coarser tail).
-            segs = 2 if e.get("A2") is not None else 1
-            K = e["Pn"] * segs
-            pps = _pts_per_split(e["net"], prec)
-            splits = max(1, (K + pps - 1) // pps)
-            if segs == 2:
-                splits += splits % 2          # first half of the splits = segment 1, second half = segment 2
-            lay.append((mt, nt, splits, slab_elems, cs_elems, moff, wg))
-            all_maps.append(np.asarray(e["rmap"], np.int32))
-            moff_r = moff
-            moff += mt * 32
-            if nt:
-                all_maps.append(np.asarray(e["cmap"], np.int32))
-                moff += nt * 32
-            slab_elems += splits * mt * 32 * nt * 32
-            cs_elems += splits * mt * 32
-            wg += lib.call_value("vdn_dw_entry_wgs" + self.sfx, mt, nt, splits)
+        lay, all_maps, slab_elems, cs_elems, wg = dw_layout(ent, prec)
         self.dw_total_wgs = wg
         self.maps = torch.from_numpy(np.concatenate(all_maps)).to(dev)
         self.slab = torch.empty(max(slab_elems, 1), dtype=torch.float32, device=dev)
         self.colsum = torch.empty(max(cs_elems, 1), dtype=torch.float32, device=dev)
-        P4 = lambda spec: spec[0].data_ptr() + spec[0].element_size() * (spec[1] + layout.col_offset_elems(spec[2], prec))
-        self.dw_list_kind = []
-        for i, e in enumerate(ent):
-            mt, nt, splits, so, co, mo, wg0 = lay[i]
-            d = dw[i]
-            d["A1"], d["lda1"] = P4(e["A"]), e["A"][3]
-            if e["B"] is not None:
-                d["B1"], d["ldb1"] = P4(e["B"]), e["B"][3]
-            if e.get("A2") is not None:
-                d["A2"], d["lda2"], d["B2"], d["ldb2"] = P4(e["A2"]), e["A2"][3], P4(e["B2"]), e["B2"][3]
-            d["P"], d["m_tiles"], d["n_tiles"], d["splits"], d["wg_begin"] = e["Pn"], mt, nt, splits, wg0
-            # rows of the compact work lists (device scalars written by the forward)
-            d["P_dev"] = (w["bg_active"] if e["net"] == "nerf" else w["fg_active"])[1].data_ptr()
-            self.dw_list_kind.append("bg" if e["net"] == "nerf" else "fg")
-            d["slab"] = self.slab.data_ptr() + 4 * so
-            want_cs = e["bias"] or e.get("extra_row0")
-            d["colsum"] = self.colsum.data_ptr() + 4 * co if want_cs else 0
-            net = self.nets[e["net"]]
-            fd = fin[i]
-            fd["slab"], fd["colsum"] = d["slab"], d["colsum"]
-            fd["rmap"] = self.maps.data_ptr() + 4 * mo
-            fd["cmap"] = self.maps.data_ptr() + 4 * (mo + mt * 32)
-            fd["splits"], fd["M"], fd["N"] = splits, mt * 32, nt * 32
-            fd["scale"] = e["scale"]
-            if e.get("extra_row0"):
-                # colsum(ub_8) / scale joins row 0 of d W8 inside the lin8 entry's own finalize (VdnDwFinalizeDesc.xsum): no
-                # '+=' descriptor, no second finalize launch. (The sums are indexed by the image row = the target column.)
-                main = next(k for k, x in enumerate(ent) if x["net"] == e["net"] and x["name"] == e["name"] and not x.get("extra_row0"))
-                fm = fin[main]
-                fm["xsum"], fm["xsplits"], fm["xM"], fm["xrow"] = d["colsum"], splits, mt * 32, 0
-                fm["xscale"] = 1.0 / float(self.r.sdf_network.scale)
-                fd["slab"], fd["colsum"] = 0, 0
-            else:
-                tgt = net.dw_target(e["name"])
-                fd["target"], fd["t_stride"] = tgt.data_ptr(), tgt.shape[1]
-                if e["bias"]:
-                    bt = net.bias_target(e["name"])
-                    fd["btarget"], fd["bscale"] = bt.data_ptr(), 1.0
+        # rows of the compact work lists (device scalars written by the forward)
+        self.dw_list_kind = ["bg" if e["net"] == "nerf" else "fg" for e in ent]
+        p_dev = [(w["bg_active"] if k == "bg" else w["fg_active"])[1].data_ptr() for k in self.dw_list_kind]
+        dw, fin = dw_tables(ent, lay, self.nets, prec, self.slab, self.colsum, self.maps, p_dev, float(self.r.sdf_network.scale))
         self.dw_table = torch.from_numpy(dw.view(np.uint8)).to(dev)
         wg_sdf = int(dw[n_sdf]["wg_begin"]) if n_sdf < len(ent) else wg
         rest = dw[n_sdf:].copy()
@@ -387,16 +445,12 @@ class TrainEngine:
         self.fin_groups = {k: (torch.from_numpy(v.view(np.uint8).copy()).to(dev), len(v), int(max(len(e["rmap"]) for e in mm[k])),
                                bool((v["accumulate"] != 0).any())) for k, v in fg.items() if len(v) and len(mm[k])}
         # weight-norm backward table
-        rows, row_group = [], []
+        row_group = []
         for key, net in self.nets.items():          # "sdf" first (dict order of self.nets)
             for name, (g, v, b) in net.img.matrices.items():
                 if g is not None:
-                    rows.append((g, v, net.img.inv_norm[net.img.r_off[name]:], net.dweff_view(name), net.grads[id(g)], net.grads[id(v)]))
                     row_group.append(("sdf",) if key == "sdf" else ("rest", "nerf" if key == "nerf" else "heads"))
-        wn = np.zeros(len(rows), dtype=lib.struct_dtype("VdnWeightNormBwdDesc"))
-        for i, (g, v, inv, dwe, dg, dv) in enumerate(rows):
-            wn[i]["g"], wn[i]["v"], wn[i]["inv_norm"], wn[i]["dw_eff"] = g.data_ptr(), v.data_ptr(), inv.data_ptr(), dwe.data_ptr()
-            wn[i]["dg"], wn[i]["dv"], wn[i]["rows"], wn[i]["cols"] = dg.data_ptr(), dv.data_ptr(), v.shape[0], v.shape[1]
+        wn, rows = weightnorm_table(self.nets.values())
         self.wn_table = torch.from_numpy(wn.view(np.uint8).copy() if len(rows) else np.zeros(8, np.uint8)).to(dev)
         self.n_wn = len(rows)
         self.wn_max_rows = max([r[1].shape[0] for r in rows] + [1])
