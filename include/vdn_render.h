@@ -787,6 +787,57 @@ typedef struct {
 int vdn_mesh_mc_count(const VdnMeshMcArgs* args_host, void* stream);
 int vdn_mesh_mc_emit(const VdnMeshMcArgs* args_host, void* stream);
 
+
+/* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
+ * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,
+ * c2w = make_c2w(r, t) @ init_c2w (lie_group_helper.py Exp in the reference's own fp32 expression: n = |r| + 1e-15,
+ * R = I + sin(n)/n K + (1 - cos n)/n^2 K^2, K = [r]x). Same output row, near / far and pixel / mask / feature gathers. */
+typedef struct {
+    const float* pixels_x;     /* [B] */
+    const float* pixels_y;     /* [B] */
+    const float* intrinsic_inv;/* [3,3] row-major */
+    const float* r;            /* [3] axis-angle of the camera (LearnPose.r[i]) */
+    const float* t;            /* [3] translation (LearnPose.t[i]) */
+    const float* init_c2w;     /* [4,4] row-major or NULL (identity) */
+    const float* image;        /* [H,W,3] or NULL */
+    const float* mask;         /* [H,W,mask_ch] or NULL (then mask = 1) */
+    const float* feats;        /* [H,W,C] or NULL */
+    float* out;                /* [B, out_ld] */
+    float* near;               /* [B] or NULL */
+    float* far;                /* [B] or NULL */
+    int32_t B, H, W, C, mask_ch, out_ld;
+} VdnGenRaysPoseArgs;
+int vdn_gen_rays_pose(const VdnGenRaysPoseArgs* args_host, void* stream);
+
+/* vdn_pose_adjoint: d loss / d (r, t) of camera `cam` from the ray adjoints (vdn_ray_adjoint's d_rays_o, d_rays_d, d_z, d_z_out)
+ * of rays made by vdn_gen_rays_pose with the same pixels and parameters. The chain, in reverse:
+ *   depths -> near / far (NeuSRenderer._attach_rays): z_out = far * c + 1/n_samples, c = (z_out - 1/n_samples) / far (0 where
+ *     far == 0); the inside depths only with n_importance == 0: z = near + (far - near) * lin_samples;
+ *   near / far -> rays (near_far_from_sphere): mid = -(o.d)/(d.d), near = mid - 1, far = mid + 1;
+ *   rays -> c2w: rays_d = c2w[:3,:3] normalize(K^-1 p), rays_o = c2w[:3,3];
+ *   c2w -> (r, t): adjoints of `@ init_c2w` and of Exp (at r = 0 exactly: dR/dr_k = [e_k]x, as torch's autograd gives).
+ * Two launches on the stream: a wave per ray writes the ray's fp64 terms of d c2w to `scratch`, then ONE workgroup sums them
+ * in a fixed order (no atomics: bit-reproducible) and applies the pose adjoint. Writes dense [n_cams,3] gradients, zero outside
+ * row `cam`. */
+typedef struct {
+    const float* pixels_x;     /* [B] */
+    const float* pixels_y;     /* [B] */
+    const float* intrinsic_inv;/* [3,3] */
+    const float* r;            /* [3] camera cam's parameters */
+    const float* t;            /* [3] */
+    const float* init_c2w;     /* [4,4] or NULL */
+    const float* d_rays_o;     /* [B,3] */
+    const float* d_rays_d;     /* [B,3] */
+    const float* d_z;          /* [B,N] or NULL (read only when n_importance == 0) */
+    const float* lin_samples;  /* [N] torch.linspace(0, 1, n_samples) (n_importance == 0) */
+    const float* d_z_out;      /* [B,O] or NULL */
+    const float* z_out;        /* [B,O] outside depths of the step (with d_z_out) */
+    float* grad_r;             /* [n_cams,3] out */
+    float* grad_t;             /* [n_cams,3] out */
+    double* scratch;           /* [B,12] workspace */
+    int32_t B, N, O, n_samples, n_importance, cam, n_cams, _pad;
+} VdnPoseAdjointArgs;
+int vdn_pose_adjoint(const VdnPoseAdjointArgs* args_host, void* stream);
 #ifdef __cplusplus
 }
 #endif

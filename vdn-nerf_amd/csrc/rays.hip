@@ -10,6 +10,7 @@
 // -ffp-contract=off so that mul/add pairs round like the reference's separate aten ops.
 #include "k_ray_rows.h"
 #include "k_composite_row.h"
+#include "k_pixel_gather.h"
 
 namespace vdn {
 
@@ -259,20 +260,9 @@ __global__ void gen_rays_kernel(GenRaysArgs a) {
         o[r] = org[r];
         o[3 + r] = d[r];
     }
-    const int xi = min(max((int)x, 0), a.W - 1), yi = min(max((int)y, 0), a.H - 1);
-    const long pix = (long)yi * a.W + xi;
-    if (a.out_ld > 6) o[6] = a.mask ? a.mask[pix * a.mask_ch] : 1.0f;
-    if (a.image != nullptr && a.out_ld >= 10) {
-        o[7] = a.image[pix * 3];
-        o[8] = a.image[pix * 3 + 1];
-        o[9] = a.image[pix * 3 + 2];
-    }
-    if (a.feats != nullptr)
-        for (int ch = 0; ch < a.C; ++ch) o[10 + ch] = a.feats[pix * a.C + ch];
+    gather_pixel_row(a, x, y, o);
     if (a.near != nullptr && a.far != nullptr) {          // dataset.py:111-118
-        const float aa = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        const float bb = 2.0f * (org[0] * d[0] + org[1] * d[1] + org[2] * d[2]);
-        const float mid = 0.5f * (-bb) / aa;
+        const float mid = sphere_mid(org, d);
         a.near[i] = mid - 1.0f;
         a.far[i] = mid + 1.0f;
     }

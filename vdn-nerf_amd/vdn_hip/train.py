@@ -485,7 +485,7 @@ class TrainEngine:
         return w
 
     def forward(self, rays_o, rays_d, z, z_out, background_rgb, cos_anneal_ratio, skip_far=False, ray_grads=False, pending_merge=None,
-                after_sdf=None, fuse_loss=None, before_heads=None, rest_normals=False, cos_anneal_dev=None):
+                after_sdf=None, fuse_loss=None, before_heads=None, rest_normals=False, cos_anneal_dev=None, ray_grads_compact=False):
         """Differentiable part of render() at detached z [B,N] (+ z_out [B,O]); returns the output tensors.
         skip_far (the Trainer's hot loop): inside samples beyond the relaxed sphere (|p| >= 1.2: inside_sphere = 0 and
         relax_inside_sphere = 0, renderer.py:284-286) enter the loss only through exact zeros, so the SDF / colour / VDN
@@ -500,10 +500,14 @@ class TrainEngine:
         vdn_composite_bwd_train in backward() (the loss gradients are made inside them). Needs skip_far (the eikonal denominator
         is the foreground list's length).
         cos_anneal_dev: a [1] device tensor the compositor (and its adjoint in backward()) reads cos_anneal_ratio from instead of the
-        by-value argument (VdnCompositeArgs.cos_anneal_dev): launches captured in a HIP graph follow a changing ratio."""
+        by-value argument (VdnCompositeArgs.cos_anneal_dev): launches captured in a HIP graph follow a changing ratio.
+        ray_grads_compact (the Trainer's learnable-pose step): allows ray_grads with skip_far. The samples the work list skips enter
+        the loss only through inside_sphere = relax_inside_sphere = 0, so their point / direction / section-length adjoints are
+        exactly zero: backward() zeroes those rows of the networks' input adjoints and vdn_ray_adjoint reads zeros there. The
+        fused compositor kernels stay off with ray adjoints."""
         r, w, B, N, T = self.r, self.w, self.B, self.N, self.T
         st = _stream()
-        if ray_grads and skip_far:
+        if ray_grads and skip_far and not ray_grads_compact:
             raise ValueError("ray gradients need every inside sample evaluated (skip_far=False)")
         self._ray_grads = bool(ray_grads)
         self._car_dev = cos_anneal_dev
@@ -987,6 +991,11 @@ class TrainEngine:
                 b.rays_d, b.n_per_ray, b.acc_pts = rays_d.data_ptr(), self.N, int(accumulate)
                 b.d_pts, b.d_dirs = w["d_pts"].data_ptr(), w["d_dirs"].data_ptr()
             lib.call("vdn_rendernet_bwd" + self.sfx, self._fg(b), st)
+        if rg and self._fg_compact:
+            # samples off the foreground work list enter the loss through exact zeros: their adjoints stay zero (the heads and
+            # the SDF backward write the listed rows only)
+            w["d_pts"].zero_()
+            w["d_dirs"].zero_()
         # d_normals already holds the alpha + eikonal parts: the heads add their input gradients into it;
         # d_featvec is overwritten by the first head and accumulated by the second
         rnet_bwd("color", w["d_color"], w["col_out"], w["col_h"], w["col_dout"], w["col_dh"], 3, r.color_network, False)

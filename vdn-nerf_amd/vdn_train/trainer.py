@@ -32,16 +32,61 @@ DEFAULT_TRAIN_CONF = dict(learning_rate=5e-4, learning_rate_alpha=0.05, end_iter
                           igr_weight=0.1, mask_weight=0.0, use_white_bkgd=True, extract_depth=False, depth_start_iter=5000)
 
 
+# learnable cameras (dpt_runner.py:77-97, the `*_learn_*` configurations' values)
+DEFAULT_POSE_CONF = dict(focal_learnable=True, poses_learnable=True, pose_lr=5e-4, focal_lr=5e-4, pose_lr_gamma=0.9, focal_lr_gamma=0.9,
+                         step_size=5000, start_refine_pose_iter=-1, start_refine_focal_iter=-1, use_mask=False)
+
 _stream = lib.stream_handle          # the HIP handle of torch's current stream
 
 
+class MultiStepSchedule:
+    """torch.optim.lr_scheduler.MultiStepLR restated on a host float: the same recursion (at each step(), lr *= gamma ** (times
+    the new epoch appears among the milestones)), starting at epoch 0 like a freshly constructed scheduler (whose initial step
+    already applies a milestone at 0). loaded_lr: the runner's resume order - scheduler constructed, THEN the optimizer's saved
+    state loaded (dpt_runner.py:386-387), which puts back the saved, already decayed lr: epoch 0 at that lr, no milestone
+    re-applied."""
+
+    def __init__(self, base_lr, milestones, gamma, loaded_lr=None):
+        from collections import Counter
+        self.milestones, self.gamma = Counter(milestones), gamma
+        self.base_lr, self.lr, self.last_epoch = base_lr, base_lr, -1
+        self.step()
+        if loaded_lr is not None:
+            self.lr = loaded_lr
+
+    def step(self):
+        self.last_epoch += 1
+        if self.last_epoch in self.milestones:
+            self.lr = self.lr * self.gamma ** self.milestones[self.last_epoch]
+
+
+def pose_schedules(conf, pose_lr=None, focal_lr=None):
+    """dpt_runner.py:93-97: the pose milestones are range(warm_up_end, end_iter, step_size); the focal ones are the TUPLE
+    (warm_up_end, end_iter, step_size) as the reference writes it. pose_lr / focal_lr: the learning rates of a loaded
+    optimizer_pose / optimizer_focal state (a resume). -> (pose, focal) MultiStepSchedule."""
+    c = conf
+    pose = MultiStepSchedule(c["pose_lr"], range(c["warm_up_end"], c["end_iter"], c["step_size"]), c["pose_lr_gamma"], pose_lr)
+    focal = MultiStepSchedule(c["focal_lr"], (c["warm_up_end"], c["end_iter"], c["step_size"]), c["focal_lr_gamma"], focal_lr)
+    return pose, focal
+
+
+def refine_pose_now(iter_step, start_refine_pose_iter):
+    """dpt_runner.py:246-253: the pose optimizer zeroes and steps only when iter_step > start_refine_pose_iter."""
+    return iter_step > start_refine_pose_iter
+
+
 class Trainer:
-    def __init__(self, renderer, batch_size, device, conf=None, world_size=1, rank=0, collectives=None, overlap=None):
+    def __init__(self, renderer, batch_size, device, conf=None, world_size=1, rank=0, collectives=None, overlap=None, cameras=None):
         """collectives: None = on when world_size > 1; True runs the collective calls also in a one-rank group (the RCCL path
         on a single GPU). overlap: None = on (VDN_OVERLAP=0 turns it off) - see the module docstring; after train_step the
         colour / VDN / background parameters and gradients are then complete on the side stream: join() before touching them
         (state_dict, load_checkpoint, TrainEngine.param_grads and the networks' own weight-image accessor do: render(),
-        validate_image ... right after train_step are ordered behind the update without an explicit join())."""
+        validate_image ... right after train_step are ordered behind the update without an explicit join()).
+        cameras: a dpt_models.poses.LearnableRays (LearnPose + LearnIntrin + the resident RaysGenerator) for the reference's
+        learnable-pose runs: train_step_at() then makes the rays on the device from the current poses and refines them
+        (see _init_cameras)."""
+        if cameras is not None and world_size > 1:
+            raise NotImplementedError("learnable poses with data parallelism (world_size > 1)")
         self.r, self.B, self.dev = renderer, batch_size, torch.device(device)
         self.conf = dict(DEFAULT_TRAIN_CONF)
         self.conf.update(conf or {})
@@ -125,6 +170,265 @@ class Trainer:
         self.g_color, self.g_weights, self.g_eik, self.scalars = f(B, 3), f(B, T), f(1), f(6)
         self.g_feats = f(B, 96) if self.engine.wdepth else None
         self.bg = torch.ones(3, device=self.dev) if self.conf["use_white_bkgd"] else None
+        self.cameras = None
+        if cameras is not None:
+            self._init_cameras(cameras)
+
+    # ---- learnable cameras (dpt_runner.py:77-97, 197-259, 383-401)
+    def _init_cameras(self, cameras):
+        """LearnPose.r / .t become views of ONE flat pose buffer [r (n*3) | t (n*3)] with its own Adam moments; the rays of a step
+        come from vdn_gen_rays_pose and the pose gradient from vdn_pose_adjoint. LearnIntrin.fx stays fixed: the reference builds
+        K from fx.item() (poses.py:80-93), no gradient reaches it and optimizer_focal never steps."""
+        for k, v in DEFAULT_POSE_CONF.items():
+            self.conf.setdefault(k, v)
+        pn = cameras.pose_net
+        if pn.r.device != self.dev:
+            raise ValueError("the pose network must live on %s" % self.dev)
+        self.cameras, self.pose_net, self.intrin_net = cameras, pn, cameras.intrin_net
+        n = pn.num_cams
+        self._pose_flat = torch.empty(6 * n, dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            for j, p in enumerate((pn.r, pn.t)):
+                self._pose_flat[3 * n * j:3 * n * (j + 1)].copy_(p.detach().reshape(-1))
+                p.data = self._pose_flat[3 * n * j:3 * n * (j + 1)].view(n, 3)
+        self._pose_grad = torch.zeros_like(self._pose_flat)
+        self._pose_exp_avg = torch.zeros_like(self._pose_flat)
+        self._pose_exp_avg_sq = torch.zeros_like(self._pose_flat)
+        # Adam steps only parameters that require a gradient (learn_R / learn_t): element ranges of the flat buffer
+        self._pose_ranges = [(3 * n * j, 3 * n * (j + 1)) for j, p in enumerate((pn.r, pn.t)) if p.requires_grad]
+        self._pose_steps = 0
+        self.poses_iter_step = 0
+        self._set_intrinsics()
+        self.pose_sched, self.focal_sched = pose_schedules(self.conf)
+        self._sched_started = False
+        px = cameras.pixels
+        self._pixels = px
+        self._ld = 10 + (px.C if px.with_depth else 1)
+        self._rows = torch.zeros(self.B, self._ld, dtype=torch.float32, device=self.dev)
+        self._near, self._far = torch.empty(self.B, 1, device=self.dev), torch.empty(self.B, 1, device=self.dev)
+        self._init_c2w = pn.init_c2w.detach().to(self.dev).contiguous() if pn.init_c2w is not None else None
+
+    def _set_intrinsics(self):
+        # K^-1 of LearnIntrin() inverted on the host, as vdn_train.rays.RaysGenerator does (poses.py:107)
+        K = self.intrin_net().detach().cpu().float()
+        self._intrin_inv = torch.inverse(K)[:3, :3].contiguous().to(self.dev)
+
+    def pose_lr(self):
+        return self.pose_sched.lr
+
+    def focal_lr(self):
+        return self.focal_sched.lr
+
+    def gen_rays_at(self, img_idx, px, py):
+        """Rays of camera img_idx from its current (r, t) (vdn_gen_rays_pose) -> (rows [B, 10 + C], near [B,1], far [B,1]);
+        the buffers are the Trainer's own, rewritten by the next step."""
+        px, py = (torch.as_tensor(p, dtype=torch.float32).to(self.dev).contiguous() for p in (px, py))
+        B = px.numel()
+        rows = self._rows if B == self.B else torch.zeros(B, self._ld, dtype=torch.float32, device=self.dev)
+        near, far = (self._near, self._far) if B == self.B else (torch.empty(B, 1, device=self.dev), torch.empty(B, 1, device=self.dev))
+        g, n, i = self._pixels, self.pose_net.num_cams, int(img_idx)
+        a = lib.VdnGenRaysPoseArgs()
+        a.pixels_x, a.pixels_y, a.intrinsic_inv = px.data_ptr(), py.data_ptr(), self._intrin_inv.data_ptr()
+        a.r, a.t = self._pose_flat[3 * i:].data_ptr(), self._pose_flat[3 * n + 3 * i:].data_ptr()
+        a.init_c2w = self._init_c2w[i].data_ptr() if self._init_c2w is not None else None
+        a.image = g.images[i].data_ptr()
+        if g.masks is not None:
+            a.mask, a.mask_ch = g.masks[i].data_ptr(), g.masks.shape[-1]
+        if g.with_depth:
+            a.feats, a.C = g.depth_feats[i].data_ptr(), g.C
+        a.out, a.near, a.far = rows.data_ptr(), near.data_ptr(), far.data_ptr()
+        a.B, a.H, a.W, a.out_ld = B, g.H, g.W, self._ld
+        lib.call("vdn_gen_rays_pose", a, _stream())
+        self._last_pixels = (px, py)
+        return rows, near, far
+
+    def pose_adjoint(self, img_idx, px, py, d_rays_o, d_rays_d, d_z=None, d_z_out=None, z_out=None, out=None):
+        """vdn_pose_adjoint: ray adjoints of camera img_idx's rays -> dense [6n] gradient [r (n*3) | t (n*3)] (zero outside
+        camera img_idx), the layout of the flat pose buffer."""
+        r, n, i = self.r, self.pose_net.num_cams, int(img_idx)
+        out = self._pose_grad if out is None else out
+        a = lib.VdnPoseAdjointArgs()
+        a.pixels_x, a.pixels_y, a.intrinsic_inv = px.data_ptr(), py.data_ptr(), self._intrin_inv.data_ptr()
+        a.r, a.t = self._pose_flat[3 * i:].data_ptr(), self._pose_flat[3 * n + 3 * i:].data_ptr()
+        a.init_c2w = self._init_c2w[i].data_ptr() if self._init_c2w is not None else None
+        a.d_rays_o, a.d_rays_d = d_rays_o.contiguous().data_ptr(), d_rays_d.contiguous().data_ptr()
+        if d_z is not None and r.n_importance == 0:
+            a.d_z, a.lin_samples = d_z.data_ptr(), r._consts(self.dev)["lin_samples"].data_ptr()
+            a.N = d_z.shape[1]
+        if d_z_out is not None:
+            a.d_z_out, a.z_out, a.O = d_z_out.data_ptr(), z_out.data_ptr(), d_z_out.shape[1]
+        a.grad_r, a.grad_t = out.data_ptr(), out[3 * n:].data_ptr()
+        B = px.numel()
+        if self.__dict__.get("_pose_scratch") is None or self._pose_scratch.numel() < 12 * B:
+            self._pose_scratch = torch.empty(12 * B, dtype=torch.float64, device=self.dev)
+        a.scratch = self._pose_scratch.data_ptr()
+        a.B, a.n_samples, a.n_importance, a.cam, a.n_cams = px.numel(), r.n_samples, r.n_importance, i, n
+        lib.call("vdn_pose_adjoint", a, _stream())
+        return out
+
+    def train_step_at(self, img_idx, px=None, py=None, t_rand=None, t_rand_out=None):
+        """One iteration of dpt_runner.py:197-259 with learnable cameras: rays of camera img_idx from its current pose
+        (vdn_gen_rays_pose; px / py: pixel coordinates, random when None), columns split as the runner does (mask thresholded
+        at 0.1 with use_mask, else ones), then
+          iter_step <= start_refine_pose_iter: the fixed-pose step (train_step: foreground work list, fused compositor) - the
+            reference discards the pose gradients of those steps;
+          after that: the ray-gradient step on the work list (TrainEngine.forward(ray_grads_compact=True)), vdn_ray_adjoint ->
+            vdn_pose_adjoint -> Adam on the pose buffer at the MultiStepLR rate.
+        -> device tensor [loss, color_loss, psnr, eikonal, depth_loss, mask_loss]."""
+        if self.cameras is None:
+            raise RuntimeError("train_step_at needs Trainer(cameras=LearnableRays(...))")
+        if not self._sched_started:                   # dpt_runner.py:175: update_learning_rate() in front of the loop
+            self.pose_sched.step()
+            self.focal_sched.step()
+            self._sched_started = True
+        g = self._pixels
+        if px is None:
+            px = torch.randint(low=0, high=g.W, size=[self.B], device=self.dev).float()
+            py = torch.randint(low=0, high=g.H, size=[self.B], device=self.dev).float()
+        rows, near, far = self.gen_rays_at(img_idx, px, py)
+        px, py = self._last_pixels
+        rays_o, rays_d, true_rgb = rows[:, 0:3], rows[:, 3:6], rows[:, 7:10]
+        mask = (rows[:, 6:7] > 0.1).float() if self.conf["use_mask"] else None
+        gt_feats = rows[:, 10:] if g.with_depth else None
+        if refine_pose_now(self.iter_step, self.conf["start_refine_pose_iter"]):
+            sc = self._pose_train_step(int(img_idx), px, py, rays_o, rays_d, near, far, true_rgb, gt_feats, mask, t_rand, t_rand_out)
+        else:
+            sc = self.train_step(rays_o, rays_d, near, far, true_rgb, gt_feats=gt_feats, mask=mask, t_rand=t_rand, t_rand_out=t_rand_out)
+        self.poses_iter_step += 1
+        self.pose_sched.step()                        # dpt_runner.py:263: update_learning_rate() after every iteration
+        self.focal_sched.step()
+        return sc
+
+    def _pose_train_step(self, img_idx, px, py, rays_o, rays_d, near, far, true_rgb, gt_feats, mask, t_rand, t_rand_out):
+        """train_step's arithmetic with ray gradients, all on the caller's stream: sampler -> forward on the foreground work list
+        with the ray workspaces -> compositor -> loss kernel -> backward (every network's weight gradients, then vdn_ray_adjoint)
+        -> vdn_pose_adjoint -> Adam on the networks (their step groups) and on the pose buffer -> weight images."""
+        r, eng, st, B = self.r, self.engine, _stream(), self.B
+        pk = lambda t, shape: None if t is None else t.reshape(shape).contiguous()
+        rays_o, rays_d, near, far = pk(rays_o, (B, 3)), pk(rays_d, (B, 3)), pk(near, (B, 1)), pk(far, (B, 1))
+        true_rgb, mask = pk(true_rgb, (B, 3)), pk(mask, (B, 1))
+        gt_feats = pk(gt_feats, (B, gt_feats.shape[1])) if gt_feats is not None else None
+        if r.perturb > 0 and t_rand is None and t_rand_out is None and r.n_outside > 0:
+            if self._jitter is None or self._jitter_next >= self._jitter.shape[0]:
+                self._jitter, self._jitter_next = torch.rand(32, B * (1 + r.n_outside), device=self.dev), 0
+            u = self._jitter[self._jitter_next]
+            self._jitter_next += 1
+            t_rand, t_rand_out = u[:B].view(B, 1), u[B:].view(B, r.n_outside)
+        self.join()
+        with torch.no_grad():
+            z, z_out = r._sample(rays_o, rays_d, near.reshape(B), far.reshape(B), r.perturb, t_rand, t_rand_out, None,
+                                 defer_last_merge=True)
+        depth_on = self.conf["extract_depth"] and self.iter_step > self.conf["depth_start_iter"] and gt_feats is not None
+        w = eng.forward(rays_o, rays_d, z.contiguous(), z_out, self.bg, self.cos_anneal_ratio(), skip_far=True, ray_grads=True,
+                        ray_grads_compact=True, pending_merge=r._pending_merge)
+        a = lib.VdnLossArgs()
+        a.color, a.true_rgb, a.weights, a.eik = w["color"].data_ptr(), true_rgb.data_ptr(), w["weights"].data_ptr(), w["eik"].data_ptr()
+        a.mask = mask.data_ptr() if mask is not None else None
+        a.igr_weight, a.mask_weight = self.conf["igr_weight"], self.conf["mask_weight"]
+        a.grad_scale = 1.0
+        a.B, a.T, a.C = B, eng.T, 96
+        a.g_color, a.g_eik, a.out_scalars = self.g_color.data_ptr(), self.g_eik.data_ptr(), self.scalars.data_ptr()
+        if self.conf["mask_weight"] != 0.0:
+            a.g_weights = self.g_weights.data_ptr()
+        if depth_on:
+            a.feats, a.gt_feats, a.g_feats = w["feat_out"].data_ptr(), gt_feats.data_ptr(), self.g_feats.data_ptr()
+            a.depth_weight = self.depth_iter_weight()
+            self.depth_iter += 1
+        lib.call("vdn_loss_fwd_bwd", a, st)
+        grad = eng.backward(self.g_color, self.g_feats if depth_on else None, self.g_weights if self.conf["mask_weight"] != 0.0 else None,
+                            self.g_eik)
+        # d loss / d (r, t): the ray adjoints of this step's rays (z_out: the depths the step rendered)
+        self.pose_adjoint(img_idx, px, py, w["d_rays_o"], w["d_rays_d"], w.get("d_z"), w.get("d_z_out"),
+                          z_out.contiguous() if z_out is not None else None)
+        lr, main_step = self.learning_rate(), self.iter_step + 1 - self._step0()
+
+        def adam(ranges, step):
+            (b0, e0), (b1, e1) = ranges[0], (ranges[1] if len(ranges) > 1 else (0, 0))
+            lib.call("vdn_adam_step_ranges", lib.ptr(self._param_flat), lib.ptr(grad), lib.ptr(self._exp_avg), lib.ptr(self._exp_avg_sq),
+                     b0, e0, b1, e1, lr, 0.9, 0.999, 1e-8, step, st)
+        if depth_on and self._depth_ranges:
+            self._depth_adam_steps += 1
+        adam(self._sdf_ranges, main_step)
+        if self._rest_ranges:
+            adam(self._rest_ranges, main_step)
+        if depth_on and self._depth_ranges:
+            adam(self._depth_ranges, self._depth_adam_steps)
+        images.refresh_together([eng.nets[k].img for k in eng.nets], st, self._img_cache.setdefault("pose_all", {}))
+        self._pose_adam()
+        self.iter_step += 1
+        return self.scalars
+
+    def _pose_adam(self):
+        """torch.optim.Adam(LearnPose.parameters(), lr=pose_lr) on the dense gradients: every camera's moments decay and the
+        cameras other than this step's keep moving on momentum, as in the reference."""
+        if not self._pose_ranges:
+            return
+        self._pose_steps += 1
+        (b0, e0), (b1, e1) = self._pose_ranges[0], (self._pose_ranges[1] if len(self._pose_ranges) > 1 else (0, 0))
+        lib.call("vdn_adam_step_ranges", lib.ptr(self._pose_flat), lib.ptr(self._pose_grad), lib.ptr(self._pose_exp_avg),
+                 lib.ptr(self._pose_exp_avg_sq), b0, e0, b1, e1, self.pose_lr(), 0.9, 0.999, 1e-8, self._pose_steps, _stream())
+
+    # ---- the reference's pose checkpoints (dpt_runner.py:383-401)
+    def pnf_state_dict(self):
+        """{intrin_net, pose_param_net, optimizer_focal, optimizer_pose, poses_iter_step}: optimizer_pose loads into
+        torch.optim.Adam(LearnPose.parameters()) (parameter 0 is the frozen init_c2w: no state), optimizer_focal into
+        torch.optim.Adam(LearnIntrin.parameters()) (it never steps: no state)."""
+        pn, n = self.pose_net, self.pose_net.num_cams
+        params = list(pn.parameters())
+        opt = torch.optim.Adam([torch.nn.Parameter(p.detach().clone()) for p in params], lr=self.conf["pose_lr"])
+        for grp in opt.param_groups:
+            grp.setdefault("initial_lr", self.conf["pose_lr"])
+            grp["lr"] = self.pose_lr()
+        sd = opt.state_dict()
+        for k, p in enumerate(params):
+            for j, q in enumerate((pn.r, pn.t)):
+                if p is q and q.requires_grad and self._pose_steps > 0:
+                    sl = slice(3 * n * j, 3 * n * (j + 1))
+                    sd["state"][k] = {"step": torch.tensor(float(self._pose_steps)),
+                                      "exp_avg": self._pose_exp_avg[sl].view(n, 3).clone(),
+                                      "exp_avg_sq": self._pose_exp_avg_sq[sl].view(n, 3).clone()}
+        fopt = torch.optim.Adam(list(self.intrin_net.parameters()), lr=self.conf["focal_lr"])
+        for grp in fopt.param_groups:
+            grp.setdefault("initial_lr", self.conf["focal_lr"])
+            grp["lr"] = self.focal_lr()
+        cl = lambda m: {k: v.detach().clone() for k, v in m.state_dict().items()}
+        return {"intrin_net": cl(self.intrin_net), "pose_param_net": cl(pn), "optimizer_focal": fopt.state_dict(),
+                "optimizer_pose": sd, "poses_iter_step": self.poses_iter_step}
+
+    def save_pnf_checkpoint(self, path):
+        torch.save(self.pnf_state_dict(), path)
+
+    def load_pnf_checkpoint(self, path_or_dict):
+        """dpt_runner.py:383-389. The schedules restart from epoch 0 (the reference saves no scheduler state) at the learning
+        rates the checkpoint's optimizer states hold."""
+        ck = torch.load(path_or_dict, map_location=self.dev) if isinstance(path_or_dict, str) else path_or_dict
+        pn, n = self.pose_net, self.pose_net.num_cams
+        with torch.no_grad():
+            sd = ck["pose_param_net"]
+            for name, v in sd.items():
+                own = dict(pn.named_parameters())[name]
+                own.copy_(v.to(self.dev))                    # in place: r / t stay views of the flat pose buffer
+            self.intrin_net.load_state_dict(ck["intrin_net"])
+            self._set_intrinsics()
+            if pn.init_c2w is not None:
+                self._init_c2w = pn.init_c2w.detach().to(self.dev).contiguous()
+            self._pose_exp_avg.zero_()
+            self._pose_exp_avg_sq.zero_()
+            st, params, steps = ck["optimizer_pose"]["state"], list(pn.parameters()), 0
+            for k, p in enumerate(params):
+                for j, q in enumerate((pn.r, pn.t)):
+                    if p is q and k in st:
+                        sl = slice(3 * n * j, 3 * n * (j + 1))
+                        self._pose_exp_avg[sl].copy_(st[k]["exp_avg"].reshape(-1).to(self.dev))
+                        self._pose_exp_avg_sq[sl].copy_(st[k]["exp_avg_sq"].reshape(-1).to(self.dev))
+                        steps = max(steps, int(st[k]["step"]))
+            self._pose_steps = steps
+        self.poses_iter_step = int(ck["poses_iter_step"])
+        # the epoch counters restart (the reference saves no scheduler state), the rates do not: loading the optimizers' state
+        # after constructing the schedulers restores their saved, decayed lr, and the schedulers go on multiplying that
+        lr_of = lambda k: float(ck[k]["param_groups"][0]["lr"])
+        self.pose_sched, self.focal_sched = pose_schedules(self.conf, lr_of("optimizer_pose"), lr_of("optimizer_focal"))
+        self._sched_started = False
 
     # ---- schedules (dpt_runner.py:304-319, 167-171)
     def learning_rate(self):
