@@ -3,14 +3,22 @@
 per GPU per step (BASELINE.json metric), synthetic 800x800 scene, random-init weights of the
 shipped architecture.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N>1: launched by torch.distributed.run, or spawned here)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run, or spawned here)
 
 Every leg times exactly K steps (after W untimed ones); `ms_per_step` is their total time / K. --dump-outputs DIR writes
 what the last of them handed back and left behind, as DIR/<name>.npy (rank 0; float32 / float64, a few MB): `step_stats`, the
 step's [loss, color_loss, psnr, eikonal, depth_loss, mask_loss], and `parameters`, every network parameter after its update.
 Inputs (seeded weights, rays, jitter) are the same on every run with the same arguments, so two builds compare array by array.
 
-One JSON line on rank 0 with the driver's contract plus
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps of the headline leg, the
+dump, and one JSON line on rank 0 with the driver's contract (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...), the workload (`config`, its point counts from the last timed step), `trials`, `model_flops_per_s` and
+`final_loss` (the last timed step's loss).
+
+--full runs everything else as well: `work_list_rows_mean` (one more untimed pass over the resident batches; `final_loss` and
+the point counts then come from its last step), every leg and figure below, and at N > 1 `allreduce_exposed_ms`, the in-step
+`roofline` and `dp_process_groups_created_max_over_ranks`. --headline-only, --no-all-samples, --no-roofline, --no-cpu-baseline
+and --cpu-baseline-full trim or extend what --full adds. Its line carries, beside the plain run's,
   roofline      the fused SDF kernel as the timed step launches it (HIP events on the launch stream, in situ; `schedule` says on which
                 schedule - the one-stream one of the committed kernel trace - with that schedule's own step time), beside its inference
                 launch; traffic = PMC bytes from the committed profile of the same launch;
@@ -278,10 +286,11 @@ class Leg:
         self.last = out
         return dt
 
-    def measure(self, warmup, steps, keep_outputs=False):
+    def measure(self, warmup, steps, keep_outputs=False, rows=True):
         """`warmup` untimed steps, then exactly `steps` timed ones in min(5, steps) regions of (nearly) equal length; `value` /
         `ms_per_step` are their total. keep_outputs: self.outputs = what the last timed step handed back (its statistics) and
-        left behind (the parameters after its update), copied to the host before anything else runs."""
+        left behind (the parameters after its update), copied to the host before anything else runs. rows=False: no untimed
+        pass for `work_list_rows_mean`; the point counts and `final_loss` are then the last timed step's."""
         for i in range(warmup):
             self.step(i)
         n = min(5, steps)
@@ -297,18 +306,21 @@ class Leg:
                             "parameters": self.trainer.param_flat.detach().float().cpu().numpy()}
         first_untimed = warmup + steps
         eng = self.trainer.engine
-        # mean work-list rows of the steady state: one more (untimed) pass over ALL resident batches - the lists differ by +-10 %
-        # between images, and every mean that is compared with another (the kernel statistics under profiles/ quote this one:
-        # roofline fractions are recomputed from rows / AverageUs) has to cover whole cycles of them - with the device-side row
-        # counters copied out per step
-        counts = []
-        n_cycle = len(self.batches)
-        for i in range(n_cycle):
-            self.step(first_untimed + i)
-            counts.append((eng.w["fg_active"][1].clone(), eng.w["bg_active"][1].clone() if "bg_active" in eng.w else None))
-        self.fence()
-        rows_fg = float(np.mean([int(a.item()) for a, _ in counts]))
-        rows_bg = float(np.mean([int(b.item()) for _, b in counts])) if counts[0][1] is not None else 0.0
+        extra = {}
+        if rows:
+            # mean work-list rows of the steady state: one more (untimed) pass over ALL resident batches - the lists differ by
+            # +-10 % between images, and every mean that is compared with another (the kernel statistics under profiles/ quote
+            # this one: roofline fractions are recomputed from rows / AverageUs) has to cover whole cycles of them - with the
+            # device-side row counters copied out per step
+            counts = []
+            n_cycle = len(self.batches)
+            for i in range(n_cycle):
+                self.step(first_untimed + i)
+                counts.append((eng.w["fg_active"][1].clone(), eng.w["bg_active"][1].clone() if "bg_active" in eng.w else None))
+            self.fence()
+            rows_fg = float(np.mean([int(a.item()) for a, _ in counts]))
+            rows_bg = float(np.mean([int(b.item()) for _, b in counts])) if counts[0][1] is not None else 0.0
+            extra["work_list_rows_mean"] = {"foreground": rows_fg, "background": rows_bg, "over_steps": n_cycle}
         fg = int(eng.w["fg_active"][1].item())
         bg = int(eng.w["bg_active"][1].item()) if "bg_active" in eng.w else 0
         rays = self.world * self.B
@@ -317,7 +329,7 @@ class Leg:
                 "trials": {"regions": len(regions), "steps_per_region": sizes, "timed_steps": steps,
                            "timed_seconds": float(sum(regions)),
                            "ms_per_step_min": min(per_step) * 1e3, "ms_per_step_max": max(per_step) * 1e3},
-                "work_list_rows_mean": {"foreground": rows_fg, "background": rows_bg, "over_steps": n_cycle},
+                **extra,
                 "foreground_points_evaluated_last_step": fg, "foreground_points_total": eng.P,
                 "background_points_evaluated_last_step": bg, "background_points_total": eng.Q,
                 "executed_flop_per_ray": fpr, "executed_model_flops_per_s": rays / step_s * fpr,
@@ -592,20 +604,72 @@ def dump_outputs(out_dir, arrays, budget=64 << 20):
         np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
+def headline_line(args, world, wdepth, head, res, extras=None):
+    """The line's head: the driver's contract, the workload and the headline leg's own figures. A plain run prints this alone;
+    --full adds the other legs (`extras`: the object-centric leg's point fractions go into `config.workload`) and the rest."""
+    extras = extras or {}
+    K, W = args.steps, args.warmup
+    dtype = "f32" if args.precision == "fp32" else "bf16"
+    return {
+        "metric": "rays/sec (512-ray batch, 128 samples/ray)", "value": res["value"], "unit": "rays/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": res["ms_per_step"],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+        "config": {"workload": "training step of %s (hierarchical sampling + render forward + backward + gradient "
+                               "all-reduce + Adam): SDF 8x256 + colour 4x256 %s+ NeRF 8x256, 512 rays x (64 coarse + 64 importance "
+                               "+ 32 outside) per GPU per step; pixels uniform over %s; samples that enter the loss through exact "
+                               "zeros are skipped: %.0f %% of the foreground and %.0f %% of the background points evaluated%s"
+                               % (args.config, "+ VDN head 4x256->96 " if wdepth else "",
+                                  "the full 800 x 800 frame" if args.crop is None else "the central %d-px window" % args.crop,
+                                  100.0 * res["foreground_points_evaluated_last_step"] / res["foreground_points_total"],
+                                  100.0 * res["background_points_evaluated_last_step"] / max(res["background_points_total"], 1),
+                                  (" (object_centric leg: %.0f %% / %.0f %%)" % (
+                                      100.0 * extras["object_centric"]["foreground_points_evaluated_last_step"] / extras["object_centric"]["foreground_points_total"],
+                                      100.0 * extras["object_centric"]["background_points_evaluated_last_step"] / max(extras["object_centric"]["background_points_total"], 1)))
+                                  if "object_centric" in extras else ""),
+                   "rays_per_gpu": args.batch, "samples_per_ray": 128, "outside_samples": 32, "parallelism": "dp%d" % world,
+                   "flop_per_ray": flop_per_ray(wdepth), "allreduce_bytes": head.trainer.param_flat.numel() * 4,
+                   # flop_per_ray is SURVEY.md 8d's algorithmic count (every sample evaluated); samples that render_core
+                   # multiplies by exact zeros are not evaluated: the executed count is below
+                   "executed_flop_per_ray": res["executed_flop_per_ray"],
+                   "background_points_evaluated_last_step": res["background_points_evaluated_last_step"],
+                   "background_points_total": res["background_points_total"],
+                   "foreground_points_evaluated_last_step": res["foreground_points_evaluated_last_step"],
+                   "foreground_points_total": res["foreground_points_total"]},
+        "trials": res["trials"],
+        **({"work_list_rows_mean": res["work_list_rows_mean"]} if "work_list_rows_mean" in res else {}),
+        # FLOPs of the points the step actually evaluated (not the all-samples count)
+        "model_flops_per_s": res["executed_model_flops_per_s"],
+        "final_loss": res["final_loss"],
+    }
+
+
+def leave(world):
+    """N > 1: every rank leaves together, its communicators destroyed."""
+    if world > 1:
+        import torch.distributed as dist
+        from vdn_train import dp
+        dist.barrier()                 # rank 0 is still printing: leave together
+        dp.shutdown()
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="SURVEY.md 8d's whole CPU protocol (3 warm-up + 5 timed batches of "
-                    "512 rays per figure: minutes of CPU time) instead of the bounded sample")
-    ap.add_argument("--headline-only", action="store_true", help="only the headline leg: keeps a rocprof trace of this command to one "
-                    "population of launches per kernel (no all-samples / fp32 / wdepth legs, no forward-only renders)")
-    ap.add_argument("--no-all-samples", action="store_true", help="skip the leg with the zero-weight work lists off")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the single-kernel timing launches (with --headline-only a rocprof "
-                    "trace of this command then holds nothing but the timed step's own launches)")
+    ap.add_argument("--full", action="store_true", help="everything else the benchmark measures and checks, in the same line: the "
+                    "other legs, roofline figures, work-list rows, the CPU baseline, at N > 1 the exposed all-reduce time (without it: "
+                    "set-up, warm-up, the timed steps, --dump-outputs and the headline line, nothing else)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="(--full) SURVEY.md 8d's whole CPU protocol (3 warm-up + 5 timed "
+                    "batches of 512 rays per figure: minutes of CPU time) instead of the bounded sample")
+    ap.add_argument("--headline-only", action="store_true", help="(--full) only the headline leg: keeps a rocprof trace of this command "
+                    "to one population of launches per kernel (no all-samples / fp32 / wdepth legs, no forward-only renders)")
+    ap.add_argument("--no-all-samples", action="store_true", help="(--full) skip the leg with the zero-weight work lists off")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the single-kernel timing launches (with --headline-only a "
+                    "rocprof trace of this command then holds nothing but the timed step's own launches)")
     ap.add_argument("--crop", type=int, default=None, help="draw pixels from a centred crop x crop window (object-centric capture) "
                     "instead of the full 800 x 800 frame")
     ap.add_argument("--config", choices=["womsk_white", "womsk_white_wdepth"], default="womsk_white",
@@ -617,6 +681,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.cpu_baseline_full and not args.full:
+        ap.error("--cpu-baseline-full needs --full (a plain run has no CPU baseline)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start N fresh ranks BEFORE anything touches the GPU (a process that
@@ -648,9 +714,15 @@ def main():
     # torch's generators (the step's jitter) from one fixed seed, whatever ran before: same inputs on every run
     torch.manual_seed(0)
     head = Leg(args, dev, world, rank, args.precision, wdepth, nb, crop=args.crop)
-    res = head.measure(W, K, keep_outputs=args.dump_outputs is not None)
+    res = head.measure(W, K, keep_outputs=args.dump_outputs is not None, rows=args.full)
     if args.dump_outputs is not None and rank == 0:
         dump_outputs(args.dump_outputs, head.outputs)
+    if not args.full:
+        # a plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, wdepth, head, res)), flush=True)
+        leave(world)
+        return
     extras = {}
     if world > 1:
         # K more steps with HIP events around every collective (dp.Collectives.sum_now / finish): how long each stream actually
@@ -790,43 +862,15 @@ def main():
             extras["object_centric"] = oc
 
     if rank == 0:
-        dtype = "f32" if args.precision == "fp32" else "bf16"
-        line = {
-            "metric": "rays/sec (512-ray batch, 128 samples/ray)", "value": res["value"], "unit": "rays/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": res["ms_per_step"],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-            "config": {"workload": "training step of %s (hierarchical sampling + render forward + backward + gradient "
-                                   "all-reduce + Adam): SDF 8x256 + colour 4x256 %s+ NeRF 8x256, 512 rays x (64 coarse + 64 importance "
-                                   "+ 32 outside) per GPU per step; pixels uniform over %s; samples that enter the loss through exact "
-                                   "zeros are skipped: %.0f %% of the foreground and %.0f %% of the background points evaluated%s"
-                                   % (args.config, "+ VDN head 4x256->96 " if wdepth else "",
-                                      "the full 800 x 800 frame" if args.crop is None else "the central %d-px window" % args.crop,
-                                      100.0 * res["foreground_points_evaluated_last_step"] / res["foreground_points_total"],
-                                      100.0 * res["background_points_evaluated_last_step"] / max(res["background_points_total"], 1),
-                                      (" (object_centric leg: %.0f %% / %.0f %%)" % (
-                                          100.0 * extras["object_centric"]["foreground_points_evaluated_last_step"] / extras["object_centric"]["foreground_points_total"],
-                                          100.0 * extras["object_centric"]["background_points_evaluated_last_step"] / max(extras["object_centric"]["background_points_total"], 1)))
-                                      if "object_centric" in extras else ""),
-                       "rays_per_gpu": args.batch, "samples_per_ray": 128, "outside_samples": 32, "parallelism": "dp%d" % world,
-                       "flop_per_ray": flop_per_ray(wdepth), "allreduce_bytes": head.trainer.param_flat.numel() * 4,
-                       # flop_per_ray is SURVEY.md 8d's algorithmic count (every sample evaluated); samples that render_core
-                       # multiplies by exact zeros are not evaluated: the executed count is below
-                       "executed_flop_per_ray": res["executed_flop_per_ray"],
-                       "background_points_evaluated_last_step": res["background_points_evaluated_last_step"],
-                       "background_points_total": res["background_points_total"],
-                       "foreground_points_evaluated_last_step": res["foreground_points_evaluated_last_step"],
-                       "foreground_points_total": res["foreground_points_total"]},
-            "trials": res["trials"], "work_list_rows_mean": res["work_list_rows_mean"],
-            # FLOPs of the points the step actually evaluated (not the all-samples count)
-            "model_flops_per_s": res["executed_model_flops_per_s"],
-            "final_loss": res["final_loss"],
+        line = headline_line(args, world, wdepth, head, res, extras)
+        line.update({
             "roofline": roof, "roofline_dw_gemm": roof_dw,
             # the north-star kernel inside the steps of THIS line's schedule (default: two streams; what ms_per_step is measured on)
             "roofline_in_step_two_streams": (dict({k: roof["in_step_two_streams"][k] for k in ("frac", "kernel_ms", "points", "steps")},
                                                   schedule="default two-stream schedule = the schedule of ms_per_step: the background network's "
                                                            "kernels share the chip with the launch", ms_per_step=res["ms_per_step"])
                                              if (roof is not None and "in_step_two_streams" in roof) else None),
-        }
+        })
         line.update(extras)
         if roof is not None:
             # flat copies of the nested figures (a reader that keeps only the scalars of `roofline` still sees them)
@@ -866,12 +910,7 @@ def main():
                    "cpu_baseline_rays_per_s": rnd(g(line, "cpu_baseline", "value"))}
         line["summary"] = {k: v for k, v in summary.items() if v is not None}
         print(json.dumps(line), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        from vdn_train import dp
-        dist.barrier()                 # rank 0 is still printing: leave together
-        dp.shutdown()
-        dist.destroy_process_group()
+    leave(world)
 
 
 if __name__ == "__main__":

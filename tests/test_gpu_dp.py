@@ -277,8 +277,8 @@ def test_bench_two_rank_control_flow():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VDN_DIST_BACKEND="gloo")
-    # the driver's own flags: at N > 1 bench.py runs the headline leg, the exposed all-reduce time and the in-step roofline - nothing else
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    # --full at N > 1: the headline leg, the exposed all-reduce time and the in-step roofline - nothing else
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     for cmd in ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                  "--master-port", "29541"] + tail, [sys.executable] + tail):
         env.pop("WORLD_SIZE", None)
@@ -300,12 +300,13 @@ def test_bench_two_rank_control_flow():
 
 
 def test_bench_line_carries_every_leg(tmp_path):
-    """One default-shaped run (shortened): the driver's contract keys, the executed-FLOP accounting, the trial spread and the
+    """One --full run (shortened): the driver's contract keys, the executed-FLOP accounting, the trial spread and the
     fp32 parity-path / wdepth / all-samples legs in the same line; --steps timed steps exactly, and --dump-outputs."""
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dump = str(tmp_path / "dump")
-    d = _bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", dump])
+    d = _bench([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                "--dump-outputs", dump])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline", "trials", "parity_path", "wdepth", "all_samples_evaluated", "object_centric"):
         assert k in d, k
@@ -334,3 +335,42 @@ def test_bench_line_carries_every_leg(tmp_path):
     assert g["weight_sum_max_rel_err"] < 1e-3 and g["gradient_error_rel_err_max"] < 0.2
     assert list(d)[-1] == "summary" and d["summary"]["value_rays_per_s"] > 0 and "runner_flow_bf16_rays_per_s" in d["summary"]
     assert d["roofline"]["inference_launch_frac"] == d["roofline"]["inference_launch"]["frac"]
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """A plain run (no --full) at N = 1 and N = 2: the driver's contract, the headline leg's K timed steps and --dump-outputs,
+    none of the other legs or figures; its timed steps and dumped arrays are those of a --full run with the same arguments."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2"]
+    plain, full = str(tmp_path / "plain"), str(tmp_path / "full")
+    d = _bench(bench + ["--dump-outputs", plain])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "trials", "model_flops_per_s", "final_loss"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["dtype"] == "bf16" and d["value"] > 0
+    assert d["unit"] == "rays/s" and d["higher_is_better"] is True and d["metric"].startswith("rays/sec")
+    assert d["trials"]["timed_steps"] == 3 and d["trials"]["steps_per_region"] == [1, 1, 1]
+    assert abs(d["ms_per_step"] - d["trials"]["timed_seconds"] / 3 * 1e3) < 1e-6 * d["ms_per_step"]
+    assert abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "roofline_dw_gemm", "cpu_baseline", "work_list_rows_mean", "parity_path", "wdepth", "all_samples_evaluated",
+                "object_centric", "runner_flow", "real_cameras", "bf16_vs_fp32", "forward_only_rays_per_s", "summary"} & set(d)
+    stats, params = np.load(os.path.join(plain, "step_stats.npy")), np.load(os.path.join(plain, "parameters.npy"))
+    # nothing runs after the timed steps: final_loss is the last timed step's loss
+    assert d["final_loss"] == stats[0]
+    assert params.size * 4 == d["config"]["allreduce_bytes"]
+    # the same timed steps as a --full run (only the headline leg of it: the dump is taken before anything else runs)
+    f = _bench(bench + ["--full", "--headline-only", "--no-roofline", "--no-cpu-baseline", "--dump-outputs", full])
+    assert "work_list_rows_mean" in f and f["trials"]["timed_steps"] == 3
+    for name in ("step_stats", "parameters"):
+        assert np.array_equal(np.load(os.path.join(plain, name + ".npy")), np.load(os.path.join(full, name + ".npy"))), name
+    # N = 2 (gloo, both ranks on the one GPU): the headline leg alone, no all-reduce timing, no in-step roofline
+    env = dict(os.environ, VDN_DIST_BACKEND="gloo")
+    env.pop("WORLD_SIZE", None)
+    d2 = _bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], env)
+    assert d2["n_gpus"] == 2 and d2["value"] > 0 and d2["config"]["parallelism"] == "dp2" and d2["trials"]["timed_steps"] == 3
+    assert not {"roofline", "allreduce_exposed_ms", "dp_process_groups_created_max_over_ranks", "cpu_baseline", "summary"} & set(d2)
+    # --cpu-baseline-full asks for more than a plain run does: refused without --full
+    import subprocess
+    bad = subprocess.run(bench + ["--cpu-baseline-full"], capture_output=True, text=True, timeout=300, cwd=root)
+    assert bad.returncode != 0 and "--full" in bad.stderr

@@ -1,12 +1,12 @@
 #!/bin/bash
 # SQ / TCC counter passes for one command (rocprofv3 --pmc, program directly after "--"), csv per pass under
-# gpurun_out/<tag>/passN; summarise with tools/summarise_counters.py. Separate passes: 8 SQ slots per pass, and
+# $OUT/<tag>/passN (OUT defaults to profile_out); summarise with tools/summarise_counters.py. Separate passes: 8 SQ slots per pass, and
 # FETCH_SIZE / WRITE_SIZE do not fit one TCC pass (MI355X_MICROARCH.md, rocprofv3 PMC slots).
-#   usage: tools/collect_counters.sh <tag> <program> [args...]
+#   usage: [OUT=<folder>] tools/collect_counters.sh <tag> <program> [args...]
 set -u
 tag=$1; shift
+out=$(realpath -m "${OUT:-profile_out}")/$tag
 cd /tmp && export TMPDIR=/tmp
-out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p "$out"
 cd "$GRAFT_REPO_ROOT"
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC"
@@ -21,4 +21,4 @@ for p in "$P1" "$P2" "$P3" "$P4" "$P5" "$P6"; do
   rocprofv3 --pmc $p --output-format csv -d "$out/pass$i" -- "$@" > "$out/pass$i.log" 2>&1 || echo "pass $i failed (see $out/pass$i.log)"
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- "$@" > "$out/trace.log" 2>&1 || echo "trace failed"
-echo "counters collected under gpurun_out/$tag"
+echo "counters collected under $out"

@@ -1,8 +1,8 @@
-"""profiles/<round>_* from what tools/profile_round.sh left under gpurun_out/ (dev; run from the repo root):
-python tools/dev/make_profiles.py r03"""
+"""profiles/<round>_* from what tools/profile_round.sh left under $OUT/ (profile_out by default; dev; run from the repo root):
+[OUT=<folder>] python tools/dev/make_profiles.py r03"""
 import json, os, shutil, subprocess, sys
 R = sys.argv[1] if len(sys.argv) > 1 else "r05"
-G, P = "gpurun_out", "profiles"
+G, P = os.environ.get("OUT", "profile_out"), "profiles"
 line = open("%s/%s_bench_train_bf16.json" % (G, R)).read().strip().splitlines()[-1]
 json.loads(line)
 open("%s/%s_bench_train_bf16.json" % (P, R), "w").write(line + "\n")

@@ -1,7 +1,8 @@
+OUT=$(realpath -m "${OUT:-profile_out}"); ROOT=$(pwd); mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace -d gpurun_out/tl -o tl --output-format csv -- python3 bench.py --headline-only --no-cpu-baseline --steps 30 --warmup 10 > gpurun_out/tl.log 2>&1
-f=$(find gpurun_out/tl -name '*kernel_trace.csv' | head -1)
-python3 tools/dev/timeline.py $f -600 > gpurun_out/tl_step.txt
-python3 tools/dev/timeline.py $f -601 > gpurun_out/tl_step5.txt
-rm -rf gpurun_out/tl
+cd "$ROOT"
+rocprofv3 --kernel-trace -d $OUT/tl -o tl --output-format csv -- python3 bench.py --full --headline-only --no-cpu-baseline --steps 30 --warmup 10 > $OUT/tl.log 2>&1
+f=$(find $OUT/tl -name '*kernel_trace.csv' | head -1)
+python3 tools/dev/timeline.py $f -600 > $OUT/tl_step.txt
+python3 tools/dev/timeline.py $f -601 > $OUT/tl_step5.txt
+rm -rf $OUT/tl
