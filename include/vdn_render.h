@@ -147,6 +147,9 @@ typedef struct {
      * network cat([feature_vector, VDN output]) (renderer.py:247-248; a d_feature = 352 network, blob with a 13-k-tile first layer) */
     const float* extra;        /* [P,96] dense point id, or NULL */
     void* save_extra;          /* [P,96] plane of `extra` for the weight-gradient GEMM (training) or NULL */
+    /* bf16 training, optional (with save_h): 1-bit ReLU masks of the 4 hidden layers, [4][pad32(P) * 32] bytes
+     * (csrc/mlp_engine.h: BF16::relu_bits), for VdnRenderNetBwdArgs.mask; NULL = not written. fp32: must be NULL (-4). */
+    void* save_mask;
 } VdnRenderNetArgs;
 int vdn_rendernet_fwd_f32(const VdnRenderNetArgs* args_host, void* stream);
 int vdn_rendernet_fwd_bf16(const VdnRenderNetArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */
@@ -175,6 +178,11 @@ typedef struct {
      * multiplies them by zero), the training saves are written in COMPACT order (row q holds point active_idx[q]). */
     const int32_t* active_idx; /* [P] or NULL = all points */
     const int32_t* n_active;   /* device scalar */
+    /* bf16 training, optional (with save_h, both or neither): 1-bit ReLU masks of pts_linears.0..7, [8][pad32(P) * 32]
+     * bytes, and of views_linears.0, [pad32(P) * 16] bytes (csrc/mlp_engine.h: BF16::relu_bits), for VdnNerfBwdArgs.mask /
+     * mask_v; NULL = not written. fp32: must be NULL. */
+    void* save_mask;
+    void* save_mask_v;
 } VdnNerfArgs;
 int vdn_nerf_mlp_fwd_f32(const VdnNerfArgs* args_host, void* stream);
 int vdn_nerf_mlp_fwd_bf16(const VdnNerfArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */
@@ -376,6 +384,9 @@ typedef struct {
     /* d_feature = 352 network (VdnRenderNetArgs.extra): d loss / d extra is ADDED into d_extra (the VDN head's output adjoint,
      * which the compositor wrote first) */
     float* d_extra;            /* [P,96] dense point id, or NULL for the 256-feature network */
+    /* bf16, optional: the forward's VdnRenderNetArgs.save_mask. Given, the ReLU' of the chain comes from it and save_h is not
+     * read (it stays required: the weight-gradient GEMM reads it). fp32: must be NULL (-5). */
+    const void* mask;
 } VdnRenderNetBwdArgs;
 int vdn_rendernet_bwd_f32(const VdnRenderNetBwdArgs* args_host, void* stream);
 int vdn_rendernet_bwd_bf16(const VdnRenderNetBwdArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */
@@ -403,6 +414,10 @@ typedef struct {
     int32_t n_per_ray;
     float* d_pts;              /* [P,3] dense point id (rows off the work list are not written), or NULL */
     float* d_dirs;             /* [P,3] (required with d_pts) */
+    /* bf16, optional (both or neither): the forward's VdnNerfArgs.save_mask / save_mask_v. Given, the ReLU' of the chain comes
+     * from them and save_h / save_hv are not read by this kernel. fp32 and vdn_nerf_mlp_bwd_input_*: must be NULL (-5). */
+    const void* mask;
+    const void* mask_v;
 } VdnNerfBwdArgs;
 int vdn_nerf_mlp_bwd_f32(const VdnNerfBwdArgs* args_host, void* stream);
 int vdn_nerf_mlp_bwd_bf16(const VdnNerfBwdArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */

@@ -10,7 +10,9 @@
 
 namespace vdn {
 
-template <class P, bool DPT, bool EXPL>
+// MASK (bf16, not EXPL): the ReLU' of the chain comes from the forward's 1-bit masks (a.mask / mask_v; mlp_engine.h:
+// BF16::relu_bits) instead of the saved planes save_h / save_hv, which this kernel then does not read
+template <class P, bool DPT, bool EXPL, bool MASK = false>
 __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_kernel(NerfBwdArgs a, NerfInputGradArgs in) {
     using ST = typename P::store_t;
     constexpr int kSlot = P::stride(9);
@@ -37,6 +39,17 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
     ST* delta_v = reinterpret_cast<ST*>(a.delta_v);
     ST* delta_head = reinterpret_cast<ST*>(a.delta_head);
     ST* delta_h = reinterpret_cast<ST*>(a.delta_h);
+    // MASK: the nine layers' masks (34 VGPRs, where the plane path keeps its prefetched H tiles) are loaded here, ahead of
+    // everything else; they land under the weight stream's warm-up wait (mask_landed below). Words 4 l .. 4 l + 3: pts_linears.l;
+    // 32, 33: views_linears.0
+    unsigned mk[MASK ? 34 : 1];
+    if constexpr (MASK) {
+        const unsigned char* m = static_cast<const unsigned char*>(a.mask);
+        const long MS = BF16::mask_plane(a.P, 256);
+#pragma unroll
+        for (int l = 0; l < 8; ++l) BF16::load_mask<4>(m + l * MS, p, h, mk + 4 * l);
+        BF16::load_mask<2>(static_cast<const unsigned char*>(a.mask_v), p, h, mk + 32);
+    }
 
     // inverted-sphere point and view direction of this lane's sample, as the forward builds them (renderer.py:112-115)
     float x4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, dir[3] = {0.0f, 0.0f, 0.0f}, pw[3] = {0.0f, 0.0f, 0.0f}, nrm = 1.0f;
@@ -88,12 +101,29 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
             P::store_tile(dst, p, ld, nt, h, o, ok);
         };
     };
+    // D = acc * mask bit (MASK): the same select, no plane loads. w0: the layer's first mask word
+    auto bit_store = [&](auto& D, ST* dst, int ld, int w0) VDN_INL {
+        return [&D, &mk, dst, ld, w0, p, ok, h](int nt, const f32x16& acc, int) VDN_INL {
+            const f32x16 o = BF16::mask_select(mk + w0, nt, acc);
+            D.set(nt, o);
+            P::store_tile(dst, p, ld, nt, h, o, ok);
+        };
+    };
+    // pts_linears.l's delta: the layer from `In` (KT k-tiles) into `D`
+    auto hidden = [&](auto kt_c, auto& In, auto& D, int l) VDN_INL {
+        constexpr int KT = decltype(kt_c)::value;
+        if constexpr (MASK) dense<P, KT, 8, false>(ws, In, 0, NoPre{}, bit_store(D, delta_h + l * PS, 256, 4 * l), P::kTileOps);
+        else dense<P, KT, 8, false, kBwdPrefetch>(ws, In, 0, ldH(l), mask_store(D, delta_h + l * PS, 256), P::kTileOps, P::kTileOps);
+    };
+    using K8 = std::integral_constant<int, 8>;
     ws.all_issue = __any(ok);
+    if constexpr (MASK) BF16::mask_landed(mk);
     warm_l2_wait();
     ws.start();
     // Wout^T: -> d hv (128), masked by the views layer's ReLU
-    dense<P, KO, 4, false>(ws, X, 0, [&](int nt) VDN_INL { return P::load_tile(save_hv, p, 128, nt, h); },
-                               mask_store(Y, delta_v, 128), 4);
+    if constexpr (MASK) dense<P, KO, 4, false>(ws, X, 0, NoPre{}, bit_store(Y, delta_v, 128, 32), P::kTileOps);
+    else dense<P, KO, 4, false>(ws, X, 0, [&](int nt) VDN_INL { return P::load_tile(save_hv, p, 128, nt, h); },
+                                    mask_store(Y, delta_v, 128), 4);
     // Wviews^T: -> d [feature (8 tiles) | PE(view) (only wanted for differentiable rays)]; feature_linear has no activation
     dense<P, 4, 9, false>(ws, Y, 0, NoPre{}, [&](int nt, const f32x16& acc, int) VDN_INL {
         if (nt < 8) {
@@ -109,17 +139,24 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
         X.set(8, t16);
         P::store_tile(delta_head, p, 288, 8, h, t16, ok);
     }
-    dense<P, 9, 8, false, kBwdPrefetch>(ws, X, 0, ldH(7), mask_store(Y, delta_h + 7 * PS, 256), P::kTileOps, P::kTileOps);     // Whead^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(6), mask_store(X, delta_h + 6 * PS, 256), P::kTileOps, P::kTileOps);     // W7^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, X, 0, ldH(5), mask_store(Y, delta_h + 5 * PS, 256), P::kTileOps, P::kTileOps);     // W6^T
+    hidden(std::integral_constant<int, 9>{}, X, Y, 7);     // Whead^T
+    hidden(K8{}, Y, X, 6);                                  // W7^T
+    hidden(K8{}, X, Y, 5);                                  // W6^T
     // W5^T: 11 output tiles = [PE (3, dropped) | h4 (8)]
     dense<P, 8, 11, false>(ws, Y, 0,
-        [&](int nt) VDN_INL { return nt >= 3 ? P::load_tile(save_h + 4 * PS, p, 256, nt - 3, h) : f32x16{}; },
-        [&](int nt, const f32x16& acc, const f32x16& hv) VDN_INL {
+        [&](int nt) VDN_INL {
+            if constexpr (MASK) return 0;
+            else return nt >= 3 ? P::load_tile(save_h + 4 * PS, p, 256, nt - 3, h) : f32x16{};
+        },
+        [&](int nt, const f32x16& acc, const auto& hv) VDN_INL {
             if (nt >= 3) {
                 f32x16 o;
+                if constexpr (MASK) {
+                    o = BF16::mask_select(mk + 16, nt - 3, acc);
+                } else {
 #pragma unroll
-                for (int t = 0; t < 16; ++t) o[t] = hv[t] > 0.0f ? acc[t] : 0.0f;
+                    for (int t = 0; t < 16; ++t) o[t] = hv[t] > 0.0f ? acc[t] : 0.0f;
+                }
                 X.set(nt - 3, o);
                 P::store_tile(delta_h + 4 * PS, p, 256, nt - 3, h, o, ok);
             } else if (want_pts) {          // the skip input's adjoint: slots 32 nt .. of the 10-octave encoding of pts4
@@ -128,10 +165,10 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void nerf_bwd_ke
                 else pe_adjoint_tile<4, 10, 2, P::kAccurateTrig>(acc, h, x4, dx4);
             }
         });
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, X, 0, ldH(3), mask_store(Y, delta_h + 3 * PS, 256), P::kTileOps, P::kTileOps);     // W4^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(2), mask_store(X, delta_h + 2 * PS, 256), P::kTileOps, P::kTileOps);     // W3^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, X, 0, ldH(1), mask_store(Y, delta_h + 1 * PS, 256), P::kTileOps, P::kTileOps);     // W2^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(0), mask_store(X, delta_h + 0 * PS, 256), P::kTileOps, P::kTileOps);      // W1^T
+    hidden(K8{}, X, Y, 3);      // W4^T
+    hidden(K8{}, Y, X, 2);      // W3^T
+    hidden(K8{}, X, Y, 1);      // W2^T
+    hidden(K8{}, Y, X, 0);      // W1^T
     if (want_pts) {
         dense<P, 8, 3, false>(ws, X, 0, NoPre{}, [&](int nt, const f32x16& acc, int) VDN_INL {       // W0^T
             if (nt == 0) pe_adjoint_tile<4, 10, 0, P::kAccurateTrig>(acc, h, x4, dx4);
@@ -169,6 +206,20 @@ int launch_nerf_bwd_impl(const VdnNerfBwdArgs* args, const NerfInputGradArgs& in
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     const size_t lds = 3 * P::stride(9);
+    if (args->mask != nullptr || args->mask_v != nullptr) {
+        if constexpr (std::is_same<P, BF16>::value && !EXPL) {
+            if (args->mask == nullptr || args->mask_v == nullptr) return -5;
+            static bool once_m = (allow_big_lds(nerf_bwd_kernel<P, false, false, true>, lds), allow_big_lds(nerf_bwd_kernel<P, true, false, true>, lds), true);
+            (void)once_m;
+            if (args->g_feat != nullptr)
+                hipLaunchKernelGGL((nerf_bwd_kernel<P, true, false, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args, in);
+            else
+                hipLaunchKernelGGL((nerf_bwd_kernel<P, false, false, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args, in);
+            return (int)hipGetLastError();
+        } else {
+            return -5;          // ReLU masks: the bf16 ray-regenerated path only
+        }
+    }
     static bool once = (allow_big_lds(nerf_bwd_kernel<P, false, EXPL>, lds), allow_big_lds(nerf_bwd_kernel<P, true, EXPL>, lds), true);
     (void)once;
     if (args->g_feat != nullptr)

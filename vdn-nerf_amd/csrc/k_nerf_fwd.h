@@ -125,6 +125,7 @@ int launch_nerf_fwd(const VdnNerfArgs* args, void* stream_) {
     if (args == nullptr || args->P <= 0 || !args->blob || !args->density || !args->rgb || args->n_per_ray <= 0) return -1;
     if (!args->pts4 && (!args->rays_o || !args->rays_d || !args->z)) return -1;
     if (!args->dirs && !args->rays_d) return -1;
+    if (args->save_mask || args->save_mask_v) return -2;          // ReLU masks: the bf16 kernel only (k_nerf_fwd2.h)
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     const size_t lds = 3 * P::stride(11);

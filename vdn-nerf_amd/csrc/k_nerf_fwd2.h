@@ -10,7 +10,7 @@ namespace vdn {
 
 // chunk program of the 'fwd' stream (vdn_hip/images.py: nerf_streams): pts_linears.0 (3 k-tiles), .1-.4, .5 (11: skip), .6, .7,
 // heads (feature 8 + alpha 1), views_linears.0 (9 k-tiles, 4 chunks), rgb (+ dpt) (4 k-tiles)
-template <bool DPT, bool SAVE>
+template <bool DPT, bool SAVE, bool MASK = false>
 struct NerfFwdProg {
     static constexpr int total = 64 + 9 + 4 + (DPT ? 4 : 1);
     static constexpr int kt(int c) {
@@ -29,10 +29,10 @@ struct NerfFwdProg {
     // conditional and uncounted, which can only make a wait longer
     static constexpr int stores(int c) {
         if (!SAVE || c < 0 || c >= total) return 0;
-        if (c < 64) return BF16::kTileOps;      // save_h tile
+        if (c < 64) return BF16::kTileOps + (MASK && c % 8 == 7 ? 1 : 0);      // save_h tile (+ the layer's mask behind its last tile)
         if (c < 72) return BF16::kTileOps;      // save_feature tile
         if (c < 73) return 0;                   // alpha row
-        if (c < 77) return BF16::kTileOps;      // save_hv tile
+        if (c < 77) return BF16::kTileOps + (MASK && c == 76 ? 1 : 0);      // save_hv tile (+ its mask)
         return 0;
     }
 };
@@ -40,12 +40,14 @@ struct NerfFwdProg {
 #ifndef VDN_NERF_FWD_ST_MODE
 #define VDN_NERF_FWD_ST_MODE VDN_PLANE_ST_MODE      // cache policy of this kernel's saves (development A/B; mlp_engine.h: BF16::store_tile)
 #endif
-template <bool DPT, bool SAVE>
+// MASK (with SAVE): each ReLU layer also writes its 1-bit mask (a.save_mask / save_mask_v; mlp_engine.h: BF16::relu_bits)
+template <bool DPT, bool SAVE, bool MASK = false>
 __global__ __launch_bounds__(256, 2) void nerf_fwd2_kernel(NerfArgs a) {
+    static_assert(SAVE || !MASK, "masks are training saves");
     constexpr int kSt = VDN_NERF_FWD_ST_MODE;
     using P = BF16;
     using ST = unsigned short;
-    using PG = NerfFwdProg<DPT, SAVE>;
+    using PG = NerfFwdProg<DPT, SAVE, MASK>;
     constexpr int kSlot = P::stride(11);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     flow::Pipe<4, kSlot, 3, 2> pp;
@@ -103,25 +105,40 @@ __global__ __launch_bounds__(256, 2) void nerf_fwd2_kernel(NerfArgs a) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) pe_keep[i] = X.r[i];
     }
-    // D tile (t0 + nt) <- relu(acc); in training kept for the backward
-    auto relu_into = [&](auto& D, int t0, ST* save, int ld) VDN_INL {
-        return [&D, t0, save, ld, q, h](int nt, const f32x16& acc, int) VDN_INL {
+    // D tile (t0 + nt) <- relu(acc); in training kept for the backward. MASK: the layer's bits gather in mk (tiles 2i, 2i + 1
+    // in word i) and go out in one store behind its last tile (counted in NerfFwdProg::stores)
+    unsigned mk[4];
+    auto relu_into = [&](auto& D, int t0, ST* save, int ld, unsigned char* msave = nullptr) VDN_INL {
+        return [&D, &mk, t0, save, ld, msave, q, h](int nt, const f32x16& acc, int) VDN_INL {
             f32x16 o;
 #pragma unroll
             for (int t = 0; t < 16; ++t) o[t] = relu0(acc[t]);
             D.set(t0 + nt, o);
             if constexpr (SAVE) P::template store_tile<kSt>(save, q, ld, nt, h, o, true);
+            if constexpr (MASK) {
+                const unsigned b = P::relu_bits(o);
+                if (nt & 1) mk[nt >> 1] |= b << 16;
+                else mk[nt >> 1] = b;
+                if (ld == 256 && nt == 7) P::template store_mask<4, kSt>(msave, q, h, mk, true);
+                if (ld == 128 && nt == 3) {
+                    const unsigned m2[2] = {mk[0], mk[1]};
+                    P::template store_mask<2, kSt>(msave, q, h, m2, true);
+                }
+            }
         };
     };
     auto sv = [&](int l) VDN_INL { return save_h + l * PS; };
+    unsigned char* const save_mask = static_cast<unsigned char*>(a.save_mask);
+    const long MS = P::mask_plane(a.P, 256);
+    auto sm = [&](int l) VDN_INL { return MASK ? save_mask + l * MS : nullptr; };
     warm_l2_wait();
     pp.template start<PG>();
     auto f0 = flow::flow_begin();
-    auto f1 = flow::dense2<PG, 8>(f0, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(0), 256));          // pts_linears.0
-    auto f2 = flow::dense2<PG, 8>(f1, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(1), 256));          // 1
-    auto f3 = flow::dense2<PG, 8>(f2, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(2), 256));          // 2
-    auto f4 = flow::dense2<PG, 8>(f3, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(3), 256));          // 3
-    auto f5 = flow::dense2<PG, 8>(f4, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(4), 256));          // 4
+    auto f1 = flow::dense2<PG, 8>(f0, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(0), 256, sm(0)));          // pts_linears.0
+    auto f2 = flow::dense2<PG, 8>(f1, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(1), 256, sm(1)));          // 1
+    auto f3 = flow::dense2<PG, 8>(f2, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(2), 256, sm(2)));          // 2
+    auto f4 = flow::dense2<PG, 8>(f3, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(3), 256, sm(3)));          // 3
+    auto f5 = flow::dense2<PG, 8>(f4, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(4), 256, sm(4)));          // 4
     // skip (fields.py:334-335): h = cat([input_pts, h]) -> X = [PE (3 tiles) | h (8 tiles)]. The copy needs layer 4's last
     // tile: its pending epilogue runs first (the one layer boundary of this kernel without overlap)
     auto f5d = flow::flow_drain(f5);
@@ -129,9 +146,9 @@ __global__ __launch_bounds__(256, 2) void nerf_fwd2_kernel(NerfArgs a) {
     for (int kt = 0; kt < 8; ++kt) X.copy_tile(3 + kt, Y, kt);
 #pragma unroll
     for (int i = 0; i < 6; ++i) X.r[i] = pe_keep[i];
-    auto f6 = flow::dense2<PG, 8>(f5d, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(5), 256));         // 5
-    auto f7 = flow::dense2<PG, 8>(f6, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(6), 256));          // 6
-    auto f8 = flow::dense2<PG, 8>(f7, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(7), 256));          // 7
+    auto f6 = flow::dense2<PG, 8>(f5d, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(5), 256, sm(5)));         // 5
+    auto f7 = flow::dense2<PG, 8>(f6, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(6), 256, sm(6)));          // 6
+    auto f8 = flow::dense2<PG, 8>(f7, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(7), 256, sm(7)));          // 7
     // heads on h: image rows 0..255 feature_linear, row 256 alpha_linear
     auto f9 = flow::dense2<PG, 9>(f8, pp, Y, flow::NoLoad{}, [&](int nt, const f32x16& acc, int) VDN_INL {
         if (nt < 8) {
@@ -152,7 +169,8 @@ __global__ __launch_bounds__(256, 2) void nerf_fwd2_kernel(NerfArgs a) {
             if (a.save_vpe != nullptr) P::template store_tile<kSt>(reinterpret_cast<ST*>(a.save_vpe), q, 32, 0, h, t16, true);
         }
     }
-    auto f10 = flow::dense2<PG, 4, false>(f9, pp, X, flow::NoLoad{}, relu_into(Y, 0, reinterpret_cast<ST*>(a.save_hv), 128));
+    auto f10 = flow::dense2<PG, 4, false>(f9, pp, X, flow::NoLoad{}, relu_into(Y, 0, reinterpret_cast<ST*>(a.save_hv), 128,
+                                                                             static_cast<unsigned char*>(a.save_mask_v)));
     // rgb_linear (image tile 0, rows 0..2) and dpt_linear (image tiles 1..3)
     auto f11 = flow::dense2<PG, DPT ? 4 : 1>(f10, pp, Y, flow::NoLoad{}, [&](int nt, const f32x16& acc, int) VDN_INL {
         if (nt == 0) {
@@ -175,15 +193,18 @@ inline int launch_nerf_fwd2(const VdnNerfArgs* args, void* stream_) {
     if (!args->dirs && !args->rays_d) return -1;
     const bool save = args->save_h != nullptr;
     if (save && (!args->save_hv || !args->save_feature)) return -1;
+    const bool mask = args->save_mask != nullptr;
+    if (mask != (args->save_mask_v != nullptr) || (mask && !save)) return -2;
     const int grid = (args->P + 127) / 128;
     const size_t lds = 3 * BF16::stride(11);
     static bool once = (allow_big_lds(nerf_fwd2_kernel<false, false>, lds), allow_big_lds(nerf_fwd2_kernel<true, false>, lds),
-                        allow_big_lds(nerf_fwd2_kernel<false, true>, lds), allow_big_lds(nerf_fwd2_kernel<true, true>, lds), true);
+                        allow_big_lds(nerf_fwd2_kernel<false, true>, lds), allow_big_lds(nerf_fwd2_kernel<true, true>, lds),
+                        allow_big_lds(nerf_fwd2_kernel<false, true, true>, lds), allow_big_lds(nerf_fwd2_kernel<true, true, true>, lds), true);
     (void)once;
     const bool dpt = args->feat != nullptr;
-#define VDN_L(D, S) hipLaunchKernelGGL((nerf_fwd2_kernel<D, S>), dim3(grid), dim3(256), lds, stream, *args)
-    if (dpt) { if (save) VDN_L(true, true); else VDN_L(true, false); }
-    else { if (save) VDN_L(false, true); else VDN_L(false, false); }
+#define VDN_L(D, S, M) hipLaunchKernelGGL((nerf_fwd2_kernel<D, S, M>), dim3(grid), dim3(256), lds, stream, *args)
+    if (dpt) { if (mask) VDN_L(true, true, true); else if (save) VDN_L(true, true, false); else VDN_L(true, false, false); }
+    else { if (mask) VDN_L(false, true, true); else if (save) VDN_L(false, true, false); else VDN_L(false, false, false); }
 #undef VDN_L
     return (int)hipGetLastError();
 }

@@ -9,7 +9,9 @@
 
 namespace vdn {
 
-template <class P, int NT_OUT, int EX = 0>      // EX: extra input tiles of the d_feature = 352 network (k_render_fwd.h)
+// MASK (bf16): the ReLU' of the chain comes from the forward's 1-bit masks (a.mask; mlp_engine.h: BF16::relu_bits) instead of
+// the saved planes: one 16-byte load per layer in place of eight 1-KiB tile loads
+template <class P, int NT_OUT, int EX = 0, bool MASK = false>      // EX: extra input tiles of the d_feature = 352 network (k_render_fwd.h)
 __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void rendernet_bwd_kernel(RenderNetBwdArgs a) {
     using ST = typename P::store_t;
     constexpr int kSlot = P::stride(8);
@@ -28,6 +30,15 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void rendernet_b
     ST* delta_h = reinterpret_cast<ST*>(a.delta_h);
     ST* delta_out = reinterpret_cast<ST*>(a.delta_out);
     ST* d_feat = reinterpret_cast<ST*>(a.d_feat);
+    // MASK: all four layers' masks (16 VGPRs) are loaded here, ahead of the output delta's loads; they land under the weight
+    // stream's warm-up wait (mask_landed below)
+    unsigned mk[MASK ? 16 : 1];
+    if constexpr (MASK) {
+        const unsigned char* m = static_cast<const unsigned char*>(a.mask);
+        const long MS = BF16::mask_plane(a.P, 256);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) BF16::load_mask<4>(m + l * MS, p, h, mk + 4 * l);
+    }
 
     typename P::template Act<8> X, Y;
     if constexpr (NT_OUT == 1) {
@@ -66,13 +77,29 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void rendernet_b
             P::store_tile(delta_h + l * PS, p, 256, nt, h, o, ok);
         };
     };
+    // D = acc * mask bit (MASK): the same select, no plane loads
+    auto bit_store = [&](auto& D, int l) VDN_INL {
+        return [&D, &mk, l, delta_h, PS, p, ok, h](int nt, const f32x16& acc, int) VDN_INL {
+            const f32x16 o = BF16::mask_select(mk + 4 * l, nt, acc);
+            D.set(nt, o);
+            P::store_tile(delta_h + l * PS, p, 256, nt, h, o, ok);
+        };
+    };
     ws.all_issue = __any(ok);
+    if constexpr (MASK) BF16::mask_landed(mk);
     warm_l2_wait();
     ws.start();
-    dense<P, NT_OUT, 8, false, kBwdPrefetch>(ws, X, 0, ldH(3), mask_store(Y, 3), P::kTileOps, P::kTileOps);   // W4^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(2), mask_store(X, 2), P::kTileOps, P::kTileOps);        // W3^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, X, 0, ldH(1), mask_store(Y, 1), P::kTileOps, P::kTileOps);        // W2^T
-    dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(0), mask_store(X, 0), P::kTileOps, P::kTileOps);        // W1^T
+    if constexpr (MASK) {
+        dense<P, NT_OUT, 8, false>(ws, X, 0, NoPre{}, bit_store(Y, 3), P::kTileOps);    // W4^T
+        dense<P, 8, 8, false>(ws, Y, 0, NoPre{}, bit_store(X, 2), P::kTileOps);         // W3^T
+        dense<P, 8, 8, false>(ws, X, 0, NoPre{}, bit_store(Y, 1), P::kTileOps);         // W2^T
+        dense<P, 8, 8, false>(ws, Y, 0, NoPre{}, bit_store(X, 0), P::kTileOps);         // W1^T
+    } else {
+        dense<P, NT_OUT, 8, false, kBwdPrefetch>(ws, X, 0, ldH(3), mask_store(Y, 3), P::kTileOps, P::kTileOps);   // W4^T
+        dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(2), mask_store(X, 2), P::kTileOps, P::kTileOps);        // W3^T
+        dense<P, 8, 8, false, kBwdPrefetch>(ws, X, 0, ldH(1), mask_store(Y, 1), P::kTileOps, P::kTileOps);        // W2^T
+        dense<P, 8, 8, false, kBwdPrefetch>(ws, Y, 0, ldH(0), mask_store(X, 0), P::kTileOps, P::kTileOps);        // W1^T
+    }
     f32x16 SM[2];
     dense<P, 8, 10 + EX, false>(ws, X, 0, NoPre{}, [&](int nt, const f32x16& acc, int) VDN_INL {   // W0^T
         if (nt >= 10) {
@@ -136,6 +163,24 @@ int launch_rendernet_bwd(const VdnRenderNetBwdArgs* args, void* stream_) {
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     const size_t lds = 3 * P::stride(8);
+    if (args->mask != nullptr) {
+        if constexpr (std::is_same<P, BF16>::value) {
+            static bool once_m = (allow_big_lds(rendernet_bwd_kernel<P, 1, 0, true>, lds), allow_big_lds(rendernet_bwd_kernel<P, 3, 0, true>, lds),
+                                  allow_big_lds(rendernet_bwd_kernel<P, 1, 3, true>, lds), true);
+            (void)once_m;
+            if (args->d_extra != nullptr) {
+                if (args->d_out == 96) return -4;
+                hipLaunchKernelGGL((rendernet_bwd_kernel<P, 1, 3, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args);
+            } else if (args->d_out == 96) {
+                hipLaunchKernelGGL((rendernet_bwd_kernel<P, 3, 0, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args);
+            } else {
+                hipLaunchKernelGGL((rendernet_bwd_kernel<P, 1, 0, true>), dim3(grid), dim3(P::kWaves * 64), lds, stream, *args);
+            }
+            return (int)hipGetLastError();
+        } else {
+            return -5;          // ReLU masks: the bf16 path only
+        }
+    }
     static bool once = (allow_big_lds(rendernet_bwd_kernel<P, 1>, lds), allow_big_lds(rendernet_bwd_kernel<P, 3>, lds),
                         allow_big_lds(rendernet_bwd_kernel<P, 1, 3>, lds), true);
     (void)once;

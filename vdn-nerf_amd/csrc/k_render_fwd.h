@@ -65,13 +65,26 @@ VDN_DEV void rendernet_fwd_body(const RenderNetArgs& a, char* smem) {
             if (save_small != nullptr) P::store_tile(save_small, p, 64, kt, h, t16, ok);
         }
     }
+    // bf16 training with a.save_mask: the layer's 1-bit ReLU mask gathers in mk (tiles 2i, 2i + 1 in word i) and goes out in
+    // one store behind its last tile (uncounted in `est`: a lower bound)
+    unsigned char* const save_mask = static_cast<unsigned char*>(a.save_mask);
+    const long MS = P::plane(a.P, 32);          // = BF16::mask_plane(P, 256) bytes (unused by F32: its launcher refuses masks)
+    unsigned mk[4];
     auto relu_into = [&](auto& D, int l) VDN_INL {
-        return [&D, l, save_h, PS, p, ok, h](int nt, const f32x16& acc, int) VDN_INL {
+        return [&D, &mk, l, save_h, save_mask, MS, PS, p, ok, h](int nt, const f32x16& acc, int) VDN_INL {
             f32x16 o;
 #pragma unroll
             for (int t = 0; t < 16; ++t) o[t] = relu0(acc[t]);
             D.set(nt, o);
             if (save_h != nullptr) P::store_tile(save_h + l * PS, p, 256, nt, h, o, ok);
+            if constexpr (std::is_same<P, BF16>::value) {
+                if (save_mask != nullptr) {
+                    const unsigned b = BF16::relu_bits(o);
+                    if (nt & 1) mk[nt >> 1] |= b << 16;
+                    else mk[nt >> 1] = b;
+                    if (nt == 7) BF16::store_mask<4>(save_mask + l * MS, p, h, mk, ok);
+                }
+            }
         };
     };
     const int est = save_h != nullptr ? P::kTileOps : 0;
@@ -109,6 +122,7 @@ int launch_rendernet_fwd(const VdnRenderNetArgs* args, void* stream_) {
     if (!args->pts && (!args->rays_o || !args->rays_d || !args->z)) return -1;
     if (!args->dirs && !args->rays_d) return -1;
     if (!(args->d_out == 96 || (args->d_out >= 1 && args->d_out <= 4))) return -2;
+    if (args->save_mask && (!args->save_h || !std::is_same<P, BF16>::value)) return -4;       // ReLU masks: bf16 training saves
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     if (args->extra != nullptr) {

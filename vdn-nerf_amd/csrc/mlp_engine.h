@@ -431,6 +431,79 @@ struct BF16 {
     static VDN_DEV f32x16 load_tile(const unsigned short* base, long row, int ld, int tile, int h) {
         return unpack(load_raw(base, row, ld, tile, h));
     }
+
+    // 1-bit ReLU masks of a saved layer (the backward chains' ReLU' source in place of the bf16 plane; vdn_hip/layout.py:
+    // mask_from_plane decodes them). Lane (point c, half h) keeps 16 bits per 32-feature tile, bit 16 tile + t = accumulator
+    // register t of that tile: NW = ld / 64 words per lane (4 at ld 256, 2 at ld 128). A layer's plane is
+    // [row >> 5][h (2)][row & 31][4 NW bytes], rows padded to 32: one wave's store / load of a layer is ONE contiguous run
+    // (1 KiB at ld 256).
+    static VDN_DEV long mask_plane(long P, int ld) { return rows(P) * (ld / 8); }     // bytes
+    // bit t = [the bf16 value store_tile writes for v[t] > 0], evaluated on the packed words exactly as the plane-reading
+    // backward evaluates it on the loaded plane (+inf and NaN with a clear sign pass; positives that round to +0 do not)
+    static VDN_DEV unsigned relu_bits(const f32x16& v) {
+        unsigned m = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned u = pack_bf16x2(v[2 * j], v[2 * j + 1]);
+            m |= (bf16_lo(u) > 0.0f ? 1u : 0u) << (2 * j);
+            m |= (bf16_hi(u) > 0.0f ? 1u : 0u) << (2 * j + 1);
+        }
+        return m;
+    }
+    template <int NW>
+    static VDN_DEV unsigned char* mask_ptr(unsigned char* base, long row, int h) {
+        return base + (row >> 5) * (64L * 4 * NW) + h * (32 * 4 * NW) + (row & 31) * (4 * NW);
+    }
+    // one vector store of a layer's NW words, cache policy MODE as store_tile
+    template <int NW, int MODE = VDN_PLANE_ST_MODE>
+    static VDN_DEV void store_mask(unsigned char* base, long row, int h, const unsigned (&m)[NW], bool ok) {
+        static_assert(NW == 2 || NW == 4, "mask: 128- or 256-wide layers");
+        if (!ok) return;
+        unsigned char* p = mask_ptr<NW>(base, row, h);
+        if constexpr (NW == 4) {
+            typedef unsigned mk_u32x4 __attribute__((ext_vector_type(4)));
+            const mk_u32x4 ov = {m[0], m[1], m[2], m[3]};
+            if constexpr (MODE == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 2) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 3) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 4) { asm volatile("" ::"v"(p), "v"(ov)); }
+            else *reinterpret_cast<uint4*>(p) = make_uint4(m[0], m[1], m[2], m[3]);
+        } else {
+            typedef unsigned mk_u32x2 __attribute__((ext_vector_type(2)));
+            const mk_u32x2 ov = {m[0], m[1]};
+            if constexpr (MODE == 1) asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 2) asm volatile("global_store_dwordx2 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 3) asm volatile("global_store_dwordx2 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(ov) : "memory");
+            else if constexpr (MODE == 4) { asm volatile("" ::"v"(p), "v"(ov)); }
+            else *reinterpret_cast<uint2*>(p) = make_uint2(m[0], m[1]);
+        }
+    }
+    template <int NW>
+    static VDN_DEV void load_mask(const unsigned char* base, long row, int h, unsigned* m) {
+        const unsigned char* p = mask_ptr<NW>(const_cast<unsigned char*>(base), row, h);
+        if constexpr (NW == 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(p);
+            m[0] = v.x; m[1] = v.y; m[2] = v.z; m[3] = v.w;
+        } else {
+            const uint2 v = *reinterpret_cast<const uint2*>(p);
+            m[0] = v.x; m[1] = v.y;
+        }
+    }
+    // the compiler's own wait for the mask loads, placed here (in front of a wait that drains the queue anyway) instead of at
+    // their first use deep in the chain, where it would be a vmcnt(0) behind the weight stream's in-flight DMA
+    template <int N>
+    static VDN_DEV void mask_landed(unsigned (&m)[N]) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) asm volatile("" : "+v"(m[i]));
+    }
+    // acc where the mask bit of (tile nt, register t) is set, else 0: the ReLU' select of the backward chains
+    static VDN_DEV f32x16 mask_select(const unsigned* m, int nt, const f32x16& acc) {
+        const unsigned b = m[nt >> 1] >> (16 * (nt & 1));
+        f32x16 o;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) o[t] = ((b >> t) & 1u) ? acc[t] : 0.0f;
+        return o;
+    }
 };
 
 // One dense layer on the wave's 32 points: for every output tile nt, acc = bias + W[nt] . X[x0 ..],

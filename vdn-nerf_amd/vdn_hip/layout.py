@@ -41,3 +41,15 @@ def col_offset_elems(col0, precision):
         return col0
     assert col0 % 32 == 0
     return (col0 // 32) * 1024
+
+
+def mask_from_plane(buf, P, ld):
+    """1-bit ReLU mask plane of one layer (csrc/mlp_engine.h: BF16::relu_bits) -> bool [P, ld].
+
+    Per block of 32 points: [h(2)][point(32)][ld/16 bytes]; lane (point, h) keeps 16 bits per 32-feature tile, bit 16 tile + t
+    (little-endian) = accumulator register t = 8k + 4j + e, feature 32 tile + 16k + 8j + 4h + e (the PT32 order above)."""
+    Pp = pad32(P)
+    b = buf.reshape(-1)[:Pp * ld // 8].view(Pp // 32, 2, 32, ld // 16).long()
+    bits = (b.unsqueeze(-1) >> torch.arange(8, device=b.device)) & 1         # [blk, h, c, byte, bit]: bit 16 tile + t
+    bits = bits.reshape(Pp // 32, 2, 32, ld // 32, 2, 2, 4)                   # [blk, h, c, tile, k, j, e]
+    return bits.permute(0, 2, 3, 4, 5, 1, 6).reshape(Pp, ld)[:P].bool()     # [blk, c, tile, k, j, h, e]

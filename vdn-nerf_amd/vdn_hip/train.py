@@ -331,6 +331,14 @@ class TrainEngine:
             w["vdn_out"], w["vdn_h"], w["vdn_small"] = fz(P, 96), fs(4, Pp, 256), fs(Pp, 64)
         if self.dbc:
             w["col_extra"] = fs(Pp, 96)
+        # 1-bit ReLU masks of the heads' and the background network's hidden layers (bf16; csrc/mlp_engine.h: BF16::relu_bits, decoded
+        # by layout.mask_from_plane): the forwards write them beside the bf16 planes, the backward chains read them instead of the
+        # planes (which the weight-gradient GEMM still reads). VDN_RELU_MASK=0: not written, the chains read the planes
+        self.relu_mask = self.precision == "bf16" and os.environ.get("VDN_RELU_MASK", "1") != "0"
+        fm = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev) if self.relu_mask else None
+        w["col_mask"] = fm(4, Pp * 32)
+        if self.wdepth:
+            w["vdn_mask"] = fm(4, Pp * 32)
         if O > 0:
             w["z_feed"], w["bg_dists"], w["bg_mid"] = f(B, T), f(B, T), out("bg_mid")
             # zero-initialised: points the active list skips keep finite values (the compositor multiplies them by zero)
@@ -339,6 +347,7 @@ class TrainEngine:
             w["bg_active"] = (torch.zeros(Q, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
                               torch.zeros(B, dtype=torch.int32, device=dev))
             w["nf_h"], w["nf_pe"], w["nf_feature"], w["nf_vpe"], w["nf_hv"] = fs(8, Qp, 256), fs(Qp, 96), fs(Qp, 256), fs(Qp, 32), fs(Qp, 128)
+            w["nf_mask"], w["nf_mask_v"] = fm(8, Qp * 32), fm(Qp * 16)
         w["weights"], w["alpha"], w["cdf"], w["inside"] = out("weights"), f(B, T), out("cdf"), out("inside")
         w["color"], w["wsum"], w["wmax"], w["s_val"] = out("color"), out("wsum"), out("wmax"), out("s_val")
         w["eik_partial"], w["eik"] = f(B, 2), out("eik")
@@ -588,6 +597,8 @@ class TrainEngine:
             n.density, n.rgb = w["bg_density"].data_ptr(), w["bg_rgb"].data_ptr()
             n.feat = w["bg_feat"].data_ptr() if w["bg_feat"] is not None else None
             n.save_h, n.save_pe, n.save_feature, n.save_vpe, n.save_hv = (w[k].data_ptr() for k in ("nf_h", "nf_pe", "nf_feature", "nf_vpe", "nf_hv"))
+            if self.relu_mask:
+                n.save_mask, n.save_mask_v = w["nf_mask"].data_ptr(), w["nf_mask_v"].data_ptr()
             # only the background samples the compositor does not multiply by zero (saves are in compact order)
             if self._bg_compact:
                 if not fused_prep:
@@ -615,6 +626,8 @@ class TrainEngine:
             c.rays_o, c.rays_d, c.z, c.n_per_ray = rays_o.data_ptr(), rays_d.data_ptr(), w["mid_z"].data_ptr(), N
             c.normals, c.feat, c.out = w["normals"].data_ptr(), w["feat"].data_ptr(), out.data_ptr()
             c.save_h, c.save_small = save_h.data_ptr(), small.data_ptr()
+            if self.relu_mask:
+                c.save_mask = w[net[:3] + "_mask"].data_ptr()
             c.P, c.d_out, c.squeeze_out = self.P, d_out, int(module.squeeze_out)
             if net == "color" and self.dbc:          # renderer.py:247-248
                 c.extra, c.save_extra = w["vdn_out"].data_ptr(), w["col_extra"].data_ptr()
@@ -953,6 +966,8 @@ class TrainEngine:
             nb.g_density, nb.g_rgb = w["d_bg_density"].data_ptr(), w["d_bg_rgb"].data_ptr()
             nb.g_feat = w["d_bg_feat"].data_ptr() if self.wdepth else None
             nb.save_h, nb.save_hv = w["nf_h"].data_ptr(), w["nf_hv"].data_ptr()
+            if self.relu_mask:
+                nb.mask, nb.mask_v = w["nf_mask"].data_ptr(), w["nf_mask_v"].data_ptr()
             nb.delta_o, nb.delta_v, nb.delta_head, nb.delta_h = (w[k].data_ptr() for k in ("nf_do", "nf_dv", "nf_dhead", "nf_dh"))
             nb.P = self.Q
             if self._bg_compact:
@@ -981,6 +996,9 @@ class TrainEngine:
             b = lib.VdnRenderNetBwdArgs()
             b.blob = self.nets[net].img.blobs["bwd"].data_ptr()
             b.g_out, b.out, b.save_h = g_out.data_ptr(), out.data_ptr(), save_h.data_ptr()
+            # (the fused SDF + colour launch writes no colour mask)
+            if self.relu_mask and not (net == "color" and self._color_fused):
+                b.mask = w[net[:3] + "_mask"].data_ptr()
             b.delta_out, b.delta_h = dout.data_ptr(), dh.data_ptr()
             b.d_feat, b.d_normals = w["d_featvec"].data_ptr(), w["d_normals"].data_ptr()
             b.acc_feat, b.acc_normals = int(accumulate), 1
