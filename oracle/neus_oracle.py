@@ -27,6 +27,8 @@ from typing import Optional, Sequence
 import torch
 import torch.nn.functional as F
 
+from .ray_ops import background_alpha, composite, excl_cumprod_weights, inv_s_from_variance  # noqa: F401
+
 SQRT2 = math.sqrt(2.0)
 
 
@@ -253,11 +255,6 @@ def nerf_forward(p, input_pts, input_views, conf: NeRFConf):
     return alpha, rgb, feat
 
 
-def inv_s_from_variance(variance):
-    """fields.py:363-364 + renderer.py:262: exp(10 v).clip(1e-6, 1e6)."""
-    return torch.exp(variance * 10.0).clip(1e-6, 1e6)
-
-
 # ----------------------------------------------------------------------------
 # a10: inverse-CDF sampling  (renderer.py:44-74), det=True only (renderer.py:190)
 # ----------------------------------------------------------------------------
@@ -278,13 +275,6 @@ def sample_pdf_det(bins, weights, n_samples):
     denom = torch.where(denom < 1e-5, torch.ones_like(denom), denom)
     t = (u - cdf_b) / denom
     return bin_b + t * (bin_a - bin_b)
-
-
-def excl_cumprod_weights(alpha):
-    """alpha * exclusive-cumprod(1 - alpha + 1e-7)  (renderer.py:126,187-188,301)."""
-    B = alpha.shape[0]
-    one = torch.ones(B, 1, dtype=alpha.dtype, device=alpha.device)
-    return alpha * torch.cumprod(torch.cat([one, 1.0 - alpha + 1e-7], -1), -1)[:, :-1]
 
 
 # ----------------------------------------------------------------------------
@@ -377,8 +367,8 @@ def render_core_outside(nets: Nets, rays_o, rays_d, z_vals, sample_dist):
     pts4 = torch.cat([pts / r, 1.0 / r], -1)                                      # renderer.py:114-115
     dirs = rays_d[:, None, :].expand(B, T, 3)
     density, rgb, feat = nerf_forward(nets.nerf, pts4.reshape(-1, 4), dirs.reshape(-1, 3), nets.nerf_conf)
-    alpha = 1.0 - torch.exp(-F.softplus(density.reshape(B, T)) * dists)           # renderer.py:124
-    return {"alpha": alpha, "sampled_color": rgb.reshape(B, T, -1),
+    alpha = background_alpha(density.reshape(B, T), dists)                         # renderer.py:124
+    return {"alpha": alpha, "density": density.reshape(B, T), "dists": dists, "sampled_color": rgb.reshape(B, T, -1),
             "sampled_feat": None if feat is None else feat.reshape(B, T, -1), "z_vals": mid_z}
 
 
@@ -405,46 +395,18 @@ def render_core(nets: Nets, rays_o, rays_d, z_vals, sample_dist, bg=None, backgr
         sampled_feat = sampled_feat.reshape(B, N, -1)
     sampled_color = rendering_forward(nets.color, pts, gradients, dirs, feature, nets.color_conf).reshape(B, N, -1)
 
-    inv_s = inv_s_from_variance(nets.variance)                                     # renderer.py:262-263
-    true_cos = (dirs * gradients).sum(-1, keepdim=True)                            # renderer.py:265
-    iter_cos = -(F.relu(-true_cos * 0.5 + 0.5) * (1.0 - cos_anneal_ratio) +
-                 F.relu(-true_cos) * cos_anneal_ratio)                             # renderer.py:269-270
-    d = dists.reshape(-1, 1)
-    est_next = sdf + iter_cos * d * 0.5
-    est_prev = sdf - iter_cos * d * 0.5
-    prev_cdf = torch.sigmoid(est_prev * inv_s)
-    next_cdf = torch.sigmoid(est_next * inv_s)
-    p, c = prev_cdf - next_cdf, prev_cdf
-    alpha = ((p + 1e-5) / (c + 1e-5)).reshape(B, N).clip(0.0, 1.0)                 # renderer.py:282
-
-    pts_norm = torch.linalg.norm(pts, ord=2, dim=-1, keepdim=True).reshape(B, N)
-    inside = (pts_norm < 1.0).to(z_vals.dtype).detach()
-    relax = (pts_norm < 1.2).to(z_vals.dtype).detach()
-
-    if bg is not None:                                                             # renderer.py:289-299
-        alpha = alpha * inside + bg["alpha"][:, :N] * (1.0 - inside)
-        alpha = torch.cat([alpha, bg["alpha"][:, N:]], -1)
-        sampled_color = sampled_color * inside[:, :, None] + bg["sampled_color"][:, :N] * (1.0 - inside)[:, :, None]
-        sampled_color = torch.cat([sampled_color, bg["sampled_color"][:, N:]], 1)
-        if sampled_feat is not None:
-            sampled_feat = sampled_feat * inside[:, :, None] + bg["sampled_feat"][:, :N] * (1.0 - inside)[:, :, None]
-            sampled_feat = torch.cat([sampled_feat, bg["sampled_feat"][:, N:]], 1)
-
-    weights = excl_cumprod_weights(alpha)                                          # renderer.py:301
-    weights_sum = weights.sum(-1, keepdim=True)
-    color = (sampled_color * weights[:, :, None]).sum(1)
-    d_feats = None if sampled_feat is None else (sampled_feat * weights[:, :, None]).sum(1)
-    if background_rgb is not None:
-        color = color + background_rgb * (1.0 - weights_sum)                       # renderer.py:309-310
-
+    # renderer.py:262-315: the compositor, as a function of plain tensors (oracle/ray_ops.py)
+    has_bg = bg is not None
+    cp = composite(rays_o, rays_d, sdf, gradients, dists, mid_z, sampled_color, sampled_feat, nets.variance,
+                   bg["density"] if has_bg else None, bg["sampled_color"] if has_bg else None,
+                   bg["sampled_feat"] if has_bg else None, bg["dists"] if has_bg else None, background_rgb, cos_anneal_ratio)
+    d_feats, color, weights, alpha = cp["d_feats"], cp["color"], cp["weights"], cp["alpha"]
+    c, inside, sampled_color = cp["cdf"], cp["inside_sphere"], cp["sampled_color"]
+    eik_num, eik_den, gradient_error = cp["eik_num"], cp["eik_den"], cp["gradient_error"]
     g3 = gradients.reshape(B, N, 3)
-    gerr = (torch.linalg.norm(g3, ord=2, dim=-1) - 1.0) ** 2
-    eik_num = (relax * gerr).sum()
-    eik_den = relax.sum()
-    gradient_error = eik_num / (eik_den + 1e-5)                                    # renderer.py:313-315
     return {"d_feats": d_feats, "color": color, "sdf": sdf, "dists": dists, "gradients": g3,
-            "s_val": (1.0 / inv_s).expand(B * N, 1), "mid_z_vals": mid_z, "weights": weights,
-            "cdf": c.reshape(B, N), "gradient_error": gradient_error, "inside_sphere": inside,
+            "s_val": cp["s_val"].expand(B * N, 1), "mid_z_vals": mid_z, "weights": weights,
+            "cdf": c, "gradient_error": gradient_error, "inside_sphere": inside,
             "eik_num": eik_num, "eik_den": eik_den, "alpha": alpha,
             "sampled_color": sampled_color, "feature": feature}
 

@@ -35,8 +35,11 @@ __global__ __launch_bounds__(1024) void loss_kernel(LossArgs a) {
             a.g_color[r * 3 + k] = sgn * m / mask_sum * a.grad_scale;
         }
         if (a.mask_weight != 0.0f && a.g_weights != nullptr) {
-            float ws = 0.0f;
-            for (int i = 0; i < a.T; ++i) ws += a.weights[(long)r * a.T + i];
+            // weight_sum in double, like the compositor's own: next to the upper clip gate 1 - ws is ~1e-3, so the BCE
+            // gradient's (1 - m) / (1 - ws) term needs ws good to ~1e-8; a float sum over T samples is ~1e-6 off
+            double ws_d = 0.0;
+            for (int i = 0; i < a.T; ++i) ws_d += (double)a.weights[(long)r * a.T + i];
+            const float ws = (float)ws_d;
             const float wc = fminf(fmaxf(ws, 1e-3f), 1.0f - 1e-3f);
             bce += -(double)(m * logf(wc) + (1.0f - m) * logf(1.0f - wc));
             const bool inside = ws >= 1e-3f && ws <= 1.0f - 1e-3f;
