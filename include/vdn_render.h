@@ -333,6 +333,16 @@ int vdn_sdf_color_train_bf16(const VdnSdfArgs* sdf_host, const void* color_blob,
                              float* col_out, void* stream);
 int vdn_shade_fused_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, const VdnCompositeArgs* comp_host,
                          int32_t* ticket, void* stream);
+/* Shading of free-standing points in ONE launch (bf16; csrc/k_sdf_fwd2.h MODE 4) - the vertex attributes of a mesh that goes to
+ * disk (vdn_hip/mesh.py: shade_points). Per point x (fp32, object space):
+ *     sdf, feat = sdf_network(x);   g = sdf_network.gradient(x)   (raw, not normalised: what render_core feeds the colour head)
+ *     view = -g / max(|g|, 1e-12)   (torch.nn.functional.normalize's convention: a zero gradient gives a zero direction, never NaN)
+ *     colour = color_network(x, g, view, feat)
+ * sdf_host: mode-1 arguments in point form (pts [P,3], any P > 0; sdf [P] and normals [P,3] = g are required outputs; feat is not
+ * written and must be NULL); color_blob: the colour network's "c2" stream (mode 'idr', d_feature = 256, d_out = 3); col_out [P,3]:
+ * the colour in the network's own channel order. sdf / normals are the bits of vdn_sdf_mlp_fwd_bf16(mode 1). Declines (-10, nothing
+ * launched) what it does not cover: training saves (H / V / PE / U_pe), a feature plane, a work list, the tail split. */
+int vdn_shade_points_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, float* col_out, void* stream);
 
 /* The eikonal sums of renderer.py:313-315 alone - relax_inside_sphere * (|gradient| - 1)^2 and relax_inside_sphere, summed
  * per ray and over the batch, with the compositor's own expressions (same translation unit, bit-identical to the values

@@ -437,6 +437,13 @@ constexpr int pair_begin(int gi, int GA) { return gi >= GA ? 8 : gi * 8 / GA; }
 // vector kept in registers, then the colour head on the same 32 points per wave, then - a 128-point workgroup being exactly one
 // ray of 128 samples - the ray's NeuS alpha, background blend, transmittance scan and weighted sums (k_composite_row.h) by wave 0
 // on the samples handed over in LDS, and the eikonal sums of all rays by the ray that finishes last.
+// MODE 4 ("shade points": the vertex attributes of a mesh that goes to disk, vdn_shade_points_bf16): the same pipeline on free-standing
+// points, any P (partial last workgroup / wave by the `ok` predicate, as MODE 1) - no ray, no compositor, no saves, no feature plane.
+// Per point x (fp32, object space):
+//     sdf, feat = sdf_network(x);   g = sdf_network.gradient(x)   (raw, not normalised: what render_core feeds the colour head)
+//     view = -g / max(|g|, 1e-12)   (torch.nn.functional.normalize's convention: a zero gradient gives a zero direction, never NaN)
+//     colour = color_network(x, g, view, feat)
+// The one difference from MODE 2 / 3: the view direction is formed from the normal the sweep has just produced.
 struct ShadeExtra {
     const char* color_blob;     // the colour head's chunk stream ("c2", vdn_hip/images.py), same chunk format and stride
     int* ticket;                // [1] arrival counter, zero before the first launch (the last ray leaves it zero)
@@ -444,7 +451,7 @@ struct ShadeExtra {
     int warm_bytes, warm_bytes2;    // all modes: bytes of the weight stream(s) the first round of workgroups pulls into L2 up front (0 = off; vdn_common.h: warm_l2)
     void* col_h;                // MODE 3: [4, rows, 256] the colour head's saved hidden activations (PT32 planes, compact rows)
     void* col_small;            // MODE 3: [rows, 64] its 33 small inputs (points, PE4(view), normal) as the weight-gradient GEMM reads them
-    float* col_out;             // MODE 3: [P,3] the sampled colour (dense point id)
+    float* col_out;             // MODE 3 / 4: [P,3] the sampled colour (dense point id)
     CompositeArgs cm;           // sdf / normals / color are not read (the samples come through LDS)
 };
 
@@ -498,6 +505,10 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     if (a.pts != nullptr) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) xin[d] = a.pts[pd * 3 + d] * a.scale;
+        if constexpr (MODE == 4) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) px[d] = a.pts[pd * 3 + d];
+        }
     } else {
         const long r = pd / a.n_per_ray;
         const long sidx = pd - r * a.n_per_ray;
@@ -879,6 +890,13 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                 // the normal is complete: the colour head's small input tile [points (3), PE4(view) (27), normal x, y] (fields.py:154;
                 // k order of the "c2" stream), z component kept in f32
                 float small[32], pe[27];
+                if constexpr (MODE == 4) {      // the point is looked at straight down its normal
+                    const float gx = n[0] * a.scale, gy = n[1] * a.scale, gz = n[2] * a.scale;
+                    const float inv = -1.0f / fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-12f);
+                    dir[0] = gx * inv;
+                    dir[1] = gy * inv;
+                    dir[2] = gz * inv;
+                }
                 posenc<3, 4, P::kAccurateTrig>(dir, pe);
 #pragma unroll
                 for (int d = 0; d < 3; ++d) small[d] = px[d];
@@ -917,7 +935,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
         if (ok && h == 0) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) a.normals[pd * 3 + d] = n[d] * a.scale;
-            if constexpr (MODE == 3) {
+            if constexpr (MODE == 3 || MODE == 4) {
 #pragma unroll
                 for (int d = 0; d < 3; ++d) ex.col_out[pd * 3 + d] = col[d];
             }

@@ -2,7 +2,13 @@
   marching_cubes  - vdn_mesh_mc_count / vdn_mesh_mc_emit: the classic 256-case marching cubes with PyMCubes' own vertex and
                     triangle numbering (include/vdn_render.h; the default of extract_geometry since round 6);
   marching_tets   - vdn_mesh_count / vdn_mesh_emit: marching tetrahedra on the Kuhn decomposition (rounds 3-5), kept as an option.
-The prefix sums (and the tetrahedra form's vertex welding) are torch ops on the device; nothing runs on the host."""
+The prefix sums (and the tetrahedra form's vertex welding) are torch ops on the device; nothing runs on the host.
+
+shade_points evaluates the networks at free-standing surface points - the vertex attributes of a mesh that goes to disk
+(NeuSRenderer.extract_colored_geometry, vdn_train.validate.validate_mesh)."""
+import os
+
+import numpy as np
 import torch
 
 from . import lib
@@ -68,3 +74,70 @@ def marching_cubes(u, threshold=0.0):
     a.vert_offsets, a.tri_offsets, a.vertices, a.triangles = vo.data_ptr(), to.data_ptr(), vertices.data_ptr(), triangles.data_ptr()
     lib.call("vdn_mesh_mc_emit", a, st)
     return vertices, triangles
+
+
+def fused_point_shading(renderer):
+    """True where vdn_shade_points_bf16 (csrc/k_sdf_fwd2.h MODE 4) covers the configuration: both networks on the bf16 kernels and
+    the colour head the "c2" stream exists for ('idr', d_feature 256, d_out 3). VDN_SHADE_POINTS_FUSED=0 forces the separate launches."""
+    sn, cn = renderer.sdf_network, renderer.color_network
+    return (os.environ.get("VDN_SHADE_POINTS_FUSED", "1") != "0" and sn.precision == "bf16" and cn.precision == "bf16"
+            and cn.conf.get("mode") == "idr" and cn.conf.get("d_feature") == 256 and cn.conf.get("d_out") == 3)
+
+
+def view_from_gradient(g):
+    """The view direction a surface point is shaded with: straight down its normal, -g / max(|g|, 1e-12) - the convention of
+    torch.nn.functional.normalize, so a zero gradient gives a zero direction, never NaN."""
+    return -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+
+
+def quantize_colors_bgr(c):
+    """The colour network's output [V,3] (float, BGR order: vdn_train/dataset.py trains in cv.imread's order) -> uint8 RGB:
+    rint(clip(c, 0, 1) * 255) in the array's own precision, channels reversed. rint rounds to nearest, halves to even
+    (0.5 -> 127.5 -> 128)."""
+    c = np.asarray(c)
+    if c.ndim != 2 or c.shape[1] != 3 or not np.issubdtype(c.dtype, np.floating):
+        raise ValueError("colours must be a float [V,3] array, got %s %s" % (c.dtype, c.shape))
+    q = np.rint(np.clip(c, 0.0, 1.0) * 255).astype(np.uint8)
+    return np.ascontiguousarray(q[:, ::-1])
+
+
+def shade_points(renderer, points, batch=1 << 20):
+    """points [P,3] (object space) -> (sdf [P], gradient [P,3], colour [P,3]) as fp32 device tensors:
+        sdf, feat = sdf_network(x);  g = sdf_network.gradient(x)  (raw, as render_core feeds it to the colour head);
+        view = -g / max(|g|, 1e-12);  colour = color_network(x, g, view, feat)  (the network's own channel order: BGR).
+    At most `batch` points per launch, so the workspace is bounded at any mesh size. bf16 networks with the covered colour head:
+    ONE launch per batch (vdn_shade_points_bf16); otherwise - fp32, d_feature = 352, non-'idr' heads, VDN_SHADE_POINTS_FUSED=0 -
+    the module calls, which on fp32 are the exact-fp32 reference of the fused launch."""
+    if not (torch.is_tensor(points) and points.is_cuda and points.dim() == 2 and points.shape[1] == 3):
+        raise ValueError("shade_points needs a [P,3] CUDA tensor")
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    sn, cn = renderer.sdf_network, renderer.color_network
+    x_all = points.detach().float().contiguous()
+    P, dev = x_all.shape[0], x_all.device
+    sdf = torch.empty(P, dtype=torch.float32, device=dev)
+    grad = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    col = torch.empty(P, int(cn.conf.get("d_out", 3)), dtype=torch.float32, device=dev)
+    fused = fused_point_shading(renderer)
+    with torch.no_grad():
+        for s in range(0, P, batch):
+            x = x_all[s:s + batch]
+            n = x.shape[0]
+            if fused:
+                a = lib.VdnSdfArgs()
+                a.blob = sn._images().blobs["full"].data_ptr()
+                a.pts, a.n_per_ray, a.sdf_ld, a.P, a.scale = x.data_ptr(), 1, 1, n, float(sn.scale)
+                a.sdf, a.normals = sdf[s:s + n].data_ptr(), grad[s:s + n].data_ptr()
+                lib.call("vdn_shade_points_bf16", a, lib.ptr(cn._images().blobs["c2"]), int(cn.squeeze_out), lib.ptr(col[s:s + n]),
+                         lib.stream_handle())
+                continue
+            out = sn(x)
+            g = sn.gradient(x)[:, 0]
+            feat = out[:, 1:]
+            if cn.conf.get("d_feature") == 352:         # render(depth_before_color=True): cat([feature_vector, VDN output]), renderer.py:247-248
+                if renderer.depth_network is None:
+                    raise ValueError("a d_feature = 352 colour network needs the renderer's depth_network")
+                feat = torch.cat([feat, renderer.depth_network(x, g, view_from_gradient(g), feat)], dim=-1)
+            sdf[s:s + n], grad[s:s + n] = out[:, 0], g
+            col[s:s + n] = cn(x, g, view_from_gradient(g), feat)
+    return sdf, grad, col

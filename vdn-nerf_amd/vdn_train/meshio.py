@@ -1,0 +1,115 @@
+"""Triangle meshes on disk: the binary PLY Runner.validate_mesh leaves behind (dpt_runner.py:699-713 exports through the
+third-party `trimesh`; this module writes the same kind of file with numpy alone), with optional vertex normals and colours.
+
+Layout (`binary_little_endian 1.0`):
+  element vertex V:  float x y z, [float nx ny nz], [uchar red green blue]
+  element face F:    property list uchar int vertex_indices   (always 3 indices: 13 bytes per face)
+Both elements are written from numpy structured arrays; read_ply reads exactly this layout and raises on anything else."""
+import numpy as np
+
+_POS = ("x", "y", "z")
+_NRM = ("nx", "ny", "nz")
+_COL = ("red", "green", "blue")
+FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])          # packed: 13 bytes
+
+
+def vertex_dtype(normals=False, colors=False):
+    """The packed little-endian record of one vertex."""
+    fields = [(n, "<f4") for n in _POS]
+    if normals:
+        fields += [(n, "<f4") for n in _NRM]
+    if colors:
+        fields += [(n, "u1") for n in _COL]
+    return np.dtype(fields)
+
+
+def ply_header(n_vertices, n_faces, normals=False, colors=False):
+    """The header text of a file of write_ply, line for line."""
+    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n_vertices]
+    lines += ["property float %s" % n for n in _POS]
+    if normals:
+        lines += ["property float %s" % n for n in _NRM]
+    if colors:
+        lines += ["property uchar %s" % n for n in _COL]
+    lines += ["element face %d" % n_faces, "property list uchar int vertex_indices", "end_header"]
+    return "\n".join(lines) + "\n"
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """vertices [V,3] (stored as float32), triangles [F,3] integer, normals [V,3] float or None, colors [V,3] uint8 RGB or None."""
+    vertices = np.asarray(vertices).reshape(-1, 3)
+    triangles = np.asarray(triangles).reshape(-1, 3)
+    V, F = vertices.shape[0], triangles.shape[0]
+    if not np.issubdtype(triangles.dtype, np.integer) and F > 0:
+        raise ValueError("triangles must be integers, got %s" % triangles.dtype)
+    if F > 0 and (triangles.min() < 0 or triangles.max() >= V or triangles.max() > np.iinfo(np.int32).max):
+        raise ValueError("triangle indices must lie in [0, V)")
+    vert = np.empty(V, dtype=vertex_dtype(normals is not None, colors is not None))
+    for d, n in enumerate(_POS):
+        vert[n] = vertices[:, d]
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.shape != (V, 3):
+            raise ValueError("normals must be [V,3] = %s, got %s" % ((V, 3), normals.shape))
+        for d, n in enumerate(_NRM):
+            vert[n] = normals[:, d]
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != (V, 3) or colors.dtype != np.uint8:
+            raise ValueError("colors must be uint8 [V,3] = %s, got %s %s" % ((V, 3), colors.dtype, colors.shape))
+        for d, n in enumerate(_COL):
+            vert[n] = colors[:, d]
+    face = np.empty(F, dtype=FACE_DTYPE)
+    face["n"] = 3
+    face["v"] = triangles
+    with open(path, "wb") as f:
+        f.write(ply_header(V, F, normals is not None, colors is not None).encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
+    return path
+
+
+def read_ply(path):
+    """-> dict(vertices [V,3] float32, triangles [F,3] int32, normals [V,3] float32 | None, colors [V,3] uint8 | None) of a file
+    written by write_ply; ValueError on any other header (ASCII, big-endian, other properties) or a size that does not match."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError("%s: no PLY header" % path)
+    n_head = end + len(b"end_header\n")
+    try:
+        head = data[:n_head].decode("ascii")
+    except UnicodeDecodeError:
+        raise ValueError("%s: the PLY header is not ASCII text" % path)
+    lines = head.split("\n")
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError("%s: only `format binary_little_endian 1.0` files are read, got %r" % (path, lines[1:2]))
+    try:
+        kind, what, V = lines[2].split()
+        V = int(V)
+        assert (kind, what) == ("element", "vertex") and V >= 0
+    except (ValueError, AssertionError):
+        raise ValueError("%s: expected `element vertex V`, got %r" % (path, lines[2]))
+    F = None
+    for has_n in (False, True):
+        for has_c in (False, True):
+            face_line = 3 + 3 * (1 + has_n + has_c)
+            if len(lines) > face_line and lines[face_line].startswith("element face "):
+                try:
+                    F = int(lines[face_line].split()[2])
+                except (ValueError, IndexError):
+                    F = -1
+                if F >= 0 and head == ply_header(V, F, has_n, has_c):
+                    vd = vertex_dtype(has_n, has_c)
+                    if len(data) != n_head + V * vd.itemsize + F * FACE_DTYPE.itemsize:
+                        raise ValueError("%s: %d bytes, the header announces %d" %
+                                         (path, len(data), n_head + V * vd.itemsize + F * FACE_DTYPE.itemsize))
+                    vert = np.frombuffer(data, dtype=vd, count=V, offset=n_head)
+                    face = np.frombuffer(data, dtype=FACE_DTYPE, count=F, offset=n_head + V * vd.itemsize)
+                    if F > 0 and not (face["n"] == 3).all():
+                        raise ValueError("%s: a face that is not a triangle" % path)
+                    col = lambda names: np.stack([vert[n] for n in names], axis=1) if V > 0 else np.zeros((0, 3), vert[names[0]].dtype)
+                    return {"vertices": col(_POS), "triangles": face["v"].astype(np.int32).reshape(F, 3),
+                            "normals": col(_NRM) if has_n else None, "colors": col(_COL) if has_c else None}
+    raise ValueError("%s: the header is not one write_ply writes" % path)

@@ -2,7 +2,8 @@
 Runner.render_novel_image (589-616: interpolated view) and the arithmetic of Runner.val_img (dpt_runner.py:417-491) - rays of
 one camera in batches, colour image, L1 / PSNR against the ground truth, and the weight-argmax depth written back as
 `depth_from_sdf/sdf_<name>.npy` for the wavelet fine-tuning loop (dpt_runner.py:449-453). Everything stays on the device
-until the final image copy (the reference copies every batch to the host)."""
+until the final image copy (the reference copies every batch to the host). validate_mesh (dpt_runner.py:699-713) writes the
+extracted surface as a PLY file, with vertex normals and colours."""
 import os
 
 import numpy as np
@@ -146,3 +147,39 @@ def val_img(renderer, scene, rays_gen, idx, resolution_level=1, batch_size=512, 
             Image.fromarray(np.rint(weight_max_image(res["weight_depth"])[..., 0]).astype(np.uint8)).save(
                 os.path.join(out_dir, "weight_max", "weight_max_{}_{}.png".format(iter_step, idx)))
     return l1, psnr, res["gradient_error"], res["img_fine"]
+
+
+def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, threshold=0.0, world_space=False, scale_mat=None,
+                  vertex_colors=True, vertex_normals=True):
+    """Runner.validate_mesh (dpt_runner.py:699-713) without trimesh: the iso-surface of the SDF network inside the box, written
+    to `out_path` as a binary PLY (vdn_train/meshio.py) -> (out_path, V, F). `world_space` maps the vertices by
+    v * scale_mat[0,0] + scale_mat[:3,3] (708; a uniform scale and a translation: unit normals are unchanged). Beyond the
+    reference's bare mesh, each vertex carries its unit normal and its colour seen straight down that normal
+    (NeuSRenderer.extract_colored_geometry); with both flags off the file is the reference's and no network runs past the lattice."""
+    from vdn_train import meshio
+    normals = colors = None
+    if vertex_colors or vertex_normals:
+        vertices, triangles, normals, colors = renderer.extract_colored_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+        normals = normals if vertex_normals else None
+        colors = colors if vertex_colors else None
+    else:
+        vertices, triangles = renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+    if world_space:
+        if scale_mat is None:
+            raise ValueError("world_space=True needs the scene's scale_mat (SceneData.scale_mats_np[0])")
+        scale_mat = np.asarray(scale_mat)
+        vertices = vertices * scale_mat[0, 0] + scale_mat[:3, 3][None]
+    out_dir = os.path.dirname(out_path)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    meshio.write_ply(out_path, vertices, triangles, normals=normals, colors=colors)
+    return out_path, int(vertices.shape[0]), int(triangles.shape[0])
+
+
+def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, **kw):
+    """validate_mesh for a vdn_train.dataset.SceneData: its object bounding box and scale_mats_np[0], the runner's file name
+    meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711)."""
+    bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
+    bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
+    return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
+                         scale_mat=scene.scale_mats_np[0], **kw)
