@@ -8,6 +8,8 @@
 // array and the matrix pipe, not by the latency of one wave's chain. Halving the LDS traffic needs each activation fragment to feed
 // two MFMAs (4 waves x 2 tiles, weights for two tiles in registers: 288 registers double-buffered), i.e. one wave per SIMD again.
 // This fragment was part of csrc/k_sdf_fwd0_split.h (namespace vdn::sdf0s) behind vdn_sdf_upsample_bf16.
+// (LayerIO<L>, layer_mma<L> and load_weights<L> of that time are split::FwdIO<PG, L>, split::step_mma and split::load_weights of
+// csrc/k_sdf_split.h today.)
 // ---------------------------------------------------------------------------------------------------------------------------
 // The sampler's FIRST pass (renderer.py:369-370: the sdf at the 64 coarse samples of every ray) + first up-sampling round, the
 // same way (round 5): one workgroup = two rays = 128 points = FOUR 32-point blocks, 8 waves, wave w = output tile w of every

@@ -12,14 +12,16 @@
 //
 // Arithmetic is k_sdf_bwd.h's, operation for operation (zero-initialised accumulator, k-steps in order, the same epilogue
 // expressions, ex rounded to bf16 as the EX planes were): UB and AB are bit-identical to the two-kernel path.
+// The barrier, the register set and the MMA step are k_sdf_split.h's, shared with the two forward feature-split kernels.
 #pragma once
-#include "mlp_engine.h"
-#include "vdn_kernels.h"
+#include "k_sdf_split.h"
 
 namespace vdn {
 namespace sdfbs {
 
-constexpr int kWaves = 8;
+using split::kWaves;
+using split::WSet;                              // (its bias rows stay unused: no step of the backward has a bias)
+using split::lds_barrier;
 constexpr int kStride = 20480;                  // BF16::stride(9)
 constexpr int kPe = 0;                          // ub_0 = ub_4[PE part]: 4 k-steps x 1 KiB
 constexpr int kT8 = kPe + 4 * 1024;             // tile 8 of ab_8 (g_sdf / scale): 2 k-steps
@@ -40,19 +42,19 @@ constexpr StepDesc step_desc(int i) {
         {1, 7, 9, 8, 0}, {1, 6, 8, 8, 8}, {1, 5, 8, 8, 16}, {1, 4, 8, 8, 24}, {1, 3, 8, 7, 32}, {1, 2, 7, 8, 41}, {1, 1, 8, 8, 49}, {1, 0, 8, 8, 57}};
     return t[i];
 }
-// LDS offset of k-step s of step I's input; steps alternate between the two buffers (step I writes buffer I & 1)
+// LDS offset of k-step s of step I's input, and where its output goes; steps alternate between the two buffers (step I writes buffer I & 1)
 template <int I>
-constexpr int in_off(int s) {
-    constexpr StepDesc d = step_desc(I);
-    if (!d.fbar && d.l == 0) return kPe + s * 1024;
-    if (!d.fbar && d.l == 4 && s >= 14) return kPe + (s - 14) * 1024;
-    if (d.fbar && d.l == 7 && s >= 16) return kT8 + (s - 16) * 1024;
-    return ((I & 1) ? kBuf0 : kBuf1) + s * 1024;
-}
-template <int I>
-constexpr int out_base() { return (I & 1) ? kBuf1 : kBuf0; }
-
-struct WSet { bf16x8 w[18]; };
+struct StepIO {
+    static constexpr StepDesc d = step_desc(I);
+    static constexpr int ns = 2 * d.kt;
+    static constexpr int in_off(int s) {
+        if (!d.fbar && d.l == 0) return kPe + s * 1024;
+        if (!d.fbar && d.l == 4 && s >= 14) return kPe + (s - 14) * 1024;
+        if (d.fbar && d.l == 7 && s >= 16) return kT8 + (s - 16) * 1024;
+        return ((I & 1) ? kBuf0 : kBuf1) + s * 1024;
+    }
+    static constexpr int out_base = (I & 1) ? kBuf1 : kBuf0;
+};
 
 // Every global access of the kernel goes through a buffer descriptor (wave-uniform base in SGPRs, 32-bit per-lane byte offset,
 // wave-uniform soffset): plain 64-bit addressing cost ~60 VGPRs of precomputed plane addresses here, i.e. spills.
@@ -77,38 +79,6 @@ VDN_DEV void load_weights(WSet& W, rsrc_t blob_r, rsrc_t blob_f, int wave, unsig
         constexpr int s = decltype(s_c)::value;
         W.w[s] = __builtin_bit_cast(bf16x8, bload(d.fbar ? blob_f : blob_r, lane16, ch + s * 1024));
     });
-}
-
-VDN_DEV void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-template <int I>
-VDN_DEV f32x16 step_mma(const WSet& W, const char* my) {
-    constexpr StepDesc d = step_desc(I);
-    constexpr int NS = 2 * d.kt;
-    constexpr int PRE = NS < 4 ? NS : 4;            // B fragments read ahead of their MFMAs (6: no difference, 8 more registers)
-    f32x16 acc;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
-    bf16x8 x[NS];
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        x[s] = *reinterpret_cast<const bf16x8*>(my + in_off<I>(s));
-    });
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.w[s], x[s], acc, 0, 0, 0);
-    });
-    __builtin_amdgcn_sched_group_barrier(0x100, PRE, 0);
-    static_for<NS - PRE>([&](auto) VDN_INL {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    });
-    __builtin_amdgcn_sched_group_barrier(0x008, PRE, 0);
-    return acc;
 }
 
 VDN_DEV u32x4 pack8(const f32x16& v, int k) {
@@ -260,7 +230,8 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_bwd_split_kernel(SdfRbarAr
             }
             lds_barrier();
         }
-        const f32x16 acc = step_mma<I>(W, my);
+        // (4 B fragments read ahead of their MFMAs: 6 makes no difference here and costs 8 more registers)
+        const f32x16 acc = split::step_mma<StepIO<I>, 4, false>(W, smem, lane);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (I + 2 < 16) load_weights<I + 2>(W, RW, FW, wave, lane16);     // this set is free again
         // plane tiles of the NEXT step's epilogue
@@ -310,8 +281,8 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_bwd_split_kernel(SdfRbarAr
         const u32x4 p0 = pp[0], p1 = pp[1];
         if (wave < d.nt) {
             if constexpr (!(d.fbar == 0 && d.l == 7) && !(d.fbar == 1 && d.l == 0)) {      // ub_8 and ab_0 feed no further step
-                *reinterpret_cast<u32x4*>(my + out_base<I>() + (2 * wave) * 1024) = p0;
-                *reinterpret_cast<u32x4*>(my + out_base<I>() + (2 * wave + 1) * 1024) = p1;
+                *reinterpret_cast<u32x4*>(my + StepIO<I>::out_base + (2 * wave) * 1024) = p0;
+                *reinterpret_cast<u32x4*>(my + StepIO<I>::out_base + (2 * wave + 1) * 1024) = p1;
             }
             if constexpr (!d.fbar) put(RUB, d.l + 1 == 4 ? v288 : v256, ub_off(d.l + 1) + tile_off, p0, p1);
             else put(RAB, v256, ab_off(d.l) + tile_off, p0, p1);

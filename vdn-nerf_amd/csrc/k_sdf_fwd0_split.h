@@ -16,93 +16,26 @@
 //    into the accumulator, k-steps in order, softplus in scaled units, bf16 packing of the hidden activations, and the
 //    last layer's sdf row as ONE f32 fma chain over the unrounded activations of layer 7 in MODE 0's order (wave 0 runs
 //    it from LDS). The two kernels return bit-identical values (tests/test_gpu_parity.py).
+//  * the barrier, the register set, the MMA step, the LDS map and the weight load are k_sdf_split.h's, shared with
+//    k_sdf_fwd1_split.h and k_sdf_bwd_split.h; the prologue (point, encoding, W8 row, b0) and the sdf row are this kernel's own
+//    copies of what k_sdf_fwd1_split.h has too - as shared functions they changed the generated code (profiles/README.md).
 //
 // ROUNDS = true appends the rest of an up-sampling round (renderer.py:372-386) to the pass: with 16 new samples per ray a
 // workgroup's 32 points are exactly two rays, so waves 0 and 1 go on to merge their ray's new samples (z and the sdf values
 // just computed, handed over in LDS) into its sorted row and to draw the next round's samples from it - vdn_merge_upsample's
 // work (k_ray_rows.h: the same device functions, the same bits) without its launch and its trip through HBM.
 #pragma once
-#include "k_sdf_fwd2.h"
+#include "k_sdf_split.h"
 #include "k_ray_rows.h"
 
 namespace vdn {
 namespace sdf0s {
 
-constexpr int kWaves = 8;
-constexpr int kPeb = 0;                         // encoded input, 4 k-steps x 1 KiB  (layer 0's input; k-steps 14..17 of layer 4)
-constexpr int kBuf0 = 4 * 1024;                 // hidden activations, 16 k-steps x 1 KiB each, ping-pong
-constexpr int kBuf1 = kBuf0 + 16 * 1024;
-constexpr int kW8 = kBuf1 + 16 * 1024;          // row 0 of the last layer, 256 f32
-constexpr int kG = kW8 + 1024;                  // layer 7's activations in f32: [tile][q][lane] x 16 B
-constexpr int kLds = kG + 8 * 4 * 1024;
+using namespace split;                          // kWaves, the LDS map kPeb .. kG, FwdIO, tile_of_wave, WSet, load_weights, step_mma, lds_barrier
+constexpr int kLds = kFwdLds;
 
 using PG = sdf2::Prog<0>;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int L>
-struct LayerIO {
-    static constexpr int kt = PG::layer(L).kt, nt = PG::layer(L).nt, ns = 2 * kt;
-    // LDS byte offset of k-step s of layer L's input
-    static constexpr int in_off(int s) {
-        if (L == 0) return kPeb + s * 1024;
-        if (L == 4 && s >= 14) return kPeb + (s - 14) * 1024;
-        return ((L & 1) ? kBuf0 : kBuf1) + s * 1024;      // layer L-1 wrote buffer (L-1) & 1
-    }
-    static constexpr int out_base = (L & 1) ? kBuf1 : kBuf0;
-};
-
-struct WSet {
-    bf16x8 w[18];
-    f32x4 b[4];
-};
-
-// the chunk of (layer L, this wave's tile) -> registers
-template <int L>
-VDN_DEV void load_weights(WSet& W, const char* blob, int tile, int lane) {
-    constexpr int nt = PG::layer(L).nt, kt = PG::layer(L).kt;
-    const int t = tile < nt ? tile : nt - 1;            // layer 3 has 7 tiles: wave 7 recomputes tile 6 and drops it
-    const char* ch = blob + (long)(PG::first_chunk(L) + t) * sdf2::kStride;
-    const bf16x8* wa = reinterpret_cast<const bf16x8*>(ch) + lane;
-    static_for<2 * kt>([&](auto s_c) VDN_INL { W.w[decltype(s_c)::value] = wa[decltype(s_c)::value * 64]; });
-    const f32x4* bb = reinterpret_cast<const f32x4*>(ch + kt * 2048);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) W.b[q] = bb[2 * q + (lane >> 5)];
-}
-
-VDN_DEV void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-template <int L>
-VDN_DEV f32x16 layer_mma(const WSet& W, const char* smem, int lane) {
-    using IO = LayerIO<L>;
-    constexpr int NS = IO::ns;
-    constexpr int PRE = NS < 6 ? NS : 6;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        acc[4 * q + 0] = W.b[q][0]; acc[4 * q + 1] = W.b[q][1]; acc[4 * q + 2] = W.b[q][2]; acc[4 * q + 3] = W.b[q][3];
-    }
-    bf16x8 x[NS];
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        x[s] = *reinterpret_cast<const bf16x8*>(smem + IO::in_off(s) + lane * 16);
-    });
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.w[s], x[s], acc, 0, 0, 0);
-    });
-    // PRE fragment reads up front, then one read per MFMA (mlp_engine.h, BF16::mma)
-    __builtin_amdgcn_sched_group_barrier(0x100, PRE, 0);
-    static_for<NS - PRE>([&](auto) VDN_INL {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    });
-    __builtin_amdgcn_sched_group_barrier(0x008, PRE, 0);
-    return acc;
-}
 
 constexpr int kRows = kG;                       // ROUNDS: per-ray scratch rows (4 x kMaxT floats per ray) where layer 7's activations were
 constexpr int kNewSdf = kW8;                    // ROUNDS: the 32 new sdf values, where the last layer's row was
@@ -121,8 +54,8 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd0_split_kernel(SdfArgs 
     }
 
     WSet WA, WB;                                    // even / odd layers
-    load_weights<0>(WA, a.blob, wave, lane);
-    load_weights<1>(WB, a.blob, wave, lane);
+    load_weights<PG, 0>(WA, a.blob, tile_of_wave<PG, 0>(wave), lane);
+    load_weights<PG, 1>(WB, a.blob, tile_of_wave<PG, 1>(wave), lane);
     __builtin_amdgcn_sched_barrier(0);
 
     const long pd = wr.point;
@@ -161,10 +94,10 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd0_split_kernel(SdfArgs 
 
     auto hidden = [&](auto l_c, WSet& W) VDN_INL {
         constexpr int L = decltype(l_c)::value;
-        using IO = LayerIO<L>;
-        const f32x16 acc = layer_mma<L>(W, smem, lane);
+        using IO = FwdIO<PG, L>;
+        const f32x16 acc = step_mma<IO, 6, true>(W, smem, lane);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (L + 2 <= 7) load_weights<L + 2>(W, a.blob, wave, lane);      // this set is free again
+        if constexpr (L + 2 <= 7) load_weights<PG, L + 2>(W, a.blob, tile_of_wave<PG, L + 2>(wave), lane);      // this set is free again
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (L < 7) {
             u32x4 o[2];
@@ -188,6 +121,7 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd0_split_kernel(SdfArgs 
         }
         lds_barrier();
     };
+    // (written out: as a static_for the compiler schedules the prologue's point loads differently - profiles/README.md)
     hidden(std::integral_constant<int, 0>{}, WA);
     hidden(std::integral_constant<int, 1>{}, WB);
     hidden(std::integral_constant<int, 2>{}, WA);

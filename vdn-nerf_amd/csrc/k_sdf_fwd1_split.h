@@ -15,20 +15,17 @@
 //  * the same weight stream ("full"), the same arithmetic as MODE 1 operation for operation - accumulator from the bias (forward)
 //    or zero (sweep), k-steps in order, softplus / sigma in scaled units with the same 8-bit packing, the f32 sdf row as one fma
 //    chain in MODE 1's order (wave 0, from LDS), the encoding's adjoint by one wave in MODE 1's order - so every plane (H, V, PE,
-//    feature), sdf and normal comes out bit-identical to the large kernel's (tests/test_gpu_parity.py).
+//    feature), sdf and normal comes out bit-identical to the large kernel's (tests/test_gpu_parity.py);
+//  * the barrier, the register set, the MMA step, the LDS map and the weight load are k_sdf_split.h's, shared with k_sdf_fwd0_split.h
+//    and k_sdf_bwd_split.h; the prologue and the sdf row are copies of k_sdf_fwd0_split.h's (profiles/README.md: why they stayed).
 #pragma once
-#include "k_sdf_fwd2.h"
+#include "k_sdf_split.h"
 
 namespace vdn {
 namespace sdf1s {
 
-constexpr int kWaves = 8;
-constexpr int kPeb = 0;                         // encoded input, 4 k-steps x 1 KiB (layer 0's input; k-steps 14..17 of layer 4)
-constexpr int kBuf0 = 4 * 1024;                 // activations, 16 k-steps x 1 KiB each, ping-pong
-constexpr int kBuf1 = kBuf0 + 16 * 1024;
-constexpr int kW8 = kBuf1 + 16 * 1024;          // row 0 of the last layer, 256 f32
-constexpr int kG = kW8 + 1024;                  // layer 7's activations in f32: [tile][q][lane] x 16 B (the f32 sdf row)
-constexpr int kSig = kG + 8 * 4 * 1024;         // 255 sigma: [layer 8][wave 8][lane] x 16 B, wave-private
+using namespace split;                          // kWaves, the LDS map kPeb .. kG, FwdIO, tile_of_wave, WSet, load_weights, step_mma, lds_barrier
+constexpr int kSig = kFwdLds;                   // 255 sigma: [layer 8][wave 8][lane] x 16 B, wave-private
 constexpr int kLds = kSig + 8 * 8 * 1024;       // 133 KiB
 
 using PG = sdf2::Prog<1>;
@@ -37,88 +34,6 @@ using sdf2::kTail;
 using sdf2::kC1;
 using sdf2::kVSave;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int LI>
-struct StepIO {
-    static constexpr sdf2::LayerDesc L = PG::layer(LI);
-    static constexpr int kt = L.kt, nt = L.nt, ns = 2 * L.kt;
-    // LDS byte offset of k-step s of step LI's input
-    static constexpr int in_off(int s) {
-        if (LI == 0) return kPeb + s * 1024;
-        if (LI == 4 && s >= 14) return kPeb + (s - 14) * 1024;
-        return (((LI - 1) & 1) ? kBuf1 : kBuf0) + s * 1024;     // step LI-1 wrote buffer (LI-1) & 1
-    }
-    static constexpr int out_base = (LI & 1) ? kBuf1 : kBuf0;
-    static constexpr bool bias = L.kind <= sdf2::LAST;
-};
-
-struct WSet {
-    bf16x8 w[18];
-    f32x4 b[4];
-};
-
-// the chunk of (step LI, tile) -> registers
-template <int LI>
-VDN_DEV void load_weights(WSet& W, const char* blob, int tile, int lane) {
-    using IO = StepIO<LI>;
-    const char* ch = blob + (long)(PG::first_chunk(LI) + tile) * kStride;
-    const bf16x8* wa = reinterpret_cast<const bf16x8*>(ch) + lane;
-    static_for<IO::ns>([&](auto s_c) VDN_INL { W.w[decltype(s_c)::value] = wa[decltype(s_c)::value * 64]; });
-    if constexpr (IO::bias) {
-        const f32x4* bb = reinterpret_cast<const f32x4*>(ch + IO::kt * 2048);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) W.b[q] = bb[2 * q + (lane >> 5)];
-    }
-}
-// the tile wave w computes in step LI: its own where the step has it (layer 3 has 7: wave 7 recomputes tile 6 and drops it);
-// the two encoding tiles of the skip layer's sweep (7, then 8) and of W0^T (0, then 1) are wave 7's
-template <int LI>
-VDN_DEV int tile_of_wave(int wave) {
-    constexpr int nt = PG::layer(LI).nt;
-    if constexpr (PG::layer(LI).kind == sdf2::SWEEP_PE) return 0;
-    if constexpr (PG::layer(LI).kind == sdf2::SWEEP_SKIP) return wave;           // 0..7 (tile 8 follows on wave 7)
-    return wave < nt ? wave : nt - 1;
-}
-
-VDN_DEV void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-template <int LI>
-VDN_DEV f32x16 step_mma(const WSet& W, const char* smem, int lane) {
-    using IO = StepIO<LI>;
-    constexpr int NS = IO::ns;
-    constexpr int PRE = NS < 6 ? NS : 6;
-    f32x16 acc;
-    if constexpr (IO::bias) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            acc[4 * q + 0] = W.b[q][0]; acc[4 * q + 1] = W.b[q][1]; acc[4 * q + 2] = W.b[q][2]; acc[4 * q + 3] = W.b[q][3];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
-    }
-    bf16x8 x[NS];
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        x[s] = *reinterpret_cast<const bf16x8*>(smem + IO::in_off(s) + lane * 16);
-    });
-    static_for<NS>([&](auto s_c) VDN_INL {
-        constexpr int s = decltype(s_c)::value;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W.w[s], x[s], acc, 0, 0, 0);
-    });
-    // PRE fragment reads up front, then one read per MFMA (mlp_engine.h, BF16::mma)
-    __builtin_amdgcn_sched_group_barrier(0x100, PRE, 0);
-    static_for<NS - PRE>([&](auto) VDN_INL {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    });
-    __builtin_amdgcn_sched_group_barrier(0x008, PRE, 0);
-    return acc;
-}
 
 // rows [row0 + 32 b, row0 + 32 b + 32) of the work list, b = blockIdx.x - only when the list ends within max_rows behind row0
 // (then sdf2::sdf_fwd2_kernel leaves those rows alone: VdnSdfArgs.tail_row0 / tail_max_rows)
@@ -138,8 +53,8 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd1_split_kernel(SdfArgs 
     const long pd = a.active_idx != nullptr ? (long)a.active_idx[p] : p;    // dense point id
 
     WSet WA, WB;                                    // even / odd steps
-    load_weights<0>(WA, a.blob, tile_of_wave<0>(wave), lane);
-    load_weights<1>(WB, a.blob, tile_of_wave<1>(wave), lane);
+    load_weights<PG, 0>(WA, a.blob, tile_of_wave<PG, 0>(wave), lane);
+    load_weights<PG, 1>(WB, a.blob, tile_of_wave<PG, 1>(wave), lane);
     __builtin_amdgcn_sched_barrier(0);
 
     float xin[3];
@@ -212,26 +127,26 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd1_split_kernel(SdfArgs 
 
     auto step = [&](auto li_c, WSet& W) VDN_INL {
         constexpr int LI = decltype(li_c)::value;
-        using IO = StepIO<LI>;
+        using IO = FwdIO<PG, LI>;
         constexpr sdf2::LayerDesc L = IO::L;
         constexpr bool has_next2 = LI + 2 < PG::NL;
-        const int T = tile_of_wave<LI>(wave);
+        const int T = tile_of_wave<PG, LI>(wave);
         // the last step is wave 7's alone (both tiles of W0^T)
         if constexpr (L.kind == sdf2::SWEEP_PE) {
             if (wave != 7) return;
         }
-        f32x16 acc = step_mma<LI>(W, smem, lane);
+        f32x16 acc = step_mma<IO, 6, IO::bias>(W, smem, lane);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (L.kind == sdf2::SWEEP_SKIP || L.kind == sdf2::SWEEP_PE) {
             if (wave == 7) {                         // the second encoding tile with the same register set
                 UPE[0] = acc;
-                load_weights<LI>(W, a.blob, L.kind == sdf2::SWEEP_SKIP ? 8 : 1, lane);
+                load_weights<PG, LI>(W, a.blob, L.kind == sdf2::SWEEP_SKIP ? 8 : 1, lane);
                 __builtin_amdgcn_sched_barrier(0);
-                UPE[1] = step_mma<LI>(W, smem, lane);
+                UPE[1] = step_mma<IO, 6, IO::bias>(W, smem, lane);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if constexpr (has_next2) load_weights<LI + 2>(W, a.blob, tile_of_wave<LI + 2>(wave), lane);      // this set is free again
+        if constexpr (has_next2) load_weights<PG, LI + 2>(W, a.blob, tile_of_wave<PG, LI + 2>(wave), lane);      // this set is free again
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (L.kind == sdf2::HID) {
             u32x4 o[2], sq;
@@ -313,22 +228,7 @@ __global__ __launch_bounds__(kWaves * 64, 1) void sdf_fwd1_split_kernel(SdfArgs 
         }
         if constexpr (LI + 1 < PG::NL) lds_barrier();
     };
-    step(std::integral_constant<int, 0>{}, WA);
-    step(std::integral_constant<int, 1>{}, WB);
-    step(std::integral_constant<int, 2>{}, WA);
-    step(std::integral_constant<int, 3>{}, WB);
-    step(std::integral_constant<int, 4>{}, WA);
-    step(std::integral_constant<int, 5>{}, WB);
-    step(std::integral_constant<int, 6>{}, WA);
-    step(std::integral_constant<int, 7>{}, WB);
-    step(std::integral_constant<int, 8>{}, WA);
-    step(std::integral_constant<int, 9>{}, WB);
-    step(std::integral_constant<int, 10>{}, WA);
-    step(std::integral_constant<int, 11>{}, WB);
-    step(std::integral_constant<int, 12>{}, WA);
-    step(std::integral_constant<int, 13>{}, WB);
-    step(std::integral_constant<int, 14>{}, WA);
-    step(std::integral_constant<int, 15>{}, WB);
+    static_for<16>([&](auto li_c) VDN_INL { step(li_c, (decltype(li_c)::value & 1) ? WB : WA); });
     if (wave == 7) {
         step(std::integral_constant<int, 16>{}, WA);
         if (ok && h == 0) {
