@@ -6,6 +6,9 @@ Every table of a TrainEngine (GEMM, finalize, weight-norm; whole and per launch 
 pointers as (buffer name, byte offset), the buffers named by the engine's own workspace keys - and hashed. The digests in
 tests/golden/dw_plan_tables.json were made with this file's dump at the commit before the refactor:
     python tests/test_gpu_dw_plan_tables.py --dump OUT.json [--pkg DIR_OF_vdn_hip]
+
+The launch groups (TrainEngine.groups: one DwGroup each) are also checked against each other: they cut the tables of `all` into
+ranges of entries, nothing lost, nothing twice.
 """
 import hashlib
 import json
@@ -63,42 +66,96 @@ def _canon(tab, struct, stor):
 
 def engine_digests(eng):
     stor = _storages(eng)
-    tabs = {"dw": (eng.dw_table, "VdnDwDesc"), "fin": (eng.fin_table, "VdnDwFinalizeDesc"), "wn": (eng.wn_table, "VdnWeightNormBwdDesc")}
-    for g, v in eng.dw_groups.items():
-        tabs["dw." + g] = (v[0], "VdnDwDesc")
-    for g, v in eng.fin_groups.items():
-        tabs["fin." + g] = (v[0], "VdnDwFinalizeDesc")
-    for g, v in eng.wn_groups.items():
-        tabs["wn." + g] = (v[0], "VdnWeightNormBwdDesc")
+    structs = {"dw": "VdnDwDesc", "fin": "VdnDwFinalizeDesc", "wn": "VdnWeightNormBwdDesc"}
+    tabs = {}
+    for g, grp in eng.groups.items():
+        for kind, struct in structs.items():
+            if getattr(grp, "n_" + kind):
+                tabs[kind if g == "all" else kind + "." + g] = (getattr(grp, kind), struct)
     out = {}
     for k, (t, struct) in sorted(tabs.items()):
         body = json.dumps(_canon(t, struct, stor), sort_keys=True)
         out[k] = hashlib.sha256(body.encode()).hexdigest()
-    out["scalars"] = [eng.dw_total_wgs, eng.n_dw, eng.n_fin, eng.fin_max_M, eng.n_wn, eng.wn_max_rows, eng.fin_has_phase1,
-                      sorted((g, v[1], v[2]) for g, v in eng.dw_groups.items()),
-                      sorted((g, v[1], v[2], v[3]) for g, v in eng.fin_groups.items())]
+    a, parts = eng.groups["all"], {g: grp for g, grp in eng.groups.items() if g != "all"}
+    out["scalars"] = [a.wgs, a.n_dw, a.n_fin, a.max_m, a.n_wn, a.wn_rows, a.phase1,
+                      sorted((g, v.n_dw, v.wgs) for g, v in parts.items()),
+                      sorted((g, v.n_fin, v.max_m, v.phase1) for g, v in parts.items())]
     out["maps"] = hashlib.sha256(eng.maps.cpu().numpy().tobytes()).hexdigest()
     return out
 
 
-def all_digests(dev):
+def make_engines(dev):
     from vdn_train import synth, factory
     from vdn_hip.train import TrainEngine
     res = {}
     for name, kw in CONFIGS.items():
         st = synth.make_all_states(0, wdepth=kw["wdepth"], depth_before_color=kw.get("depth_before_color", False))
         rend = factory.build_renderer(device=dev, states=st, **kw)
-        res[name] = engine_digests(TrainEngine(rend, B, dev))
-    return json.loads(json.dumps(res))
+        res[name] = TrainEngine(rend, B, dev)
+    return res
+
+
+def all_digests(engines):
+    return json.loads(json.dumps({name: engine_digests(eng) for name, eng in engines.items()}))
+
+
+@pytest.fixture(scope="module")
+def engines():
+    import torch
+    return make_engines(torch.device("cuda:0"))
 
 
 @pytest.mark.gpu
-def test_ray_engine_tables_unchanged():
-    import torch
-    got = all_digests(torch.device("cuda:0"))
+def test_ray_engine_tables_unchanged(engines):
+    got = all_digests(engines)
     want = json.load(open(GOLDEN))
     bad = ["%s/%s" % (c, k) for c in want for k in want[c] if got[c].get(k) != want[c][k]]
     assert not bad, bad
+    extra = ["%s/%s" % (c, k) for c in want for k in got[c] if k not in want[c]]
+    assert not extra and sorted(got) == sorted(want), extra
+
+
+def _rows(grp, kind):
+    from vdn_hip import lib
+    struct = {"dw": "VdnDwDesc", "fin": "VdnDwFinalizeDesc", "wn": "VdnWeightNormBwdDesc"}[kind]
+    n = getattr(grp, "n_" + kind)
+    if not n:
+        return np.zeros(0, dtype=lib.struct_dtype(struct))
+    # (the first n descriptors: the SDF group's GEMM table is the device copy of the whole table, used with its own count)
+    return np.frombuffer(getattr(grp, kind).cpu().numpy().tobytes(), dtype=lib.struct_dtype(struct))[:n].copy()
+
+
+def _same(a, b):
+    return a.dtype == b.dtype and len(a) == len(b) and all(np.array_equal(a[f], b[f]) for f in a.dtype.names)
+
+
+@pytest.mark.gpu
+def test_launch_groups_partition_the_tables(engines):
+    """The launch groups of every engine cut the tables of `all` into ranges of entries: sdf + heads + nerf (and sdf + rest, rest =
+    heads + nerf) carry every GEMM descriptor once, in order, with workgroups numbered from each group's own zero; the finalize
+    rows of sdf + rest and the weight-norm rows of sdf + heads + nerf are those of `all`."""
+    for name, eng in engines.items():
+        G = eng.groups
+        assert set(G) == {"all", "sdf", "rest", "heads", "nerf"}, name
+
+        def chain(kind, *groups):
+            parts, wg0 = [], 0
+            for g in groups:
+                r = _rows(G[g], kind)
+                if kind == "dw":
+                    assert len(r) and int(r["wg_begin"][0]) == 0, (name, g)
+                    r["wg_begin"] += wg0             # back to the whole table's numbering
+                    wg0 += G[g].wgs
+                parts.append(r)
+            return np.concatenate(parts)
+        assert _same(chain("dw", "sdf", "heads", "nerf"), _rows(G["all"], "dw")), name
+        assert _same(chain("dw", "heads", "nerf"), _rows(G["rest"], "dw")), name
+        assert G["sdf"].wgs + G["heads"].wgs + G["nerf"].wgs == G["all"].wgs and G["heads"].wgs + G["nerf"].wgs == G["rest"].wgs, name
+        multiset = lambda rows: sorted(r.tobytes() for r in rows)
+        assert multiset(chain("fin", "sdf", "rest")) == multiset(_rows(G["all"], "fin")), name
+        assert multiset(chain("fin", "heads", "nerf")) == multiset(_rows(G["rest"], "fin")), name
+        assert _same(chain("wn", "sdf", "heads", "nerf"), _rows(G["all"], "wn")), name
+        assert _same(chain("wn", "heads", "nerf"), _rows(G["rest"], "wn")), name
 
 
 if __name__ == "__main__":
@@ -106,4 +163,4 @@ if __name__ == "__main__":
     pkg = args[args.index("--pkg") + 1] if "--pkg" in args else os.path.join(ROOT, "vdn-nerf_amd")
     sys.path[:0] = [pkg, ROOT]
     import torch
-    json.dump(all_digests(torch.device("cuda:0")), open(args[args.index("--dump") + 1], "w"), indent=1, sort_keys=True)
+    json.dump(all_digests(make_engines(torch.device("cuda:0"))), open(args[args.index("--dump") + 1], "w"), indent=1, sort_keys=True)

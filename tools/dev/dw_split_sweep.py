@@ -36,4 +36,4 @@ for r in range(R):
 for k in legs:
     eng = legs[k].trainer.engine
     print("sdf %5d nerf %5d heads %5d : wall %.1f us/step (min %.1f)  WGs sdf %d nerf %d heads %d" % (k[0], k[1], k[2], float(np.median(res[k])), min(res[k]),
-          eng.dw_groups["sdf"][2], eng.dw_groups["nerf"][2], eng.dw_groups["heads"][2]))
+          eng.groups["sdf"].wgs, eng.groups["nerf"].wgs, eng.groups["heads"].wgs))

@@ -107,8 +107,7 @@ def chain():
 
 
 def gemm():
-    tab, n, wgs = eng.dw_groups["nerf"]
-    lib.call("vdn_dw_gemm_bf16", lib.ptr(tab), n, wgs, lib.stream_handle())
+    eng.groups["nerf"].launch_gemm("_bf16", lib.stream_handle())
 
 
 print("\nthe shipped pair on this batch's work list (%d of %d background rows; the chain and the GEMM cover ALL 13 matrices of the" % (rows_bg, eng.Q))

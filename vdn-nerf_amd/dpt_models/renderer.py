@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from vdn_hip import lib
+from vdn_hip.train import PLAN_STATE          # engine attributes a replayed forward restores as its capture left them
 from dpt_models.fields import _require_gpu, _stream
 
 
@@ -185,9 +186,6 @@ class _RenderCoreFn(torch.autograd.Function):
 # environment switches that select launches inside the captured region: a plan is valid for one setting of them
 _PLAN_ENV = ("VDN_RENDER_FG_COMPACT", "VDN_FG_COMPACT", "VDN_BG_COMPACT", "VDN_FUSED_PREP", "VDN_TRAIN_COLOR_FUSED", "VDN_SDF_TAIL",
              "VDN_SDF_TAIL_ROW0", "VDN_SDF_TAIL_MAX", "VDN_BWD_SPLIT_DW", "VDN_SDF_BWD_SPLIT", "VDN_FUSE_ROUNDS", "VDN_FUSE_SDF_ROUNDS")
-# engine attributes forward() leaves for backward(): a replayed forward restores them as the capture left them
-_PLAN_STATE = ("_ctx", "_fg_compact", "_bg_compact", "_composite_bwd_done", "_bwd_train", "_pending", "_ray_grads", "_color_fused",
-               "_car_dev", "_fwd_rays", "_fused_keep")
 
 
 class _OneStreamCapture:
@@ -245,7 +243,7 @@ class _TrainPlan:
             z = z.contiguous()
             eng.forward(self.rays_o, self.rays_d, z, z_out, self.bgc, 0.0, skip_far=skip, rest_normals=skip, cos_anneal_dev=self.car)
         self.fwd, self.z, self.z_out = g, z, z_out
-        self.state = {k: eng.__dict__.get(k) for k in _PLAN_STATE}
+        self.state = {k: getattr(eng, k) for k in PLAN_STATE}
 
     def stage(self, rays_o, rays_d, near, far, background_rgb, car, t_rand, t_rand_out):
         src = [rays_o, rays_d, near, far]
@@ -265,14 +263,14 @@ class _TrainPlan:
         self.fwd.replay()
         eng.__dict__.update(self.state)
         eng._ctx = self.state["_ctx"][:3] + (self._car_host,) + self.state["_ctx"][4:]
-        eng.generation = getattr(eng, "generation", 0) + 1
+        eng.generation += 1
 
     def replay_backward(self, eng, g_color, g_feats, g_weights, g_eik):
         """-> False when this call has to run eagerly (the engine has not run a backward yet)."""
         pat = (g_color is not None, g_feats is not None, g_weights is not None, g_eik is not None)
         ent = self.bwd.get(pat)
         if ent is None or ent is False:
-            if not getattr(eng, "_bwd_warm", False) or ent is False:
+            if not eng._bwd_warm or ent is False:
                 return False
             B, dev = eng.B, eng.dev
             f = lambda *sh: torch.zeros(*sh, dtype=torch.float32, device=dev)

@@ -14,7 +14,7 @@ two calls whose P round to the same padded rows still get plans of their own. Wh
 layout (splits, workgroup offsets) and the device copy of the row / column maps. The device descriptor tables hold the
 addresses of that call's planes, slab, column sums and gradient buffers, which are all fresh allocations: the cached tables
 are reused only when every address (and the SDF scale) matches the previous call's - which torch's caching allocator usually
-arranges for a loop at a fixed P - and are rebuilt and uploaded (three small host-to-device copies) otherwise.
+arranges for a loop at a fixed P - and are rebuilt and uploaded (one train.DwGroup: three small host-to-device copies) otherwise.
 """
 from collections import OrderedDict
 
@@ -57,32 +57,23 @@ def _weight_grads(module, ent, net, precision, sdf_scale=1.0):
     if c is None:
         lay, maps, slab_elems, cs_elems, wgs = _train.dw_layout(ent, precision)
         c = cache[key] = dict(lay=lay, maps=torch.from_numpy(np.concatenate(maps)).to(dev), slab_elems=slab_elems,
-                              cs_elems=cs_elems, wgs=wgs, max_m=int(max(len(e["rmap"]) for e in ent)), ptrs=None)
+                              cs_elems=cs_elems, wgs=wgs, ptrs=None, group=None)
         while len(cache) > _CAP:
             cache.popitem(last=False)
     else:
         cache.move_to_end(key)
     slab = torch.empty(max(c["slab_elems"], 1), dtype=torch.float32, device=dev)
     colsum = torch.empty(max(c["cs_elems"], 1), dtype=torch.float32, device=dev)
-    wn, rows = _train.weightnorm_table([net])
+    nets = {ent[0]["net"]: net}
+    wn, _ = _train.weightnorm_table(nets)
     ptrs = (tuple(s[0].data_ptr() for e in ent for s in (e["A"], e["B"], e.get("A2"), e.get("B2")) if s is not None)
             + (slab.data_ptr(), colsum.data_ptr(), net.dweff.data_ptr(), next(iter(net.grads.values())).data_ptr(),
                wn.view(np.uint8).tobytes(), sdf_scale))
     if c["ptrs"] != ptrs:
-        dw, fin = _train.dw_tables(ent, c["lay"], {ent[0]["net"]: net}, precision, slab, colsum, c["maps"], [0] * len(ent), sdf_scale)
-        c["dw"] = torch.from_numpy(dw.view(np.uint8).copy()).to(dev)
-        c["fin"] = torch.from_numpy(fin.view(np.uint8).copy()).to(dev)
-        c["phase1"] = bool((fin["accumulate"] != 0).any())
-        c["wn"] = torch.from_numpy(wn.view(np.uint8).copy()).to(dev) if len(rows) else None
-        c["n_wn"], c["wn_rows"] = len(rows), max([r[1].shape[0] for r in rows] + [1])
+        dw, fin = _train.dw_tables(ent, c["lay"], nets, precision, slab, colsum, c["maps"], [0] * len(ent), sdf_scale)
+        c["group"] = _train.dw_group(dw, fin, wn, 0, len(ent), c["wgs"], dev, wn_idx=range(len(wn)))
         c["ptrs"] = ptrs
-    sfx = "_f32" if precision == "fp32" else "_bf16"
-    lib.call("vdn_dw_gemm" + sfx, lib.ptr(c["dw"]), len(ent), c["wgs"], st)
-    lib.call("vdn_dw_finalize", lib.ptr(c["fin"]), len(ent), c["max_m"], 0, st)
-    if c["phase1"]:
-        lib.call("vdn_dw_finalize", lib.ptr(c["fin"]), len(ent), c["max_m"], 1, st)
-    if c["n_wn"]:
-        lib.call("vdn_weightnorm_bwd", lib.ptr(c["wn"]), c["n_wn"], c["wn_rows"], st)
+    c["group"].launch("_f32" if precision == "fp32" else "_bf16", st)
     # (slab / colsum go back to the caching allocator in stream order: the launches above are their last readers)
 
 

@@ -246,17 +246,70 @@ def dw_tables(ent, lay, nets, precision, slab, colsum, maps, p_dev, sdf_scale):
 
 
 def weightnorm_table(nets):
-    """Weight-norm backward descriptors of every weight-normed matrix of `nets` (_Net objects, in order) -> (table, rows)."""
+    """Weight-norm backward descriptors of every weight-normed matrix of `nets` ({key: _Net}, in order) -> (table, the owning
+    net's key per row)."""
     rows = []
-    for net in nets:
+    for key, net in nets.items():
         for name, (g, v, b) in net.img.matrices.items():
             if g is not None:
-                rows.append((g, v, net.img.inv_norm[net.img.r_off[name]:], net.dweff_view(name), net.grads[id(g)], net.grads[id(v)]))
+                rows.append((key, g, v, net.img.inv_norm[net.img.r_off[name]:], net.dweff_view(name), net.grads[id(g)], net.grads[id(v)]))
     wn = np.zeros(len(rows), dtype=lib.struct_dtype("VdnWeightNormBwdDesc"))
-    for i, (g, v, inv, dwe, dg, dv) in enumerate(rows):
+    for i, (key, g, v, inv, dwe, dg, dv) in enumerate(rows):
         wn[i]["g"], wn[i]["v"], wn[i]["inv_norm"], wn[i]["dw_eff"] = g.data_ptr(), v.data_ptr(), inv.data_ptr(), dwe.data_ptr()
         wn[i]["dg"], wn[i]["dv"], wn[i]["rows"], wn[i]["cols"] = dg.data_ptr(), dv.data_ptr(), v.shape[0], v.shape[1]
-    return wn, rows
+    return wn, [r[0] for r in rows]
+
+
+class DwGroup:
+    """Device tables of the backward's tail for one launch group: the weight-gradient GEMM (`dw`: n_dw descriptors, wgs
+    workgroups), its finalize pass (`fin`: n_fin descriptors, max_m = the tallest target, phase1 = some descriptor accumulates)
+    and the weight-norm backward (`wn`: n_wn descriptors, wn_rows = the tallest matrix; None without one)."""
+
+    def __init__(self, dw, n_dw, wgs, fin, n_fin, max_m, phase1, wn, n_wn, wn_rows):
+        self.dw, self.n_dw, self.wgs = dw, n_dw, wgs
+        self.fin, self.n_fin, self.max_m, self.phase1 = fin, n_fin, max_m, phase1
+        self.wn, self.n_wn, self.wn_rows = wn, n_wn, wn_rows
+
+    def launch_gemm(self, sfx, stream):
+        lib.call("vdn_dw_gemm" + sfx, lib.ptr(self.dw), self.n_dw, self.wgs, stream)
+
+    def launch(self, sfx, stream, gemm_event=None, event_stream=None):
+        """GEMM, finalize (phase 0, phase 1 where flagged), weight-norm backward on `stream` (a raw handle); each is skipped where
+        the group has no row of its kind. gemm_event: recorded right behind the GEMM launch on `event_stream` (the torch stream
+        object of `stream`; default: torch's current stream, which must then be `stream`)."""
+        if self.n_dw:
+            self.launch_gemm(sfx, stream)
+        if gemm_event is not None:
+            gemm_event.record(event_stream if event_stream is not None else lib.current_stream())
+        for phase in range((2 if self.phase1 else 1) if self.n_fin else 0):
+            lib.call("vdn_dw_finalize", lib.ptr(self.fin), self.n_fin, self.max_m, phase, stream)
+        if self.n_wn:
+            lib.call("vdn_weightnorm_bwd", lib.ptr(self.wn), self.n_wn, self.wn_rows, stream)
+
+
+def dw_group(dw, fin, wn, lo, hi, total_wgs, dev, extra_fin=None, wn_idx=(), dw_dev=None):
+    """The DwGroup of entries [lo, hi) of the full numpy tables `dw` / `fin` (dw_tables) and rows `wn_idx` of `wn`
+    (weightnorm_table). The group's GEMM numbers its workgroups from its own zero: the copy's wg_begin is rebased (total_wgs: the
+    whole table's workgroups). dw_dev: a device copy of the whole GEMM table - a group that starts at entry 0 needs no
+    rebasing and uses it as it is, with its own count. extra_fin: finalize rows behind the entries' own."""
+    up = lambda a: torch.from_numpy(a.view(np.uint8).copy()).to(dev)
+    wg_lo, wg_hi = (int(dw[i]["wg_begin"]) if i < len(dw) else total_wgs for i in (lo, hi))
+    if lo == 0 and dw_dev is not None:
+        tab = dw_dev
+    else:
+        sub = dw[lo:hi].copy()
+        sub["wg_begin"] -= wg_lo
+        tab = up(sub)
+    f = fin[lo:hi] if extra_fin is None else np.concatenate([fin[lo:hi], extra_fin])
+    w = wn[list(wn_idx)]
+    return DwGroup(tab, hi - lo, wg_hi - wg_lo, up(f), len(f), int(fin[lo:hi]["M"].max()), bool((f["accumulate"] != 0).any()),
+                   up(w) if len(w) else None, len(w), int(w["rows"].max()) if len(w) else 1)
+
+
+# attributes of a TrainEngine that forward() leaves for backward(): a replayed graph plan (dpt_models/renderer.py: _TrainPlan)
+# restores them as its capture left them
+PLAN_STATE = ("_ctx", "_fg_compact", "_bg_compact", "_composite_bwd_done", "_bwd_train", "_pending", "_ray_grads", "_color_fused",
+              "_car_dev", "_fwd_rays", "_fused_keep")
 
 
 class TrainEngine:
@@ -287,9 +340,18 @@ class TrainEngine:
         self._ev_fork2 = torch.cuda.Event() if self._side2 is not None else None
         self._ev_join2 = torch.cuda.Event() if self._side2 is not None else None
         self._ev_heads = torch.cuda.Event() if use_side else None
-        self._pending = False
-        self._fused_keep = None
+        # ---- per-step state, at its idle value: what forward() leaves for backward() (PLAN_STATE above: a replayed graph plan
+        # restores exactly these) ...
+        self._ctx = self._fwd_rays = self._car_dev = self._bwd_train = self._fused_keep = None
+        self._pending = self._ray_grads = self._color_fused = self._composite_bwd_done = False
         self._fg_compact = self._bg_compact = False
+        # ... and the rest: `generation` counts forwards (render()'s autograd node checks its result is the latest), _bwd_warm = a
+        # backward ran eagerly, _bwd_args_keep holds the adjoints the compositor's argument block points at, join_hook (the
+        # Trainer) orders the caller's stream behind a deferred half of the backward, sdf_probe (bench.py) collects event pairs
+        # around the SDF launch; _out_strided / _clone_slots are made at the first outputs_clone() / param_grads()
+        self.generation = 0
+        self._bwd_warm = False
+        self._bwd_args_keep = self.join_hook = self.sdf_probe = self._out_strided = self._clone_slots = None
         precs = {m.precision for m in (renderer.nerf, renderer.sdf_network, renderer.color_network, renderer.depth_network) if m is not None}
         if len(precs) != 1:
             raise ValueError("all networks of a renderer must share one precision, got %s" % sorted(precs))
@@ -400,13 +462,7 @@ class TrainEngine:
 
         # ---- tables
         dev = self.dev
-        # Two launch groups: the SDF network's entries (the critical path into the next step: its sampler only needs the SDF
-        # weights) and the rest (colour / VDN heads, background network). `ent` lists the SDF entries first, so the group
-        # tables are a prefix and a suffix of the full table; the suffix copy numbers its workgroups from its own zero.
-        n_sdf = sum(1 for e in ent if e["net"] == "sdf")
-        assert all(e["net"] == "sdf" for e in ent[:n_sdf]) and all(e["net"] != "sdf" for e in ent[n_sdf:])
         lay, all_maps, slab_elems, cs_elems, wg = dw_layout(ent, prec)
-        self.dw_total_wgs = wg
         self.maps = torch.from_numpy(np.concatenate(all_maps)).to(dev)
         self.slab = torch.empty(max(slab_elems, 1), dtype=torch.float32, device=dev)
         self.colsum = torch.empty(max(cs_elems, 1), dtype=torch.float32, device=dev)
@@ -414,66 +470,35 @@ class TrainEngine:
         self.dw_list_kind = ["bg" if e["net"] == "nerf" else "fg" for e in ent]
         p_dev = [(w["bg_active"] if k == "bg" else w["fg_active"])[1].data_ptr() for k in self.dw_list_kind]
         dw, fin = dw_tables(ent, lay, self.nets, prec, self.slab, self.colsum, self.maps, p_dev, float(self.r.sdf_network.scale))
-        self.dw_table = torch.from_numpy(dw.view(np.uint8)).to(dev)
-        wg_sdf = int(dw[n_sdf]["wg_begin"]) if n_sdf < len(ent) else wg
-        rest = dw[n_sdf:].copy()
-        rest["wg_begin"] -= wg_sdf
-        self.dw_groups = {"sdf": (self.dw_table, n_sdf, wg_sdf)}
-        if len(rest):
-            self.dw_groups["rest"] = (torch.from_numpy(rest.view(np.uint8)).to(dev), len(rest), wg - wg_sdf)
-        # the rest group once more as its two halves (the Trainer's schedule launches them at different times: DESIGN.md 3d):
-        # "heads" = colour / VDN heads, "nerf" = the background network. `ent` lists sdf, heads, nerf in this order.
-        n_heads_end = n_sdf + sum(1 for e in ent if e["net"] not in ("sdf", "nerf"))
-        assert all(e["net"] == "nerf" for e in ent[n_heads_end:])
-        sub_ranges = {"heads": (n_sdf, n_heads_end), "nerf": (n_heads_end, len(ent))}
-        for gname, (lo, hi) in sub_ranges.items():
-            if hi > lo:
-                sub = dw[lo:hi].copy()
-                wg_lo = int(dw[lo]["wg_begin"])
-                wg_hi = int(dw[hi]["wg_begin"]) if hi < len(ent) else wg
-                sub["wg_begin"] -= wg_lo
-                self.dw_groups[gname] = (torch.from_numpy(sub.view(np.uint8)).to(dev), hi - lo, wg_hi - wg_lo)
+        wn, wn_net = weightnorm_table(self.nets)
         # one more finalize descriptor: d loss / d variance = sum over rays of the compositor's per-ray partials (a [B,1] "column
-        # sum" with one row): the reduction rides in the finalize launch instead of a launch of its own
+        # sum" with one row): the reduction rides in the finalize launch (of the SDF group) instead of a launch of its own
         vfin = np.zeros(1, dtype=fin.dtype)
         self._var_map = torch.zeros(1, dtype=torch.int32, device=dev)
         vfin[0]["colsum"], vfin[0]["rmap"] = w["d_var_partial"].data_ptr(), self._var_map.data_ptr()
         vfin[0]["btarget"], vfin[0]["bscale"] = self.grad_views[id(self.r.deviation_network.variance)].data_ptr(), 1.0
         vfin[0]["splits"], vfin[0]["M"], vfin[0]["N"] = self.B, 1, 0
-        fin_all = np.concatenate([fin, vfin])
-        self.fin_table = torch.from_numpy(fin_all.view(np.uint8)).to(dev)
-        self.fin_has_phase1 = bool((fin_all["accumulate"] != 0).any())
-        self.n_fin = len(fin_all)
-        self.n_dw = len(ent)
-        self.fin_max_M = int(max(len(e["rmap"]) for e in ent))
-        # per-group finalize tables (the variance's reduction rides with the SDF group)
-        fg = {"sdf": np.concatenate([fin[:n_sdf], vfin]), "rest": fin[n_sdf:]}
-        mm = {"sdf": ent[:n_sdf], "rest": ent[n_sdf:]}
-        for gname, (lo, hi) in sub_ranges.items():
-            fg[gname], mm[gname] = fin[lo:hi], ent[lo:hi]
-        self.fin_groups = {k: (torch.from_numpy(v.view(np.uint8).copy()).to(dev), len(v), int(max(len(e["rmap"]) for e in mm[k])),
-                               bool((v["accumulate"] != 0).any())) for k, v in fg.items() if len(v) and len(mm[k])}
-        # weight-norm backward table
-        row_group = []
-        for key, net in self.nets.items():          # "sdf" first (dict order of self.nets)
-            for name, (g, v, b) in net.img.matrices.items():
-                if g is not None:
-                    row_group.append(("sdf",) if key == "sdf" else ("rest", "nerf" if key == "nerf" else "heads"))
-        wn, rows = weightnorm_table(self.nets.values())
-        self.wn_table = torch.from_numpy(wn.view(np.uint8).copy() if len(rows) else np.zeros(8, np.uint8)).to(dev)
-        self.n_wn = len(rows)
-        self.wn_max_rows = max([r[1].shape[0] for r in rows] + [1])
-        self.wn_groups = {}
-        for k in ("sdf", "rest", "heads", "nerf"):
-            idx = [i for i, gk in enumerate(row_group) if k in gk]
-            if idx:
-                self.wn_groups[k] = (torch.from_numpy(wn[idx].view(np.uint8).copy()).to(dev), len(idx), max(rows[i][1].shape[0] for i in idx))
+        # Launch groups: "all"; the SDF network's entries (the critical path into the next step: its sampler only
+        # needs the SDF weights) and the "rest"; the rest once more as its two halves, which the Trainer's schedule launches at
+        # different times: "heads" = colour / VDN heads, "nerf" = the background network. `ent` lists sdf, heads, nerf in this
+        # order, so every group is a range of entries (tests/test_gpu_dw_plan_tables.py: the groups partition the tables).
+        n_sdf = sum(1 for e in ent if e["net"] == "sdf")
+        n_heads_end = n_sdf + sum(1 for e in ent if e["net"] not in ("sdf", "nerf"))
+        ranges = {"all": (0, len(ent)), "sdf": (0, n_sdf), "rest": (n_sdf, len(ent)), "heads": (n_sdf, n_heads_end),
+                  "nerf": (n_heads_end, len(ent))}
+        dw_dev = torch.from_numpy(dw.view(np.uint8)).to(dev)
+        self.groups = {}
+        for g, (lo, hi) in ranges.items():
+            if hi > lo:
+                own = {e["net"] for e in ent[lo:hi]}         # a weight-normed matrix goes with its network's entries
+                self.groups[g] = dw_group(dw, fin, wn, lo, hi, wg, dev, vfin if lo == 0 else None,
+                                          [i for i, k in enumerate(wn_net) if k in own], dw_dev)
         self._param_ptrs = self._ptr_key()
 
     @property
     def grad_flat(self):
         """The flat gradient buffer (dpt_runner.py:121-130 parameter order), complete on torch's current stream."""
-        if getattr(self, "join_hook", None) is not None:     # the Trainer's deferred half of the backward (side stream)
+        if self.join_hook is not None:     # the Trainer's deferred half of the backward (side stream)
             self.join_hook()
         return self._grad_flat
 
@@ -677,7 +702,7 @@ class TrainEngine:
             self._composite_bwd_done = True
         else:
             lib.call("vdn_alpha_composite_fwd", c, st)
-        self.generation = getattr(self, "generation", 0) + 1
+        self.generation += 1
         return w
 
     def _fg(self, args):
@@ -709,7 +734,19 @@ class TrainEngine:
         """The tail split of the fused SDF forward (csrc/k_sdf_fwd1_split.h): on where there is no side stream, off with one."""
         tail_default = "1" if self._side is None else "0"
         return (self.precision == "bf16" and self._fg_compact and os.environ.get("VDN_SDF_TAIL", tail_default) != "0"
-                and not getattr(self, "_ray_grads", False))
+                and not self._ray_grads)
+
+    def _sdf_args(self, rays_o, rays_d, feat):
+        """Argument block of the fused SDF kernel on the section mid-points in the workspace, its feature plane going to `feat`;
+        the caller adds the S plane, the saves and the work list."""
+        w, N, img = self.w, self.N, self.nets["sdf"].img
+        s = lib.VdnSdfArgs()
+        s.blob = img.blobs["full"].data_ptr()
+        s.rays_o, s.rays_d, s.z, s.n_per_ray, s.z_ld, s.sdf_ld = rays_o.data_ptr(), rays_d.data_ptr(), w["mid_z"].data_ptr(), N, N, N
+        s.P, s.scale = self.P, float(self.r.sdf_network.scale)
+        s.sdf, s.feat, s.normals = w["sdf"].data_ptr(), feat.data_ptr(), w["normals"].data_ptr()
+        s.w8row = img.weff_view("lin8").data_ptr()
+        return s
 
     def _sdf_rest(self, rays_o, rays_d, stream):
         """`sdf` and `normals` of the inside samples the foreground work list skips: the list's complement (vdn_foreground_active,
@@ -724,13 +761,7 @@ class TrainEngine:
         fa.complement = 1
         fa.active_idx, fa.n_active, fa.ray_counts = (t.data_ptr() for t in w["fg_rest"])
         lib.call("vdn_foreground_active", fa, stream)
-        s = lib.VdnSdfArgs()
-        img = self.nets["sdf"].img
-        s.blob = img.blobs["full"].data_ptr()
-        s.rays_o, s.rays_d, s.z, s.n_per_ray, s.z_ld, s.sdf_ld = rays_o.data_ptr(), rays_d.data_ptr(), w["mid_z"].data_ptr(), N, N, N
-        s.P, s.scale = self.P, float(self.r.sdf_network.scale)
-        s.sdf, s.feat, s.normals = w["sdf"].data_ptr(), w["d_featvec"].data_ptr(), w["normals"].data_ptr()
-        s.w8row = img.weff_view("lin8").data_ptr()
+        s = self._sdf_args(rays_o, rays_d, w["d_featvec"])
         if "S" in w:              # (the fp32 kernel keeps softplus' in a plane between its forward pass and its sweep)
             if "S_rest" not in w:
                 w["S_rest"] = torch.empty_like(w["S"])
@@ -741,18 +772,12 @@ class TrainEngine:
     def _sdf_forward(self, rays_o, rays_d):
         """The fused SDF kernel (PE -> 9 layers -> sdf / feature + gradient sweep) with the training-mode saves, on the
         section mid-points currently in the workspace. Separate so that bench.py can time exactly this launch."""
-        r, w, N = self.r, self.w, self.N
-        s = lib.VdnSdfArgs()
-        img = self.nets["sdf"].img
-        s.blob = img.blobs["full"].data_ptr()
-        s.rays_o, s.rays_d, s.z, s.n_per_ray, s.z_ld, s.sdf_ld = rays_o.data_ptr(), rays_d.data_ptr(), w["mid_z"].data_ptr(), N, N, N
-        s.P, s.scale = self.P, float(r.sdf_network.scale)
-        s.sdf, s.feat, s.normals = w["sdf"].data_ptr(), w["feat"].data_ptr(), w["normals"].data_ptr()
+        r, w = self.r, self.w
+        s = self._sdf_args(rays_o, rays_d, w["feat"])
         if "S" in w:
             s.S = w["S"].data_ptr()
-        s.w8row = img.weff_view("lin8").data_ptr()
         s.H, s.V, s.PE = w["H"].data_ptr(), w["V"].data_ptr(), w["PE"].data_ptr()
-        if getattr(self, "_ray_grads", False):
+        if self._ray_grads:
             s.U_pe = w["U_pe"].data_ptr()
         # The tail of the work list (bf16): the 128-row kernel runs whole rounds of one workgroup per CU, so ~37 K rows cost two
         # rounds; when the list ends within VDN_SDF_TAIL_MAX rows behind the last full round, those rows go to the 32-row
@@ -762,7 +787,7 @@ class TrainEngine:
         # 80): it shortens the launch when the second round's CUs would idle (-37 us per step on one stream), but on the default
         # two-stream schedule those CUs run the background network and the extra CU time costs +7 .. +20 us (same-box A/B).
         tail = self._tail_wanted()
-        fused = getattr(self, "_color_fused", False) and not tail
+        fused = self._color_fused and not tail
         if tail:
             row0 = int(os.environ.get("VDN_SDF_TAIL_ROW0", str(128 * torch.cuda.get_device_properties(self.dev).multi_processor_count)))
             tail = self.P > row0
@@ -778,7 +803,7 @@ class TrainEngine:
             lib.call("vdn_sdf_mlp_fwd" + self.sfx, 1, self._fg(s), _stream())
             if tail:
                 lib.call("vdn_sdf_fwd_tail_bf16", s, _stream())
-        probe = getattr(self, "sdf_probe", None)
+        probe = self.sdf_probe
         if probe is None:
             launch()
             return
@@ -793,7 +818,7 @@ class TrainEngine:
     def _dw_rows(self):
         """Rows each weight-gradient entry contracts over in the current step (the work lists of the last forward)."""
         n = {"bg": int(self.w["bg_active"][1].item()) if "bg_active" in self.w else 0, "fg": int(self.w["fg_active"][1].item())}
-        tab = np.frombuffer(self.dw_table.cpu().numpy().tobytes(), dtype=lib.struct_dtype("VdnDwDesc"))
+        tab = np.frombuffer(self.groups["all"].dw.cpu().numpy().tobytes(), dtype=lib.struct_dtype("VdnDwDesc"))
         return tab, [min(int(d["P"]), n[k]) for d, k in zip(tab, self.dw_list_kind)]
 
     def dw_bytes(self):
@@ -812,22 +837,23 @@ class TrainEngine:
         return sum(2.0 * (2 if d["A2"] else 1) * r * int(d["m_tiles"]) * 32 * int(d["n_tiles"]) * 32 for d, r in zip(tab, rows))
 
     def _launch_dw(self):
-        lib.call("vdn_dw_gemm" + self.sfx, lib.ptr(self.dw_table), self.n_dw, self.dw_total_wgs, _stream())
+        self.groups["all"].launch_gemm(self.sfx, _stream())
 
     def _launch_dw_groups(self):
         """The weight-gradient GEMM as the Trainer's step launches it: one launch per group (bench.py times this)."""
         for group in ("sdf", "rest"):
-            if group in self.dw_groups:
-                tab, n, wgs = self.dw_groups[group]
-                lib.call("vdn_dw_gemm" + self.sfx, lib.ptr(tab), n, wgs, _stream())
+            if group in self.groups:
+                self.groups[group].launch_gemm(self.sfx, _stream())
 
     def side_weight_grads(self, group, after=None, gemm_event=None):
-        """One half of the rest group on the side stream (backward(defer_rest=True) came first): "nerf" = the background
+        """The rest group, or one half of it, on the side stream (backward(defer_rest=True) came first): "nerf" = the background
         network's weight gradients, behind its backward on that stream; "heads" = the colour / VDN heads', behind the heads'
-        backward on the caller's stream. `after`: one more event to wait for. gemm_event: recorded on the side stream right
-        behind the GEMM launch - the last reader of the forward's workspaces on that stream (saved planes, deltas, the device-side
-        row counts of the work lists): the next step's preparation, which rewrites them, waits for it. Returns the torch
-        stream (None without a side stream: the work was issued on the caller's)."""
+        backward on the caller's stream; "rest" = both in one launch. `after`: one more event to wait for (the Trainer passes
+        the SDF group's GEMM with "rest", so that the two HBM-bound GEMMs do not share the chip and this one runs beside the next
+        step's sampler instead). gemm_event: recorded on the side stream right behind the GEMM launch - the last reader of the
+        forward's workspaces on that stream (saved planes, deltas, the device-side row counts of the work lists): the next
+        step's preparation, which rewrites them, waits for it. Returns the torch stream (None without a side stream: the work
+        was issued on the caller's): the caller orders its next use of those gradients / planes behind it."""
         if self._side is None:
             self.weight_grads(group, _stream())
             return None
@@ -839,41 +865,11 @@ class TrainEngine:
         self._pending = False            # joined by the caller's own event, not by _join()
         return self._side
 
-    def rest_weight_grads(self, after=None, gemm_event=None):
-        """Second half of backward(defer_rest=True): the colour / VDN / background networks' weight gradients, issued on the side
-        stream behind the background network's backward (or, without a side stream, on the caller's stream). `after`: an event
-        the work should also wait for (the Trainer passes the SDF group's GEMM, so that the two HBM-bound GEMMs do not share the
-        chip and this one runs beside the next step's sampler instead). Returns the torch stream it was issued on (None = the
-        caller's): the caller orders its next use of those gradients / planes behind it."""
-        if self._side is None:
-            self.weight_grads("rest", _stream())
-            return None
-        if after is not None:           # (recorded on the caller's stream behind the heads' backward: covers it)
-            self._side.wait_event(after)
-        else:
-            self._side.wait_event(self._ev_heads)
-        self.weight_grads("rest", self._side.cuda_stream, gemm_event, event_stream=self._side)
-        self._pending = False            # joined by the caller's own event, not by _join()
-        return self._side
-
     def weight_grads(self, group, stream, gemm_event=None, event_stream=None):
-        """Weight-gradient GEMM + finalize + weight-norm backward of one launch group ("sdf": the SDF network and the variance;
-        "rest": colour / VDN heads and the background network) on `stream` (a raw handle). The two groups touch disjoint
-        slabs and disjoint ranges of the flat gradient buffer. gemm_event: recorded right behind the GEMM launch on
-        `event_stream` (the torch stream object of `stream`; default: torch's current stream, which must then be `stream`)."""
-        if group in self.dw_groups:
-            tab, n, wgs = self.dw_groups[group]
-            lib.call("vdn_dw_gemm" + self.sfx, lib.ptr(tab), n, wgs, stream)
-        if gemm_event is not None:
-            gemm_event.record(event_stream if event_stream is not None else lib.current_stream())
-        if group in self.fin_groups:
-            tab, n, max_m, phase1 = self.fin_groups[group]
-            lib.call("vdn_dw_finalize", lib.ptr(tab), n, max_m, 0, stream)
-            if phase1:
-                lib.call("vdn_dw_finalize", lib.ptr(tab), n, max_m, 1, stream)
-        if group in self.wn_groups:
-            tab, n, max_rows = self.wn_groups[group]
-            lib.call("vdn_weightnorm_bwd", lib.ptr(tab), n, max_rows, stream)
+        """The tail of one launch group (DwGroup.launch) on `stream` (a raw handle): "sdf" = the SDF network and the variance,
+        "rest" = colour / VDN heads ("heads") and the background network ("nerf"). Groups touch disjoint slabs and disjoint
+        ranges of the flat gradient buffer."""
+        self.groups[group].launch(self.sfx, stream, gemm_event, event_stream)
 
     def _composite_common(self, c, rays_o, rays_d, background_rgb, cos_anneal_ratio):
         w, r = self.w, self.r
@@ -889,7 +885,7 @@ class TrainEngine:
         if background_rgb is not None:
             c.background_rgb = background_rgb.data_ptr()
         c.cos_anneal_ratio = float(cos_anneal_ratio)
-        if getattr(self, "_car_dev", None) is not None:
+        if self._car_dev is not None:
             c.cos_anneal_dev = self._car_dev.data_ptr()
         c.B, c.N, c.T = self.B, self.N, self.T
         return c
@@ -918,7 +914,7 @@ class TrainEngine:
                 if g_feat is None:
                     w["d_bg_feat"].zero_()
         c.d_var_partial = w["d_var_partial"].data_ptr()       # summed into the variance's gradient by the finalize launch (_build_dw_plan)
-        if getattr(self, "_ray_grads", False):
+        if self._ray_grads:
             c.d_dists, c.d_dir_cos = w["d_dists"].data_ptr(), w["d_dir_cos"].data_ptr()
             if r.n_outside > 0:
                 c.d_bg_dists = w["d_bg_dists"].data_ptr()
@@ -931,12 +927,12 @@ class TrainEngine:
         """Upstream grads (any may be None) -> list of parameter grads (clones) per network. g_cdf [B,N] / g_gradients
         [B,N,3]: adjoints of the `cdf_fine` / `gradients` outputs (the reference returns them attached, renderer.py:426-439).
         defer_rest (the Trainer's hot loop): only the SDF network's and the variance's gradients are complete on return (on the
-        caller's stream); the caller finishes the others with rest_weight_grads() - on the side stream, behind the background
+        caller's stream); the caller finishes the others with side_weight_grads() - on the side stream, behind the background
         network's backward - so that they overlap whatever follows on the main stream.
         Every event recorded on the caller's stream is a marker packet in front of the next kernel of the step's critical chain
         (3 - 4 us each: tools/dev/event_probe.py), so the Trainer passes what it already has: fork_event = an event it recorded
         on the current stream since the forward's last launch (the side stream waits for that one instead of a new one);
-        heads_event=False when it will hand side_weight_grads / rest_weight_grads an `after` event recorded later on this stream
+        heads_event=False when it will hand side_weight_grads an `after` event recorded later on this stream
         (which then also covers the heads' backward)."""
         r, w, st = self.r, self.w, _stream()
         self._bwd_warm = True           # (render()'s graph plans capture a backward only after one ran eagerly: lazy one-time set-up is done)
@@ -946,10 +942,10 @@ class TrainEngine:
         if (g_cdf is not None or g_gradients is not None) and self._fg_compact:
             raise ValueError("adjoints of cdf_fine / gradients need every inside sample evaluated (skip_far=False)")
         use_vdn = self.wdepth and g_feat is not None
-        rg = getattr(self, "_ray_grads", False)
-        if getattr(self, "_composite_bwd_done", False):
+        rg = self._ray_grads
+        if self._composite_bwd_done:
             self._composite_bwd_done = False          # (forward(fuse_loss=...) ran the compositor's adjoint already)
-        elif getattr(self, "_bwd_train", None) is not None:
+        elif self._bwd_train is not None:
             fl, self._bwd_train = self._bwd_train, None
             c = self._composite_bwd_args(None, g_feat, None, None, None)
             lib.call("vdn_composite_bwd_train", c, lib.ptr(w["color"]), lib.ptr(fl["true_rgb"]), lib.ptr(fl["g_color"]),
@@ -987,7 +983,7 @@ class TrainEngine:
             # stream, beside the heads' and the SDF network's backward on the caller's, instead of waiting in one GEMM launch for
             # all groups behind everything else (the Trainer's schedule, DESIGN.md 3d, minus its deferral past the step's end)
             split_dw = (not defer_rest and self._side is not None and not rg and os.environ.get("VDN_BWD_SPLIT_DW", "1") != "0"
-                        and all(k in self.dw_groups for k in ("sdf", "heads", "nerf")))
+                        and all(k in self.groups for k in ("sdf", "heads", "nerf")))
             if split_dw:
                 self.weight_grads("nerf", self._side.cuda_stream)
             self._side_done()
@@ -1060,12 +1056,7 @@ class TrainEngine:
             self._join()
         else:
             self._join()
-            self._launch_dw()
-            lib.call("vdn_dw_finalize", lib.ptr(self.fin_table), self.n_fin, self.fin_max_M, 0, st)
-            if self.fin_has_phase1:
-                lib.call("vdn_dw_finalize", lib.ptr(self.fin_table), self.n_fin, self.fin_max_M, 1, st)
-            if self.n_wn:
-                lib.call("vdn_weightnorm_bwd", lib.ptr(self.wn_table), self.n_wn, self.wn_max_rows, st)
+            self.groups["all"].launch(self.sfx, st)
         if rg:
             ra = lib.VdnRayAdjointArgs()
             ra.rays_d, ra.mid_z = rays_d.data_ptr(), w["mid_z"].data_ptr()
@@ -1082,7 +1073,7 @@ class TrainEngine:
     def outputs_clone(self):
         """A copy of everything the latest forward hands to the caller (one device copy) -> {name: tensor}."""
         a = self._out_arena.clone()
-        if self.__dict__.get("_out_strided") is None:
+        if self._out_strided is None:
             self._out_strided = [(k, tuple(sh), tuple(torch.empty(sh, device="meta").stride()), o) for k, (o, sh) in self._out_slots.items()]
         # Tensor.set_ on the copy's storage, not as_strided / detach: each output is then a tensor of its own - not a view (autograd
         # refuses in-place ops on the views a multi-output node returns: ADVICE round 5) and with its OWN version counter (views and
@@ -1093,7 +1084,7 @@ class TrainEngine:
 
     def param_grads(self, clone=True):
         """Per-parameter gradients in renderer._all_parameters() order."""
-        if getattr(self, "join_hook", None) is not None:     # the Trainer's deferred half of the backward (side stream)
+        if self.join_hook is not None:     # the Trainer's deferred half of the backward (side stream)
             self.join_hook()
         if not clone:
             return [self.grad_views[id(p)] for p in self.params]
@@ -1103,7 +1094,7 @@ class TrainEngine:
         # backward alone - the engine's own buffer is reused by the next step. Every view starts on a 256-byte boundary:
         # torch.optim's multi-tensor kernels fall back to scalar loads on lists with a misaligned member (packed offsets
         # cost the runner's Adam step + 60 us).
-        if self.__dict__.get("_clone_slots") is None:
+        if self._clone_slots is None:
             slots, off = [], 0
             for p in self.params:
                 slots.append((tuple(p.shape), tuple(self.grad_views[id(p)].stride()), off))

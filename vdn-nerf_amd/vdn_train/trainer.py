@@ -523,8 +523,8 @@ class Trainer:
         after_sdf = self._eikonal_begin if (dp and fl is None) else None
         w = eng.forward(rays_o, rays_d, z.contiguous(), z_out, self.bg, self.cos_anneal_ratio(), skip_far=True,
                         pending_merge=r._pending_merge, after_sdf=after_sdf, fuse_loss=fl, before_heads=self.join if late_join else None)
-        fused_wd = getattr(eng, "_bwd_train", None) is not None
-        fused = bool(getattr(eng, "_composite_bwd_done", False)) or fused_wd
+        fused_wd = eng._bwd_train is not None
+        fused = eng._composite_bwd_done or fused_wd
         if dp and fl is not None and not fused:
             raise RuntimeError("the engine did not take the fused compositor path the data-parallel step was set up for")
         if dp and not fused:
@@ -612,7 +612,7 @@ class Trainer:
             images.refresh_together([eng.nets["sdf"].img], stream, self._img_cache.setdefault("sdf", {}))
 
         grad = eng._grad_flat
-        split = self.overlap and os.environ.get("VDN_SPLIT_REST", "1") != "0" and "nerf" in eng.dw_groups and "heads" in eng.dw_groups
+        split = self.overlap and os.environ.get("VDN_SPLIT_REST", "1") != "0" and "nerf" in eng.groups and "heads" in eng.groups
         # (events on the critical chain are marker packets, 3 - 4 us each: the side stream's fork reuses _ev_comp - nothing was
         # launched on this stream since; not with the VDN head, where the compositor's adjoint is still to come in backward() - the SDF GEMM's event is only recorded for the schedule that waits for it, and the heads'
         # event is covered by the `after` events below, which are recorded later on this stream)
@@ -648,7 +648,7 @@ class Trainer:
                 eng.weight_grads("heads", st)
                 update_rest(st, "heads")
             else:
-                side = eng.rest_weight_grads(after=self._ev_gemm, gemm_event=self._ev_ws) if self.overlap else None
+                side = eng.side_weight_grads("rest", after=self._ev_gemm, gemm_event=self._ev_ws) if self.overlap else None
                 self._ws_pending = side is not None
                 if side is None:
                     if not self.overlap:
