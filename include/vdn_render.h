@@ -812,6 +812,62 @@ typedef struct {
 int vdn_mesh_mc_count(const VdnMeshMcArgs* args_host, void* stream);
 int vdn_mesh_mc_emit(const VdnMeshMcArgs* args_host, void* stream);
 
+/* ---- mesh evaluation: area-weighted surface samples of a triangle mesh (csrc/mesh_eval.hip; vdn_hip/mesh.py: sample_surface) ---
+ * The sample set an accuracy / completeness / Chamfer figure against a scanned cloud is taken over (vdn_train/mesh_eval.py).
+ * Deterministic, no random state. Two passes around an exclusive prefix sum the caller makes:
+ *   vdn_surf_count: counts[f] = ceil(area_f / spacing^2), area_f = 0.5 |(b - a) x (c - a)| in double; 0 where the area is 0 or
+ *                   not finite (clamped to INT32_MAX). A corner index outside [0, V) gives counts[f] = 0 and sets *error = 1
+ *                   (the caller zeroes it first): nothing is read out of bounds.
+ *   vdn_surf_emit:  one thread per SAMPLE s < S: its triangle f by binary search in `offsets`, j = s - offsets[f], the R2
+ *                   low-discrepancy point (u, v) = frac(0.5 + (j + 1) (0.7548776662466927, 0.5698402909980532)) in double, folded
+ *                   into the triangle ((u, v) -> (1 - u, 1 - v) where u + v > 1), points[s] = a + u (b - a) + v (c - a) rounded
+ *                   to fp32, face[s] = f.
+ * Status -10: V, F or S do not fit 32-bit indexing. */
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes) */
+    double spacing;                /* one sample per spacing^2 of area */
+    int64_t V, F, S;               /* S = sum of counts (emit pass) */
+    int32_t index_bytes, _pad;     /* 8 or 4 */
+    int32_t* counts;               /* [F]   (count pass) */
+    int32_t* error;                /* [1]   (count pass) */
+    const int64_t* offsets;        /* [F] exclusive prefix sum of counts   (emit pass) */
+    float* points;                 /* [S][3] */
+    int32_t* face;                 /* [S] */
+} VdnSurfArgs;
+int vdn_surf_count(const VdnSurfArgs* args_host, void* stream);
+int vdn_surf_emit(const VdnSurfArgs* args_host, void* stream);
+
+/* ---- mesh evaluation: exact nearest neighbour on a uniform grid (csrc/mesh_eval.hip; vdn_hip/nn.py: PointGrid) --------------
+ * The grid is dense over the reference's bounding box: nx * ny * nz cells of edge h from (lo_x, lo_y, lo_z), cell id
+ * (z * ny + y) * nx + x with each coordinate floor((p - lo) / h) in fp32 clamped into the grid (so a point outside the box, or NaN,
+ * lands in a border cell).
+ *   vdn_nn_bin:   cell[i] of pts[i], i < N. The caller sorts the reference by cell (stable), packs it as 16-byte records
+ *                 {x, y, z, original index as bits} in `ref` and makes cell_start[c] = first record of cell c, cell_start[cells] = R.
+ *   vdn_nn_query: one lane per query pts[order[t]] (order: the queries' own cell-sorted order, or NULL), Chebyshev shells
+ *                 k = 0, 1, .. around the query's cell. With r = k h - margin the search stops after shell k when r > 0 and
+ *                 (best <= r or r >= max_dist), or when the shell has left the grid on all sides: every point in a cell at index
+ *                 distance >= k + 1 is at least k h away, less the rounding of the fp32 binning, which `margin` (a few ulps of
+ *                 the box extent) covers. dist = sqrt(sum (q - r)^2) in fp32, the lower original index on equal distances;
+ *                 dist = +inf, idx = -1 where no reference point lies within max_dist (inclusive; +inf: unbounded).
+ *                 rings[q] (optional) = shells visited.
+ * Status -10: N, R or the cell count do not fit 32-bit indexing. */
+typedef struct {
+    const float* pts;              /* [N][3] the points to bin / the queries */
+    int32_t* cell;                 /* [N] out   (bin) */
+    const float* ref;              /* [R][4] sorted packed reference   (query) */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1]   (query) */
+    const int32_t* order;          /* [N] or NULL   (query) */
+    float* dist;                   /* [N] out   (query) */
+    int64_t* idx;                  /* [N] out   (query) */
+    int32_t* rings;                /* [N] out or NULL   (query) */
+    int64_t N, R;
+    float lo_x, lo_y, lo_z, h, margin, max_dist;
+    int32_t nx, ny, nz, _pad;
+} VdnNnArgs;
+int vdn_nn_bin(const VdnNnArgs* args_host, void* stream);
+int vdn_nn_query(const VdnNnArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

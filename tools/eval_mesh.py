@@ -1,0 +1,33 @@
+"""Accuracy / completeness / Chamfer distance / F-scores of a mesh file against a ground-truth point cloud, on the device
+(vdn_train/mesh_eval.py; INTEGRATION.md "Mesh evaluation"):
+
+    python tools/eval_mesh.py meshes/00300000.ply scan.ply --spacing 0.2 --max-dist 20 --thresholds 1 2
+
+The mesh is a PLY of vdn_train.meshio.write_ply (validate_mesh(world_space=True) writes one in the scan's frame); the cloud is any
+binary little-endian PLY whose first element is `vertex` with x, y, z. Prints one JSON line."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "vdn-nerf_amd"), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("mesh")
+    ap.add_argument("ground_truth")
+    ap.add_argument("--spacing", type=float, required=True, help="one mesh sample per spacing^2 of area")
+    ap.add_argument("--max-dist", type=float, required=True, help="distances beyond it are outliers: left out of the means")
+    ap.add_argument("--thresholds", type=float, nargs="*", default=[], help="F-score thresholds (each <= --max-dist)")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    from vdn_train import mesh_eval
+    res = mesh_eval.evaluate_ply(a.mesh, a.ground_truth, a.spacing, a.max_dist, a.thresholds, device=a.device)
+    print(mesh_eval.to_json(dict(res, mesh=a.mesh, ground_truth=a.ground_truth, spacing=a.spacing, max_dist=a.max_dist)))
+
+
+if __name__ == "__main__":
+    main()

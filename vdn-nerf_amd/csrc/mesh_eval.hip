@@ -1,0 +1,183 @@
+// Mesh evaluation on the device (include/vdn_render.h: vdn_surf_*, vdn_nn_*): area-weighted surface sampling of a triangle mesh
+// and exact nearest neighbours on a uniform grid - the two halves of an accuracy / completeness / Chamfer figure against a scanned
+// point cloud (vdn_train/mesh_eval.py). Gather-bound integer / float work, no LDS: one thread per triangle, per sample, per point
+// or per query. The prefix sum, the stable sorts and the cell-start table between the passes are the caller's torch ops.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <climits>
+#include "vdn_render.h"
+
+namespace vdn {
+
+// ---- surface sampling -----------------------------------------------------------------------------------------------------------
+// corner indices of triangle f, or false when one of them is outside [0, V)
+__device__ inline bool surf_corners(const VdnSurfArgs& a, long f, long* i) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        i[c] = a.index_bytes == 8 ? (long)((const int64_t*)a.triangles)[f * 3 + c] : (long)((const int32_t*)a.triangles)[f * 3 + c];
+        if (i[c] < 0 || i[c] >= (long)a.V) return false;
+    }
+    return true;
+}
+
+__global__ void surf_count_kernel(VdnSurfArgs a) {
+    const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= (long)a.F) return;
+    long i[3];
+    int n = 0;
+    if (!surf_corners(a, f, i)) {
+        *a.error = 1;                  // (every writer stores the same word)
+    } else {
+        double p[3][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) p[c][d] = (double)a.vertices[i[c] * 3 + d];
+        const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
+        const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
+        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double area = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+        const double r = area / (a.spacing * a.spacing);
+        if (area > 0.0 && r < INFINITY) n = r >= (double)INT_MAX ? INT_MAX : (int)ceil(r);      // (NaN fails `area > 0`)
+    }
+    a.counts[f] = n;
+}
+
+__global__ void surf_emit_kernel(VdnSurfArgs a) {
+    const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= (long)a.S) return;
+    // the last triangle whose exclusive offset is <= s: the triangles behind it that share the offset have no samples
+    long lo = 0, hi = (long)a.F;                     // invariant: offsets[lo] <= s, offsets[hi] > s (offsets[F] = S)
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if (a.offsets[mid] <= s) lo = mid; else hi = mid;
+    }
+    const long f = lo;
+    long i[3];
+    if (!surf_corners(a, f, i)) return;              // (such a triangle has no samples: unreachable, and nothing is read out of bounds)
+    const double j1 = (double)(s - a.offsets[f] + 1);
+    double u = 0.5 + j1 * 0.7548776662466927, v = 0.5 + j1 * 0.5698402909980532;
+    u -= floor(u);
+    v -= floor(v);
+    if (u + v > 1.0) { u = 1.0 - u; v = 1.0 - v; }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double pa = (double)a.vertices[i[0] * 3 + d], pb = (double)a.vertices[i[1] * 3 + d], pc = (double)a.vertices[i[2] * 3 + d];
+        a.points[s * 3 + d] = (float)(pa + u * (pb - pa) + v * (pc - pa));
+    }
+    a.face[s] = (int)f;
+}
+
+// ---- nearest neighbour on a uniform grid ------------------------------------------------------------------------------------------
+// cell coordinate along one axis: floor((p - lo) / h) in fp32, clamped into the grid (a point outside, or NaN, lands in a border cell)
+__device__ inline int nn_axis(float p, float lo, float h, int n) {
+    const float t = (p - lo) / h;
+    return (int)fminf(fmaxf(floorf(t), 0.0f), (float)(n - 1));
+}
+
+__global__ void nn_bin_kernel(VdnNnArgs a) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)a.N) return;
+    const int cx = nn_axis(a.pts[i * 3 + 0], a.lo_x, a.h, a.nx), cy = nn_axis(a.pts[i * 3 + 1], a.lo_y, a.h, a.ny),
+              cz = nn_axis(a.pts[i * 3 + 2], a.lo_z, a.h, a.nz);
+    a.cell[i] = (cz * a.ny + cy) * a.nx + cx;
+}
+
+struct NnBest {
+    float d2;
+    int idx;
+};
+
+// the records of cells [c0, c1] of one x-row (contiguous in the sorted reference), against the query
+__device__ inline void nn_scan(const VdnNnArgs& a, int c0, int c1, float qx, float qy, float qz, NnBest& b) {
+    const int begin = max(a.cell_start[c0], 0), end = min(a.cell_start[c1 + 1], (int)a.R);
+    const float4* rec = (const float4*)a.ref;
+    for (int r = begin; r < end; ++r) {
+        const float4 p = rec[r];                       // one 16-byte load: x, y, z, original index
+        const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+        const float d2 = dx * dx + dy * dy + dz * dz;
+        const int id = __float_as_int(p.w);
+        // ties go to the lower original index, so the answer does not depend on the order cells are visited in
+        if (d2 < b.d2 || (d2 == b.d2 && id < b.idx)) { b.d2 = d2; b.idx = id; }
+    }
+}
+
+__global__ void nn_query_kernel(VdnNnArgs a) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)a.N) return;
+    const long q = a.order != nullptr ? (long)a.order[t] : t;
+    const float qx = a.pts[q * 3 + 0], qy = a.pts[q * 3 + 1], qz = a.pts[q * 3 + 2];
+    const int cx = nn_axis(qx, a.lo_x, a.h, a.nx), cy = nn_axis(qy, a.lo_y, a.h, a.ny), cz = nn_axis(qz, a.lo_z, a.h, a.nz);
+    // the last shell that still touches the grid
+    const int k_last = max(max(max(cx, a.nx - 1 - cx), max(cy, a.ny - 1 - cy)), max(cz, a.nz - 1 - cz));
+    NnBest b = {INFINITY, INT_MAX};
+    int k = 0;
+    for (;; ++k) {
+        // Chebyshev shell k: rows (y, z) on the shell's y / z faces take the whole x-range, the others its two end cells
+        const int x0 = max(cx - k, 0), x1 = min(cx + k, a.nx - 1);
+        for (int z = max(cz - k, 0); z <= min(cz + k, a.nz - 1); ++z) {
+            for (int y = max(cy - k, 0); y <= min(cy + k, a.ny - 1); ++y) {
+                const int row = (z * a.ny + y) * a.nx;
+                if (abs(z - cz) == k || abs(y - cy) == k) {
+                    nn_scan(a, row + x0, row + x1, qx, qy, qz, b);
+                } else {
+                    if (cx - k >= 0) nn_scan(a, row + cx - k, row + cx - k, qx, qy, qz, b);
+                    if (cx + k < a.nx) nn_scan(a, row + cx + k, row + cx + k, qx, qy, qz, b);
+                }
+            }
+        }
+        if (k >= k_last) break;
+        // every point in a cell at index distance >= k + 1 is at least k h away, less the fp32 rounding of the binning: `margin`
+        const float r = (float)k * a.h - a.margin;
+        if (r > 0.0f && (b.d2 <= r * r || r >= a.max_dist)) break;
+    }
+    const float d = sqrtf(b.d2);
+    const bool hit = b.idx != INT_MAX && d <= a.max_dist;
+    a.dist[q] = hit ? d : INFINITY;
+    a.idx[q] = hit ? (int64_t)b.idx : (int64_t)-1;
+    if (a.rings != nullptr) a.rings[q] = k + 1;
+}
+
+}  // namespace vdn
+
+static inline unsigned grid_of(long n) { return (unsigned)((n + 255) / 256); }
+
+extern "C" int vdn_surf_count(const VdnSurfArgs* a, void* stream) {
+    if (a == nullptr || a->triangles == nullptr || a->counts == nullptr || a->error == nullptr || a->F < 1 || a->V < 0 ||
+        (a->V > 0 && a->vertices == nullptr) || (a->index_bytes != 4 && a->index_bytes != 8) || !(a->spacing > 0.0)) return -1;
+    if (a->F > INT_MAX || a->V > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::surf_count_kernel, dim3(grid_of(a->F)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_surf_emit(const VdnSurfArgs* a, void* stream) {
+    if (a == nullptr || a->triangles == nullptr || a->vertices == nullptr || a->offsets == nullptr || a->points == nullptr ||
+        a->face == nullptr || a->F < 1 || a->V < 1 || a->S < 1 || (a->index_bytes != 4 && a->index_bytes != 8)) return -1;
+    if (a->F > INT_MAX || a->V > INT_MAX || a->S > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::surf_emit_kernel, dim3(grid_of(a->S)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+static int nn_grid_check(const VdnNnArgs* a) {
+    if (a == nullptr || a->pts == nullptr || a->N < 1 || a->nx < 1 || a->ny < 1 || a->nz < 1 || !(a->h > 0.0f) || !(a->h < INFINITY)) return -1;
+    if (a->N > INT_MAX || (int64_t)a->nx * a->ny * a->nz >= (int64_t)INT_MAX) return -10;
+    return 0;
+}
+
+extern "C" int vdn_nn_bin(const VdnNnArgs* a, void* stream) {
+    const int rc = nn_grid_check(a);
+    if (rc != 0) return rc;
+    if (a->cell == nullptr) return -1;
+    hipLaunchKernelGGL(vdn::nn_bin_kernel, dim3(grid_of(a->N)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_nn_query(const VdnNnArgs* a, void* stream) {
+    const int rc = nn_grid_check(a);
+    if (rc != 0) return rc;
+    if (a->ref == nullptr || a->cell_start == nullptr || a->dist == nullptr || a->idx == nullptr || a->R < 1 || !(a->margin >= 0.0f) ||
+        !(a->max_dist >= 0.0f)) return -1;
+    if (a->R > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::nn_query_kernel, dim3(grid_of(a->N)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}

@@ -76,6 +76,57 @@ def marching_cubes(u, threshold=0.0):
     return vertices, triangles
 
 
+def sample_surface(vertices, triangles, spacing, max_samples=1 << 26):
+    """Area-weighted, deterministic samples of a triangle mesh (vdn_surf_count / vdn_surf_emit, include/vdn_render.h):
+    vertices [V,3] CUDA float, triangles [F,3] CUDA int64 or int32 -> (points [S,3] fp32, face [S] int32, counts [F] int32).
+    Triangle f gets counts[f] = ceil(area_f / spacing^2) samples (0 for a zero or non-finite area), sample j at the R2
+    low-discrepancy point j + 1 folded into the triangle; no random state, two calls give the same bits. ValueError on CPU
+    tensors, wrong shapes, spacing <= 0, a corner index outside [0, V), or more than max_samples samples (checked on the
+    counts, before the outputs are allocated)."""
+    if not (torch.is_tensor(vertices) and vertices.is_cuda and vertices.dim() == 2 and vertices.shape[1] == 3 and vertices.is_floating_point()):
+        raise ValueError("sample_surface needs vertices as a float [V,3] CUDA tensor")
+    if not (torch.is_tensor(triangles) and triangles.is_cuda and triangles.dim() == 2 and triangles.shape[1] == 3 and
+            triangles.dtype in (torch.int64, torch.int32)):
+        raise ValueError("sample_surface needs triangles as an int64 or int32 [F,3] CUDA tensor")
+    if triangles.device != vertices.device:
+        raise ValueError("vertices and triangles must be on the same device")
+    if not (float(spacing) > 0.0 and float(spacing) < float("inf")):
+        raise ValueError("spacing must be positive and finite, got %r" % (spacing,))
+    dev = vertices.device
+    v, t = vertices.detach().float().contiguous(), triangles.contiguous()
+    V, F = v.shape[0], t.shape[0]
+    if F == 0:
+        return (torch.empty(0, 3, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = lib.stream_handle()
+        counts = torch.empty(F, dtype=torch.int32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = lib.VdnSurfArgs()
+        a.vertices, a.triangles, a.spacing, a.V, a.F = v.data_ptr(), t.data_ptr(), float(spacing), V, F
+        a.index_bytes, a.counts, a.error = t.element_size(), counts.data_ptr(), err.data_ptr()
+        _call_sized("vdn_surf_count", a, st)
+        incl = torch.cumsum(counts, 0, dtype=torch.int64)
+        S, bad = torch.stack([incl[-1], err[0].long()]).tolist()         # one host read: the output size and the error flag
+        if bad:
+            raise ValueError("a triangle refers to a vertex outside [0, %d)" % V)
+        if S > max_samples or S >= 1 << 31:
+            raise ValueError("spacing %g gives %d samples, more than max_samples = %d (or than 32-bit indexing holds)" % (spacing, S, max_samples))
+        points = torch.empty(S, 3, dtype=torch.float32, device=dev)
+        face = torch.empty(S, dtype=torch.int32, device=dev)
+        if S > 0:
+            offsets = (incl - counts).contiguous()
+            a.S, a.offsets, a.points, a.face = S, offsets.data_ptr(), points.data_ptr(), face.data_ptr()
+            _call_sized("vdn_surf_emit", a, st)
+    return points, face, counts
+
+
+def _call_sized(name, *args):
+    """lib.call for the entry points that decline sizes beyond 32-bit indexing with status -10: that is the caller's ValueError."""
+    if not lib.try_call(name, *args):
+        raise ValueError("%s: the sizes do not fit 32-bit indexing" % name)
+
+
 def fused_point_shading(renderer):
     """True where vdn_shade_points_bf16 (csrc/k_sdf_fwd2.h MODE 4) covers the configuration: both networks on the bf16 kernels and
     the colour head the "c2" stream exists for ('idr', d_feature 256, d_out 3). VDN_SHADE_POINTS_FUSED=0 forces the separate launches."""

@@ -69,6 +69,62 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
     return path
 
 
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+                "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def read_points_ply(path):
+    """-> vertex positions [V,3] (float32, or float64 where the file stores doubles) of any `binary_little_endian 1.0` file whose
+    first element is `vertex` with scalar properties that include x, y, z - the layout of scanned ground-truth clouds (positions,
+    normals, uchar colours, no faces). The other properties and every later element are ignored. ValueError on ASCII or big-endian
+    files, a list property in the vertex element, missing coordinates or a truncated file. (read_ply stays the strict reader of
+    write_ply's own files.)"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError("%s: no PLY header" % path)
+    n_head = end + len(b"end_header\n")
+    try:
+        lines = [ln.strip() for ln in data[:n_head].decode("ascii").split("\n")]
+    except UnicodeDecodeError:
+        raise ValueError("%s: the PLY header is not ASCII text" % path)
+    if lines[0] != "ply":
+        raise ValueError("%s: not a PLY file" % path)
+    lines = [ln for ln in lines[1:] if ln and not ln.startswith(("comment", "obj_info"))]
+    if not lines or lines[0].split() != ["format", "binary_little_endian", "1.0"]:
+        raise ValueError("%s: only `format binary_little_endian 1.0` files are read, got %r" % (path, lines[:1]))
+    V, fields, n_elements = None, [], 0
+    for ln in lines[1:]:
+        tok = ln.split()
+        if tok[0] == "element":
+            n_elements += 1
+            if n_elements == 1:
+                try:
+                    assert tok[1] == "vertex" and len(tok) == 3
+                    V = int(tok[2])
+                    assert V >= 0
+                except (AssertionError, ValueError, IndexError):
+                    raise ValueError("%s: the first element must be `element vertex V`, got %r" % (path, ln))
+        elif tok[0] == "property" and n_elements == 1:
+            if len(tok) >= 2 and tok[1] == "list":
+                raise ValueError("%s: a list property in the vertex element: %r" % (path, ln))
+            if len(tok) != 3 or tok[1] not in _PLY_SCALARS:
+                raise ValueError("%s: unknown vertex property %r" % (path, ln))
+            fields.append((tok[2], _PLY_SCALARS[tok[1]]))
+    if V is None:
+        raise ValueError("%s: no vertex element" % path)
+    names = [n for n, _ in fields]
+    if len(set(names)) != len(names) or not all(n in names for n in _POS):
+        raise ValueError("%s: the vertex element needs one x, y and z each, got %r" % (path, names))
+    vd = np.dtype(fields)
+    if len(data) < n_head + V * vd.itemsize:
+        raise ValueError("%s: %d bytes, the vertex element alone needs %d" % (path, len(data), n_head + V * vd.itemsize))
+    vert = np.frombuffer(data, dtype=vd, count=V, offset=n_head)
+    out = np.float64 if any(vd[n] == np.dtype("<f8") for n in _POS) else np.float32
+    return np.stack([vert[n].astype(out) for n in _POS], axis=1) if V > 0 else np.zeros((0, 3), out)
+
+
 def read_ply(path):
     """-> dict(vertices [V,3] float32, triangles [F,3] int32, normals [V,3] float32 | None, colors [V,3] uint8 | None) of a file
     written by write_ply; ValueError on any other header (ASCII, big-endian, other properties) or a size that does not match."""
