@@ -868,6 +868,94 @@ typedef struct {
 int vdn_nn_bin(const VdnNnArgs* args_host, void* stream);
 int vdn_nn_query(const VdnNnArgs* args_host, void* stream);
 
+/* ---- mesh cleaning: connected components of a triangle mesh (csrc/mesh_clean.hip; vdn_hip/mesh.py: connected_components) --------
+ * Two triangles are connected when they share a vertex INDEX (no welding by position). A lock-free union-find over the index
+ * buffer in `parent` [V], which the caller initialises to 0, 1, .., V - 1:
+ *   vdn_cc_union:   one thread per triangle joins its three corners. A join finds the two roots and hooks the LARGER root under
+ *                   the smaller by a compare-and-swap on the root's own slot; a loser continues from the value the swap returned.
+ *                   Slots only ever decrease (the find loop halves long paths by atomic minimum), no thread waits for another.
+ *                   A corner index outside [0, V) sets *error = 1 (the caller zeroes it first) and that triangle joins nothing:
+ *                   nothing is read or written out of bounds. Degenerate (a, a, b) and repeated triangles are legal.
+ *   vdn_cc_flatten: one thread per vertex, label[v] = root of v = the SMALLEST vertex index of v's component: independent of the
+ *                   thread order, identical between calls and under any permutation of the triangles. A vertex in no triangle
+ *                   is its own component. F = 0 is legal here (label = parent's roots).
+ * Status -10: V or F do not fit 32-bit indexing. */
+typedef struct {
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes)   (union) */
+    int32_t* parent;               /* [V] in / out (union), in (flatten) */
+    int32_t* label;                /* [V] out   (flatten) */
+    int32_t* error;                /* [1]   (union) */
+    int64_t V, F;
+    int32_t index_bytes, _pad;     /* 8 or 4 */
+} VdnCcArgs;
+int vdn_cc_union(const VdnCcArgs* args_host, void* stream);
+int vdn_cc_flatten(const VdnCcArgs* args_host, void* stream);
+
+/* vdn_tri_area: area[f] = 0.5 |(b - a) x (c - a)| in double from the fp32 vertices (the expression of vdn_surf_count, one device
+ * function for both), 0 where the result is not finite. A corner outside [0, V) gives area 0 and sets *error = 1. */
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes) */
+    double* area;                  /* [F] out */
+    int32_t* error;                /* [1] */
+    int64_t V, F;
+    int32_t index_bytes, _pad;
+} VdnTriAreaArgs;
+int vdn_tri_area(const VdnTriAreaArgs* args_host, void* stream);
+
+/* ---- mesh cleaning: object masks (csrc/mesh_clean.hip; vdn_hip/mesh.py: dilate_masks, mask_votes) ------------------------------
+ * vdn_mask_dilate: dst = the maximum of src over the (2 radius + 1)^2 square around each pixel, pixels outside the image counting
+ *   as 0 (cv.dilate with a kernel of ones; nonzero = set, so a 0 / 1 or 0 / 255 mask keeps its two values). Separable: a row pass
+ *   src -> scratch and a column pass scratch -> dst, two launches; scratch is a plane set of its own. radius = 0 copies.
+ * vdn_mask_votes: one thread per vertex, looping over the N cameras, no atomics. P[n] maps the mesh's own frame to (u w, v w, w),
+ *   evaluated in double on the widened fp32 vertex; px = floor(u + 0.5), py = floor(v + 0.5) (pixel centres at integer coordinates,
+ *   as vdn_gen_rays has them). The vertex is "in image" of camera n iff w > 0, u and v are finite and 0 <= px < W, 0 <= py < H;
+ *   n_in_image[v] counts those cameras, n_in_mask[v] those of them whose mask is nonzero at (py, px).
+ * Status -10: V, N * H * W or H * W do not fit 32-bit indexing. */
+typedef struct {
+    const uint8_t* src;            /* [N][H][W] */
+    uint8_t* scratch;              /* [N][H][W] workspace */
+    uint8_t* dst;                  /* [N][H][W] out (may be src) */
+    int64_t N;
+    int32_t H, W, radius, _pad;
+} VdnMaskDilateArgs;
+int vdn_mask_dilate(const VdnMaskDilateArgs* args_host, void* stream);
+
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const double* P;               /* [N][3][4] row-major */
+    const uint8_t* masks;          /* [N][H][W] nonzero = set */
+    int32_t* n_in_image;           /* [V] out */
+    int32_t* n_in_mask;            /* [V] out */
+    int64_t V, N;
+    int32_t H, W;
+} VdnMaskVotesArgs;
+int vdn_mask_votes(const VdnMaskVotesArgs* args_host, void* stream);
+
+/* ---- mesh cleaning: face / vertex compaction (csrc/mesh_clean.hip; vdn_hip/mesh.py: filter_mesh) ------------------------------
+ * Two passes around the exclusive prefix sums the caller makes:
+ *   vdn_mesh_filter_mark:  face_alive[f] = keep_face[f] (or 1 where NULL) and keep_vertex of all three corners (where not NULL);
+ *                          a surviving face stores 1 to vertex_used of its corners (the caller zeroes vertex_used first; plain
+ *                          byte stores of one value). A corner outside [0, V) kills the face and sets *error = 1.
+ *   vdn_mesh_filter_remap: surviving face f goes to row face_offsets[f] of out_triangles, in the input's order and index width,
+ *                          each corner i renumbered to vertex_new[i].
+ * Status -10: V or F do not fit 32-bit indexing. */
+typedef struct {
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes) */
+    const uint8_t* keep_face;      /* [F] or NULL   (mark) */
+    const uint8_t* keep_vertex;    /* [V] or NULL   (mark) */
+    uint8_t* face_alive;           /* [F] out (mark), in (remap) */
+    uint8_t* vertex_used;          /* [V] in / out   (mark) */
+    int32_t* error;                /* [1]   (mark) */
+    const int64_t* face_offsets;   /* [F] exclusive prefix sum of face_alive   (remap) */
+    const int64_t* vertex_new;     /* [V] new index of each surviving vertex   (remap) */
+    void* out_triangles;           /* [F_out][3]   (remap) */
+    int64_t V, F, F_out;           /* F_out = sum of face_alive */
+    int32_t index_bytes, _pad;
+} VdnMeshFilterArgs;
+int vdn_mesh_filter_mark(const VdnMeshFilterArgs* args_host, void* stream);
+int vdn_mesh_filter_remap(const VdnMeshFilterArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

@@ -6,18 +6,13 @@
 #include <cstdint>
 #include <climits>
 #include "vdn_render.h"
+#include "k_tri.h"
 
 namespace vdn {
 
 // ---- surface sampling -----------------------------------------------------------------------------------------------------------
-// corner indices of triangle f, or false when one of them is outside [0, V)
 __device__ inline bool surf_corners(const VdnSurfArgs& a, long f, long* i) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        i[c] = a.index_bytes == 8 ? (long)((const int64_t*)a.triangles)[f * 3 + c] : (long)((const int32_t*)a.triangles)[f * 3 + c];
-        if (i[c] < 0 || i[c] >= (long)a.V) return false;
-    }
-    return true;
+    return tri_corners(a.triangles, a.index_bytes, (long)a.V, f, i);      // (k_tri.h, shared with mesh_clean.hip)
 }
 
 __global__ void surf_count_kernel(VdnSurfArgs a) {
@@ -28,15 +23,7 @@ __global__ void surf_count_kernel(VdnSurfArgs a) {
     if (!surf_corners(a, f, i)) {
         *a.error = 1;                  // (every writer stores the same word)
     } else {
-        double p[3][3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) p[c][d] = (double)a.vertices[i[c] * 3 + d];
-        const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-        const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-        const double area = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+        const double area = tri_area(a.vertices, i);
         const double r = area / (a.spacing * a.spacing);
         if (area > 0.0 && r < INFINITY) n = r >= (double)INT_MAX ? INT_MAX : (int)ceil(r);      // (NaN fails `area > 0`)
     }

@@ -138,6 +138,14 @@ class SceneData:
         g.images_lis = self.images_lis
         return g
 
+    def projection_matrices(self, world_space=False):
+        """float64 [n,3,4]: each camera's map from a mesh's frame to (u w, v w, w) in pixels, multiplied in float64 from the stored
+        float32 matrices - (world_mat @ scale_mat)[:3] for a mesh in object space (what extract_geometry returns), world_mat[:3]
+        for one in world space (validate_mesh(world_space=True)). What vdn_train.mesh_clean.clean_mesh takes as `cameras`."""
+        if world_space:
+            return np.stack([w.astype(np.float64)[:3, :4] for w in self.world_mats_np])
+        return np.stack([(w.astype(np.float64) @ s.astype(np.float64))[:3, :4] for w, s in zip(self.world_mats_np, self.scale_mats_np)])
+
     def depth_from_sdf_path(self, idx):
         return os.path.join(self.data_dir, self.img_dir, "depth_from_sdf", "sdf_%s.npy" % self.names[idx])
 

@@ -150,12 +150,14 @@ def val_img(renderer, scene, rays_gen, idx, resolution_level=1, batch_size=512, 
 
 
 def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, threshold=0.0, world_space=False, scale_mat=None,
-                  vertex_colors=True, vertex_normals=True):
+                  vertex_colors=True, vertex_normals=True, clean=None):
     """Runner.validate_mesh (dpt_runner.py:699-713) without trimesh: the iso-surface of the SDF network inside the box, written
     to `out_path` as a binary PLY (vdn_train/meshio.py) -> (out_path, V, F). `world_space` maps the vertices by
     v * scale_mat[0,0] + scale_mat[:3,3] (708; a uniform scale and a translation: unit normals are unchanged). Beyond the
     reference's bare mesh, each vertex carries its unit normal and its colour seen straight down that normal
-    (NeuSRenderer.extract_colored_geometry); with both flags off the file is the reference's and no network runs past the lattice."""
+    (NeuSRenderer.extract_colored_geometry); with both flags off the file is the reference's and no network runs past the lattice.
+    `clean` (a dict of vdn_train.mesh_clean.clean_mesh's keyword arguments, or None: the raw surface) cleans the mesh in object
+    space, before the world_space map; normals and colours follow their vertices, and V, F are the cleaned mesh's."""
     from vdn_train import meshio
     normals = colors = None
     if vertex_colors or vertex_normals:
@@ -164,6 +166,13 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
         colors = colors if vertex_colors else None
     else:
         vertices, triangles = renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+    if clean is not None:
+        from vdn_train import mesh_clean
+        attrs = [x for x in (normals, colors) if x is not None]
+        res = mesh_clean.clean_mesh(vertices, triangles, attributes=attrs, **clean)
+        vertices, triangles, attrs = res["vertices"], res["triangles"], list(res["attributes"])
+        normals = attrs.pop(0) if normals is not None else None
+        colors = attrs.pop(0) if colors is not None else None
     if world_space:
         if scale_mat is None:
             raise ValueError("world_space=True needs the scene's scale_mat (SceneData.scale_mats_np[0])")
@@ -176,10 +185,15 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     return out_path, int(vertices.shape[0]), int(triangles.shape[0])
 
 
-def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, **kw):
+def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, **kw):
     """validate_mesh for a vdn_train.dataset.SceneData: its object bounding box and scale_mats_np[0], the runner's file name
-    meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711)."""
+    meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711). A `clean` dict with a true "use_masks" entry gets
+    the scene's object-space cameras and its masks (cleaning happens in object space)."""
+    if clean is not None:
+        clean = dict(clean)
+        if clean.pop("use_masks", False):
+            clean.update(cameras=scene.projection_matrices(world_space=False), masks=scene.masks)
     bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
     bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
     return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
-                         scale_mat=scene.scale_mats_np[0], **kw)
+                         scale_mat=scene.scale_mats_np[0], clean=clean, **kw)
