@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void nerf_fwd2_kernel(NerfArgs a) {
     const long MS = P::mask_plane(a.P, 256);
     auto sm = [&](int l) VDN_INL { return MASK ? save_mask + l * MS : nullptr; };
     warm_l2_wait();
-    pp.template start<PG>();
+    pp.template start<flow::Policy<PG, decltype(pp)>>();
     auto f0 = flow::flow_begin();
     auto f1 = flow::dense2<PG, 8>(f0, pp, X, flow::NoLoad{}, relu_into(Y, 0, sv(0), 256, sm(0)));          // pts_linears.0
     auto f2 = flow::dense2<PG, 8>(f1, pp, Y, flow::NoLoad{}, relu_into(X, 0, sv(1), 256, sm(1)));          // 1

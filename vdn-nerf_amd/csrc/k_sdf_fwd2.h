@@ -25,7 +25,7 @@
 #include <cstdlib>
 #include "k_ray_rows.h"
 #include "k_composite_row.h"
-#include "mlp_engine.h"
+#include "chunk_stream.h"
 #include "vdn_kernels.h"
 
 namespace vdn {
@@ -77,6 +77,8 @@ constexpr int kSTiles = 63;             // softplus' tiles per point block: 8 + 
 #if VDN_SDF2_S16
 struct AccT {
     f32x4 v[4];         // [2 ph + fh]
+    static constexpr int kBiasRows = 2;
+    static VDN_DEV int quad(int g, int lane) { return 4 * (lane >> 5) + 2 * (g & 1) + ((lane >> 4) & 1); }
     VDN_DEV float operator[](int t) const { return v[t >> 2][t & 3]; }
     VDN_DEV void fill(const f32x4 (&bias)[4], bool with_bias) {
 #pragma unroll
@@ -94,20 +96,10 @@ struct AccT {
     }
 };
 #else
-struct AccT {
-    f32x16 w;
-    VDN_DEV float operator[](int t) const { return w[t]; }
-    VDN_DEV void fill(const f32x4 (&bias)[4], bool with_bias) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) w[t] = with_bias ? bias[t >> 2][t & 3] : 0.0f;
-    }
-    template <int S, class ActT>
-    VDN_DEV void mfma(const bf16x8& a, const ActT& X) { w = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, X.r[S], w, 0, 0, 0); }
-    VDN_DEV void add(const AccT& o) { w += o.w; }
-};
+using AccT = cstream::Acc32;
 #endif
 // accumulator registers 4 g .. 4 g + 3 of this lane are features 4 quad_of(g) .. + 3 of the tile's natural order
-VDN_DEV int quad_of(int g, int lane) { return kS16 ? 4 * (lane >> 5) + 2 * (g & 1) + ((lane >> 4) & 1) : 2 * g + (lane >> 5); }
+VDN_DEV int quad_of(int g, int lane) { return AccT::quad(g, lane); }
 // the point half a logical register pair belongs to
 constexpr int ph_of_pair(int pr) { return kS16 ? pr >> 2 : 0; }
 
@@ -196,156 +188,25 @@ constexpr int wait_count(int c) {
     return n < 63 ? n : 63;
 }
 
-template <int N>
-VDN_DEV void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS-DMA of 16 B per lane, written as inline asm: the builtin makes hipcc's wait-count pass treat every later LDS
-// wait as out of order (it marks a pending FLAT access), and it then emits s_waitcnt lgkmcnt(0) in front of every MFMA
-// that consumes a fragment - a full LDS round trip per MFMA group instead of a counted wait. Completion is tracked by the
-// kernel's own counted vmcnt (the compiler does not see these loads).
-// Addressing (round 5): immediate offsets, one M0 write per chunk (vdn_common.h: glds16_imm*). VDN_SDF2_DMA_IMM=0: the A/B arm
-// with one scalar base and one M0 write per piece.
-#ifndef VDN_SDF2_DMA_IMM
-#define VDN_SDF2_DMA_IMM 1
-#endif
-VDN_DEV void glds16_saddr(const char* base_uniform, unsigned lane_off, char* lds_wave_base) {
-    const unsigned lds = (unsigned)(size_t)lds_wave_base;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" ::"v"(lane_off), "s"(lds), "s"(base_uniform) : "memory", "m0");
-}
-// ---- pipeline state ---------------------------------------------------------------------------------------------
-template <int NSLOT, int SPLIT = (1 << 30)>
-struct Pipe {
-    const char* g;      // weight stream (wave-uniform)
-    const char* g2;     // chunks from SPLIT on: a second stream (MODE 2: the colour head's)
-    char* lds;          // ring base
-    int wave, lane;
-    unsigned lane16;    // lane * 16
-    bf16x8 fr[kPre];    // first fragments of the next chunk step (already read)
-    f32x4 bias[4];      // its bias rows
-    template <int C>
-    VDN_DEV char* slot() const { return lds + (C % NSLOT) * kStride; }
-    // DMA piece I (of kG) of chunk C: 1 KiB, wave-uniform base + per-lane 32-bit offset (scalar-base addressing)
-    unsigned voff0;     // lane * 16 + this wave's first byte in a chunk + 4096 (the centre of the pieces' immediate offsets)
-    unsigned m0_wave;   // LDS byte address of the same place in ring slot 0
-    VDN_DEV void init_dma() {
-        voff0 = lane16 + wave * (kG * 1024) + 4096;
-        m0_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds + wave * (kG * 1024) + 4096);
-    }
-    template <int C, int I>
-    VDN_DEV void issue_piece() {
-#if !(VDN_SDF2_ABL & 4)
-#if VDN_SDF2_DMA_IMM
-        static_assert(kG <= 8, "one group of immediate offsets");
-        constexpr int IMM = glds_imm(I);
-        constexpr long COFF = (C >= SPLIT ? (long)(C - SPLIT) : (long)C) * kStride;
-        static_assert(COFF + kStride < (1L << 31), "32-bit chunk offsets");
-        const char* base = C >= SPLIT ? g2 : g;
-        const unsigned voff = voff0 + (unsigned)COFF;
-        if constexpr (I == 0) glds16_imm_m0add<(C % NSLOT) * kStride, IMM>(base, voff, m0_wave);
-        else glds16_imm<IMM>(base, voff);
-#else
-        const int piece = wave + I * kWaves;
-        if constexpr (C >= SPLIT) glds16_saddr(g2 + ((long)(C - SPLIT) * kStride + piece * 1024), lane16, slot<C>() + piece * 1024);
-        else glds16_saddr(g + ((long)C * kStride + piece * 1024), lane16, slot<C>() + piece * 1024);
-#endif
-#endif
-    }
-    template <int C>
-    VDN_DEV void issue() {
-        static_for<kG>([&](auto i_c) VDN_INL { issue_piece<C, decltype(i_c)::value>(); });
-    }
-    // reads that open chunk step C (its first fragments, and its bias rows)
-    template <int C, int KT, bool BIAS>
-    VDN_DEV void prefetch() {
-        const char* w = slot<C>();
-        const bf16x8* wa = reinterpret_cast<const bf16x8*>(w) + lane;
-#pragma unroll
-        for (int s = 0; s < (kPre < 2 * KT ? kPre : 2 * KT); ++s) fr[s] = wa[s * 64];
-        if constexpr (BIAS) load_bias(reinterpret_cast<const f32x4*>(w + KT * 2048));
-    }
-    VDN_DEV void load_bias(const f32x4* b) {
-#pragma unroll
-        for (int g = 0; g < (kS16 ? 2 : 4); ++g) bias[g] = b[quad_of(g, lane)];
-    }
-};
-
-// One chunk step: acc = (bias) + W[chunk C] . X over KT input tiles. group(gi, NG) = the VALU work assigned to MFMA
-// group gi of NG (kGroup MFMAs per group). Group 0 certifies chunk C+1; the DMA pieces of chunk C+DEPTH follow one per
-// group; the tail reads the opening fragments of chunk C+1.
-template <int MODE, bool SAVE, int NSLOT, int DEPTH, int C, class PipeT, class ActT, class Group>
-VDN_DEV AccT chunk_step(PipeT& pp, const ActT& X, Group&& group) {
+// ---- the chunk steps' policy (chunk_stream.h) ----------------------------------------------------------------------
+template <int MODE, bool SAVE, int NSLOT, int DEPTH>
+struct StepPolicy {
     using PG = Prog<MODE>;
-    constexpr int KT = PG::kt_of(C);
-    constexpr bool BIAS = PG::bias_of(C);
-    constexpr int NS = KT * 2, NG = (NS + kGroup - 1) / kGroup;
-    constexpr int KTN = PG::kt_of(C + 1);
-    constexpr bool HAS_NEXT = C + 1 < PG::total;
-    constexpr bool HAS_DMA = C + DEPTH < PG::total;
-    const bf16x8* wa = reinterpret_cast<const bf16x8*>(pp.template slot<C>()) + pp.lane;
-    const bf16x8* wn = reinterpret_cast<const bf16x8*>(pp.template slot<C + 1>()) + pp.lane;
-    bf16x8 fr[NS];
-    AccT acc;
-    constexpr int PF = kPre < NS ? kPre : NS;                       // fragments of this chunk read by the previous step
-    constexpr int PFN = kPre < 2 * KTN ? kPre : 2 * KTN;            // fragments of the next chunk this step reads
-    static_for<PF>([&](auto s_c) VDN_INL { fr[decltype(s_c)::value] = pp.fr[decltype(s_c)::value]; });
-    acc.fill(pp.bias, BIAS);
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<NG>([&](auto g_c) VDN_INL {
-        constexpr int gi = decltype(g_c)::value;
-        constexpr int s0 = gi * kGroup, s1 = (gi + 1) * kGroup < NS ? (gi + 1) * kGroup : NS;
-        static_for<s1 - s0>([&](auto j_c) VDN_INL {
-            constexpr int s = s0 + decltype(j_c)::value;
-#if VDN_SDF2_ABL & 2
-            { const bf16x8 keep = fr[s]; asm volatile("" ::"v"(keep)); }
-#else
-            acc.template mfma<s>(fr[s], X);
-#endif
-        });
-        // B2: with two spare ring slots the workgroup re-synchronises every SECOND step - the even step certifies chunks C+1 and C+2
-        // (the latter's DMA is one step old: an L2-warm piece lands in 250 - 400 cycles of the ~1 300 a step takes); the slot a step's
-        // DMA overwrites, that of chunk C-2, was last read in step C-2, which every wave had left at the latest barrier (C or C-1)
-        // (VDN_SDF2_B2 = 2: only for the chunks in front of the sweep - behind them one barrier per step again, with the spare slot idle;
-        // the change-over needs nothing: a step of the second kind certifies chunk C+1 by the ordinary count, whether or not the
-        // even step before it already did)
-        constexpr bool B2 = VDN_SDF2_B2 != 0 && NSLOT >= DEPTH + 2 && (VDN_SDF2_B2 != 2 || C < PG::first_chunk(PG::NL < 9 ? PG::NL : 9));
-        if constexpr (gi == 0 && HAS_NEXT && (!B2 || C % 2 == 0)) {
-            __builtin_amdgcn_sched_barrier(0);      // the step's first MFMAs are in the pipe while the wave waits
-            wait_vmcnt<B2 ? wait_count_b2<MODE, SAVE>(C) : wait_count<MODE, SAVE, DEPTH>(C)>();
-#if !(VDN_SDF2_ABL & 8)
-            __builtin_amdgcn_s_barrier();
-#endif
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // DMA of chunk C+DEPTH (into the slot chunk C-1 was read from: every wave is past the barrier), spread over the groups
-        if constexpr (HAS_DMA && dma_burst<MODE, SAVE>(C)) {
-            if constexpr (gi == 0) static_for<kG>([&](auto i_c) VDN_INL { pp.template issue_piece<C + DEPTH, decltype(i_c)::value>(); });
-        } else if constexpr (HAS_DMA) {
-            static_for<kG>([&](auto i_c) VDN_INL {
-                constexpr int i = decltype(i_c)::value;
-                if constexpr ((NG >= kG ? i * NG / kG : (i < NG ? i : NG - 1)) == gi) pp.template issue_piece<C + DEPTH, i>();
-            });
-        }
-        // fragment reads kPre MFMAs ahead: the rest of this chunk, then the opening fragments of chunk C+1
-        static_for<s1 - s0>([&](auto j_c) VDN_INL {
-            constexpr int s = s0 + decltype(j_c)::value;
-            if constexpr (s + PF < NS) fr[s + PF] = wa[(s + PF) * 64];
-            else if constexpr (HAS_NEXT && s + PF - NS < PFN) pp.fr[s + PF - NS] = wn[(s + PF - NS) * 64];
-            // a chunk shorter than the next one's opening: its last MFMA slot reads the remainder
-            if constexpr (HAS_NEXT && s == NS - 1)
-                static_for<(PFN > PF ? PFN - PF : 0)>([&](auto e_c) VDN_INL { pp.fr[PF + decltype(e_c)::value] = wn[(PF + decltype(e_c)::value) * 64]; });
-        });
-        if constexpr (gi == NG - 1 && HAS_NEXT && KTN > 0 && PG::bias_of(C + 1)) {
-            pp.load_bias(reinterpret_cast<const f32x4*>(pp.template slot<C + 1>() + KTN * 2048));
-        }
-        group(g_c, std::integral_constant<int, NG>{});
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    return acc;
-}
+    using Acc = AccT;
+    static constexpr int total = PG::total, kPre = sdf2::kPre, kGroup = sdf2::kGroup, abl = VDN_SDF2_ABL;
+    static constexpr int kt(int c) { return PG::kt_of(c); }
+    static constexpr bool bias(int c) { return PG::bias_of(c); }
+    // B2: with two spare ring slots the workgroup re-synchronises every SECOND step - the even step certifies chunks C+1 and C+2
+    // (the latter's DMA is one step old: an L2-warm piece lands in 250 - 400 cycles of the ~1 300 a step takes); the slot a step's
+    // DMA overwrites, that of chunk C-2, was last read in step C-2, which every wave had left at the latest barrier (C or C-1)
+    // (VDN_SDF2_B2 = 2: only for the chunks in front of the sweep - behind them one barrier per step again, with the spare slot idle;
+    // the change-over needs nothing: a step of the second kind certifies chunk C+1 by the ordinary count, whether or not the
+    // even step before it already did)
+    static constexpr bool b2(int c) { return VDN_SDF2_B2 != 0 && NSLOT >= DEPTH + 2 && (VDN_SDF2_B2 != 2 || c < PG::first_chunk(PG::NL < 9 ? PG::NL : 9)); }
+    static constexpr bool certifies(int c) { return !b2(c) || c % 2 == 0; }
+    static constexpr int wait(int c) { return b2(c) ? wait_count_b2<MODE, SAVE>(c) : wait_count<MODE, SAVE, DEPTH>(c); }
+    static constexpr bool dma_burst(int c) { return sdf2::dma_burst<MODE, SAVE>(c); }
+};
 
 #ifndef VDN_SDF2_SP
 #define VDN_SDF2_SP 1   // softplus form: 0 = max(t,0) + log2(1 + 2^-|t|), sigma from 2^-g;  1 = med3(log2(1 + 2^t), t, 25), sigma from 1 / (1 + 2^t)
@@ -465,20 +326,14 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     constexpr bool COL = MODE >= 2;                 // the colour head follows the sweep
     using P = BF16;
     using ST = unsigned short;
-    static_assert(NSLOT >= DEPTH + 1, "ring: the chunk being read, the one being opened and DEPTH-1 in flight");
     constexpr int kRing = NSLOT * kStride;
     constexpr int kW8 = 0;                             // (W8 row 0 rides in every chunk's tail: kTail)
     constexpr int kLdsTotal = MODE >= 1 ? 160 * 1024 : kRing + kW8;
     constexpr int NLDS = MODE >= 1 ? ((kLdsTotal - kRing - kW8) / (kWaves * 1024) < kSTiles ? (kLdsTotal - kRing - kW8) / (kWaves * 1024) : kSTiles) : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    Pipe<NSLOT, MODE >= 2 ? PG::sdf_total : (1 << 30)> pp;
-    pp.g = a.blob;
-    pp.g2 = ex.color_blob;
-    pp.lds = smem;
-    pp.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    pp.lane = threadIdx.x & 63;
-    pp.lane16 = pp.lane * 16;
-    pp.init_dma();
+    using PL = StepPolicy<MODE, SAVE, NSLOT, DEPTH>;
+    cstream::Pipe<kWaves, kStride, NSLOT, DEPTH, MODE >= 2 ? PG::sdf_total : cstream::kNoSplit, kPre> pp;     // (MODE >= 2: the colour head's stream follows)
+    pp.init(a.blob, smem, ex.color_blob);
     const int lane = pp.lane, c = lane & 31, h = lane >> 5;
     const WorkRow wr = work_row(a.active_idx, a.n_active, a.P, kWaves, pp.wave, c);
     if (wr.none) return;
@@ -547,7 +402,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     // the input loads above have to be back first: the compiler waits for them with vmcnt(0), which would also wait for younger
     // warm-up loads; behind this wait the stream arrives in L2 while the encoding below is computed from registers
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    char* const wdump = smem + pp.wave * (VDN_SDF2_DMA_IMM ? kG * 1024 : 1024);       // (this wave's own first DMA piece of ring slot 0: vdn_common.h)
+    char* const wdump = pp.warm_dump();
     warm_l2_issue(a.blob, ex.warm_bytes, wr.n_wg, MODE == 0 ? 512 : 256, wdump);
     warm_l2_issue(COL ? ex.color_blob : nullptr, COL ? ex.warm_bytes2 : 0, wr.n_wg, 256, wdump);
     // (and the kernel's own code: vdn_common.h; MODE 2 is the inference launch and is never cold)
@@ -606,14 +461,8 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
         pe7[0] = X.r[0]; pe7[1] = X.r[1];
         X.r[16] = X.r[2]; X.r[17] = X.r[3];
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the ordinary loads and stores above: nothing but DMA and counted stores from here on
-    // ring start (behind the PE stores, so that nothing but counted operations is younger than a DMA): W8 row 0 into its
-    // fixed place (wave 0), chunks 0 .. DEPTH-1 in flight, chunk 0 certified, its opening fragments read
-    static_for<DEPTH>([&](auto i_c) VDN_INL { pp.template issue<decltype(i_c)::value>(); });
-    wait_vmcnt<(DEPTH - 1) * kG>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    pp.template prefetch<0, 2, true>();
+    // ring start, behind the PE stores: it drains the ordinary loads and stores above - nothing but DMA and counted stores from here on
+    pp.template start<PL>();
 
     AccT acc_prev;              // accumulator of the previous chunk's tile (its epilogue runs under this chunk's MFMAs)
     u32x4 sq_prev;              // 255 sigma of the previous chunk's tile: read by the sweep's epilogue, built by a hidden layer's
@@ -856,7 +705,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
             u32x4 sq_next;
             if constexpr (sweep_tile) sq_next = SS.template get<PG::s_tile0(L.l) + T>();
             const auto& Xin = L.kind == COL0 ? F : ((LI & 1) ? Y : X);
-            const AccT acc_cur = chunk_step<MODE, SAVE, NSLOT, DEPTH, C>(pp, Xin, [&](auto g_c, auto) VDN_INL {
+            const AccT acc_cur = cstream::chunk_step<PL, C>(pp, Xin, [&](auto g_c, auto) VDN_INL {
                 constexpr int gi = decltype(g_c)::value;
                 epilogue(std::integral_constant<int, CP>{}, std::integral_constant<int, pair_begin(gi, GA)>{},
                          std::integral_constant<int, pair_begin(gi + 1, GA)>{});
