@@ -956,6 +956,90 @@ typedef struct {
 int vdn_mesh_filter_mark(const VdnMeshFilterArgs* args_host, void* stream);
 int vdn_mesh_filter_remap(const VdnMeshFilterArgs* args_host, void* stream);
 
+/* ---- mesh cleaning: ray casting against the mesh on a uniform grid (csrc/mesh_ray.hip; vdn_hip/mesh.py: MeshGrid) ---------------
+ * The grid is dense over the bounding box of the referenced, finite vertices: nx * ny * nz cubic cells of edge h from
+ * (lo_x, lo_y, lo_z), cell id (z * ny + y) * nx + x, the coordinate of a point floor((p - lo) / h) in double, clamped into the grid.
+ * A triangle is REFERENCED unless a corner is not finite, two corner indices are equal or its area (vdn_tri_area's expression) is
+ * 0; it is referenced from every cell its axis-aligned box, grown by `margin` on all sides, overlaps. Two passes around the
+ * exclusive prefix sum over cells the caller makes:
+ *   vdn_ray_bin_count: one thread per triangle: cell_count[c] += 1 (integer atomics; the caller zeroes cell_count first) for each
+ *                      overlapped cell, and the triangle's packed record {a, b, c as 9 fp32, the 3 corner indices as int32 bits}
+ *                      (zeros for a triangle that is not referenced). A corner index outside [0, V) sets *error = 1 (the caller
+ *                      zeroes it first) and the triangle is not referenced: nothing is read or written out of bounds.
+ *   vdn_ray_bin_fill:  the same walk; refs[cursor[c]++] = f (integer atomics on `cursor`, which the caller initialises to the
+ *                      exclusive prefix sum of cell_count): the order of the references inside a cell is unspecified, and no
+ *                      result below depends on it.
+ *   vdn_ray_cast:      one lane per ray o + t d, o and d in double. The ray-triangle test is two-sided Moller-Trumbore in double
+ *                      on the widened fp32 corners a, b, c, every product and sum rounded on its own (no fused multiply-add), sums
+ *                      left to right:
+ *                          e1 = b - a, e2 = c - a, p = d x e2 = (d1 e2_2 - d2 e2_1, d2 e2_0 - d0 e2_2, d0 e2_1 - d1 e2_0),
+ *                          det = e1_0 p0 + e1_1 p1 + e1_2 p2; no hit when det == 0 or det is not finite; inv = 1 / det,
+ *                          s = o - a, u = (s0 p0 + s1 p1 + s2 p2) inv, q = s x e1 (the pattern of p),
+ *                          v = (d0 q0 + d1 q1 + d2 q2) inv, t = (e2_0 q0 + e2_1 q1 + e2_2 q2) inv;
+ *                          a hit iff u >= 0, v >= 0, u + v <= 1 and t_min < t < t_max (NaN fails every comparison).
+ *                      One (ray, triangle) pair therefore gives one t, whichever cell it is found through. Closest hit: the
+ *                      smallest t, the lower face index on equal t - independent of the reference order, the thread order and h.
+ *                      t[r] = +inf, face[r] = -1 on a miss. any_hit != 0: the walk ends at the first accepted hit; only
+ *                      face[r] >= 0 is specified then. skip_vertex[r] (optional): triangles with that corner index are ignored.
+ *                      tests[r] (optional) = ray-triangle tests made. Traversal: the segment is clipped to the grid's box grown
+ *                      by `margin` (slabs, in double), then a 3-D DDA from the entry cell; the exit parameter of a cell on axis k
+ *                      is (lo_k + (i_k + 1 or 0) h - o_k) (1 / d_k), computed from the cell index, not accumulated. After the
+ *                      references of a cell are tested the walk ends when the best t <= the cell's exit parameter, when the
+ *                      exit parameter reaches the clipped segment's end, or when the next cell is outside the grid; it takes at
+ *                      most nx + ny + nz + 3 steps by the loop's own counter. A miss, decided before the loop: an origin or
+ *                      direction that is not finite, a direction with no component whose reciprocal is finite (zero), a window
+ *                      that is empty or NaN, no overlap with the box. An axis with such a component is never crossed.
+ *   vdn_visibility_votes: one lane per (camera n, vertex x), camera-major, integer atomic adds into the two counts (the caller
+ *                      zeroes them). "In image" is vdn_mask_votes' rule (one device function for both); a vertex in image of n
+ *                      is visible from it iff no triangle without x as a corner is hit by centres[n] + t (x - centres[n]),
+ *                      0 < t < 1 - eps (any-hit walk, skip_vertex = x's index).
+ * Status -10: V, F, R, n_refs or the cell count do not fit 32-bit indexing. */
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes) */
+    int32_t* cell_count;           /* [nx*ny*nz] in / out   (count) */
+    int32_t* cursor;               /* [nx*ny*nz] in / out   (fill) */
+    int32_t* refs;                 /* [n_refs] out   (fill) */
+    float* records;                /* [F][12] out   (count) */
+    int32_t* error;                /* [1]   (count) */
+    int64_t V, F, n_refs;          /* n_refs = sum of cell_count   (fill) */
+    double lo_x, lo_y, lo_z, h, margin;
+    int32_t nx, ny, nz, index_bytes;
+} VdnRayGridArgs;
+int vdn_ray_bin_count(const VdnRayGridArgs* args_host, void* stream);
+int vdn_ray_bin_fill(const VdnRayGridArgs* args_host, void* stream);
+
+typedef struct {
+    const double* origins;         /* [R][3] */
+    const double* directions;      /* [R][3] */
+    const int64_t* skip_vertex;    /* [R] or NULL */
+    const float* records;          /* [F][12] */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1] */
+    const int32_t* refs;           /* [n_refs] */
+    double* t;                     /* [R] out */
+    int64_t* face;                 /* [R] out */
+    int32_t* tests;                /* [R] out or NULL */
+    int64_t R, F, n_refs;
+    double lo_x, lo_y, lo_z, h, margin, t_min, t_max;
+    int32_t nx, ny, nz, any_hit;
+} VdnRayCastArgs;
+int vdn_ray_cast(const VdnRayCastArgs* args_host, void* stream);
+
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const double* P;               /* [N][3][4] row-major */
+    const double* centres;         /* [N][3] camera centres, -M^-1 p4 */
+    const float* records;          /* [F][12] */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1] */
+    const int32_t* refs;           /* [n_refs] */
+    int32_t* n_in_image;           /* [V] in / out */
+    int32_t* n_visible;            /* [V] in / out */
+    int64_t V, N, F, n_refs;
+    double lo_x, lo_y, lo_z, h, margin, eps;
+    int32_t nx, ny, nz, H, W, _pad;
+} VdnVisibilityArgs;
+int vdn_visibility_votes(const VdnVisibilityArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

@@ -7,6 +7,7 @@
 #include <climits>
 #include "vdn_render.h"
 #include "k_tri.h"
+#include "k_project.h"
 
 namespace vdn {
 
@@ -102,15 +103,10 @@ __global__ void mask_votes_kernel(VdnMaskVotesArgs a) {
         const double x = (double)a.vertices[v * 3 + 0], y = (double)a.vertices[v * 3 + 1], z = (double)a.vertices[v * 3 + 2];
         int n_img = 0, n_msk = 0;
         for (long n = 0; n < (long)a.N; ++n) {
-            const double* P = a.P + n * 12;                  // (uniform over the wave: scalar loads)
-            const double uw = P[0] * x + P[1] * y + P[2] * z + P[3], vw = P[4] * x + P[5] * y + P[6] * z + P[7],
-                         w = P[8] * x + P[9] * y + P[10] * z + P[11];
-            if (!(w > 0.0)) continue;
-            const double px = floor(uw / w + 0.5), py = floor(vw / w + 0.5);
-            // (NaN and +-inf fail the range test: the comparisons are made in double, before any conversion to an integer)
-            if (!(px >= 0.0 && px < (double)a.W && py >= 0.0 && py < (double)a.H)) continue;
+            long px, py;                                     // (P is uniform over the wave: scalar loads)
+            if (!project_in_image(a.P + n * 12, x, y, z, a.H, a.W, &px, &py)) continue;
             ++n_img;
-            n_msk += a.masks[(n * a.H + (long)py) * a.W + (long)px] != 0 ? 1 : 0;
+            n_msk += a.masks[(n * a.H + py) * a.W + px] != 0 ? 1 : 0;
         }
         a.n_in_image[v] = n_img;
         a.n_in_mask[v] = n_msk;

@@ -9,7 +9,11 @@ shade_points evaluates the networks at free-standing surface points - the vertex
 
 Mesh cleaning (csrc/mesh_clean.hip; the policy on top is vdn_train/mesh_clean.py): connected_components / component_table label
 the pieces of a mesh, dilate_masks / mask_votes count in how many object masks a vertex falls, filter_mesh drops faces and
-vertices and renumbers the rest."""
+vertices and renumbers the rest.
+
+Ray casting (csrc/mesh_ray.hip): MeshGrid references the triangles from a uniform grid and casts rays against them (closest hit
+or any hit, two-sided Moller-Trumbore in double); visibility_votes counts the cameras that see each vertex unoccluded."""
+import math
 import os
 
 import numpy as np
@@ -315,6 +319,193 @@ def filter_mesh(vertices, triangles, keep_vertices=None, keep_faces=None, drop_u
             a.face_offsets, a.vertex_new, a.out_triangles, a.F_out = f_off.data_ptr(), v_new.data_ptr(), out_t.data_ptr(), n_alive
             _call_sized("vdn_mesh_filter_remap", a, st)
     return vertices[vertex_index], out_t, vertex_index
+
+
+# ---- ray casting against the mesh (csrc/mesh_ray.hip) ---------------------------------------------------------------------------------
+# default cell edge, in units of the mean triangle extent (the longest side of a triangle's own box): a marching-cubes triangle
+# then overlaps about (1 + 1/2)^3 = 3.4 cells and a ray takes half as many steps as at one extent per cell. An expectation, not a
+# measurement.
+RAY_CELL_FACTOR = 2.0
+# the grown boxes' margin, in units of (largest |coordinate| of the box + largest extent + h): 2^-32, i.e. 2^21 ulps of fp64 -
+# DESIGN.md 3m has the argument
+RAY_MARGIN = 2.0 ** -32
+
+
+class MeshGrid:
+    """The triangles of a mesh referenced from a dense uniform grid over the bounding box of its referenced, finite vertices
+    (vdn_ray_bin_count / vdn_ray_bin_fill, include/vdn_render.h), for `cast`. vertices [V,3] CUDA float (taken as fp32), triangles
+    [F,3] CUDA int64 or int32. A triangle with a non-finite corner, a repeated corner index or zero area is never referenced; F = 0
+    is legal (every ray misses). cell_size: the cells' edge - default RAY_CELL_FACTOR * the mean triangle extent - raised by steps
+    of 1.25 until the grid has at most max_cells cells; it changes the speed only, never a result. ValueError on CPU tensors, wrong
+    shapes or dtypes, a corner index outside [0, V) (found on the device), or more than max_refs references (checked after the
+    count pass, before the list is allocated: one huge triangle over a fine grid)."""
+
+    def __init__(self, vertices, triangles, cell_size=None, max_cells=1 << 22, max_refs=1 << 27):
+        _check_triangles("MeshGrid", triangles)
+        _check_vertices("MeshGrid", vertices, triangles)
+        if max_cells < 1 or max_refs < 1:
+            raise ValueError("max_cells and max_refs must be at least 1")
+        if cell_size is not None and not (float(cell_size) > 0.0 and float(cell_size) < float("inf")):
+            raise ValueError("cell_size must be positive and finite, got %r" % (cell_size,))
+        dev = vertices.device
+        v, t = vertices.detach().float().contiguous(), triangles.contiguous()
+        V, F = v.shape[0], t.shape[0]
+        if V >= 1 << 31 or F >= 1 << 31:
+            raise ValueError("MeshGrid: the sizes do not fit 32-bit indexing")
+        if F > 0 and V == 0:
+            raise ValueError("a triangle refers to a vertex outside [0, 0)")
+        self.device, self.V, self.F = dev, V, F
+        lo, hi, mean_extent = [0.0] * 3, [0.0] * 3, 0.0
+        with torch.cuda.device(dev):
+            if F > 0:
+                # the box and the mean extent over the triangles whose corners are in range and finite (gathered at safe indices)
+                tl = t.long()
+                ok = ((tl >= 0) & (tl < V)).all(dim=1)
+                p = v[torch.where(ok[:, None], tl, torch.zeros_like(tl))]
+                ok &= torch.isfinite(p).all(dim=2).all(dim=1)
+                inf = torch.full((1, 3), float("inf"), device=dev)
+                bmin, bmax = torch.where(ok[:, None], p.amin(dim=1), inf), torch.where(ok[:, None], p.amax(dim=1), -inf)
+                n_ok = ok.sum()
+                ext = torch.where(ok, (bmax - bmin).amax(dim=1), torch.zeros((), device=dev)).double().sum() / n_ok.clamp_min(1)
+                stats = torch.cat([bmin.amin(dim=0).double(), bmax.amax(dim=0).double(), ext[None], n_ok[None].double()]).tolist()   # one host read
+                if stats[7] > 0:
+                    lo, hi, mean_extent = stats[0:3], stats[3:6], stats[6]
+            extent = [b - a for a, b in zip(lo, hi)]
+            L = max(extent)
+            h = float(cell_size) if cell_size is not None else RAY_CELL_FACTOR * mean_extent
+            if not (h > 0.0 and math.isfinite(h)):
+                h = L if L > 0.0 else 1.0                          # (no triangle with an extent: one cell)
+            dims = lambda s: [int(math.floor(e / s)) + 1 for e in extent]
+            while np.prod(dims(h), dtype=object) > max_cells:
+                h *= 1.25
+            self.lo, self.h, self.dims = [float(x) for x in lo], h, dims(h)
+            self.n_cells = int(np.prod(self.dims, dtype=object))
+            self.margin = RAY_MARGIN * (max(abs(x) for x in lo + hi) + L + h)
+            self.records = torch.empty(max(F, 1), 12, dtype=torch.float32, device=dev)
+            count = torch.zeros(self.n_cells, dtype=torch.int32, device=dev)
+            self.cell_start = torch.zeros(self.n_cells + 1, dtype=torch.int32, device=dev)
+            self.n_refs = 0
+            if F > 0:
+                st = lib.stream_handle()
+                err = torch.zeros(1, dtype=torch.int32, device=dev)
+                a = self._geometry(lib.VdnRayGridArgs())
+                a.vertices, a.triangles, a.V, a.F, a.index_bytes = v.data_ptr(), t.data_ptr(), V, F, t.element_size()
+                a.cell_count, a.records, a.error = count.data_ptr(), self.records.data_ptr(), err.data_ptr()
+                _call_sized("vdn_ray_bin_count", a, st)
+                incl = torch.cumsum(count, 0, dtype=torch.int64)
+                n_refs, bad = torch.stack([incl[-1], err[0].long()]).tolist()         # one host read: the list's size and the error flag
+                if bad:
+                    raise ValueError("a triangle refers to a vertex outside [0, %d)" % V)
+                if n_refs > max_refs or n_refs >= 1 << 31:
+                    raise ValueError("a cell size of %g gives %d triangle references, more than max_refs = %d (or than 32-bit indexing holds)"
+                                     % (h, n_refs, max_refs))
+                self.n_refs = int(n_refs)
+                self.cell_start[1:] = incl.to(torch.int32)
+            self.refs = torch.empty(max(self.n_refs, 1), dtype=torch.int32, device=dev)
+            if self.n_refs > 0:
+                cursor = self.cell_start[:-1].clone()
+                a.cursor, a.refs, a.n_refs = cursor.data_ptr(), self.refs.data_ptr(), self.n_refs
+                _call_sized("vdn_ray_bin_fill", a, st)
+        self.nbytes = sum(x.numel() * x.element_size() for x in (self.records, self.cell_start, self.refs))
+
+    def _geometry(self, a):
+        """the grid's tables and geometry into an argument block (the fields every block of csrc/mesh_ray.hip names alike)"""
+        a.lo_x, a.lo_y, a.lo_z, a.h, a.margin = self.lo[0], self.lo[1], self.lo[2], self.h, self.margin
+        a.nx, a.ny, a.nz = self.dims
+        if hasattr(a, "cell_start"):
+            a.records, a.cell_start, a.refs = self.records.data_ptr(), self.cell_start.data_ptr(), self.refs.data_ptr()
+            a.F, a.n_refs = self.F, self.n_refs
+        return a
+
+    def _rays(self, x, what):
+        x = torch.as_tensor(x)
+        if x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
+            raise ValueError("%s must be a float [R,3] array, got %s %s" % (what, x.dtype, tuple(x.shape)))
+        return x.detach().to(device=self.device, dtype=torch.float64).contiguous()
+
+    def cast(self, origins, directions, t_min=0.0, t_max=float("inf"), any_hit=False, skip_vertex=None, return_tests=False):
+        """Rays origins[r] + t directions[r] ([R,3], taken as float64) against the mesh -> (t [R] float64, face [R] int64): the
+        closest hit with t_min < t < t_max, the lower face index on equal t; +inf and -1 on a miss (vdn_ray_cast: two-sided
+        Moller-Trumbore in double, bit-identical between calls and across cell sizes). any_hit: stop at the first hit found -
+        only face >= 0 means anything then. skip_vertex [R] integers (optional): the triangles with that vertex as a corner are
+        ignored for that ray. return_tests adds tests [R] int32, the ray-triangle tests made per ray. Rays that are not finite,
+        have no direction or an empty window miss. Pass the rays in a coherent order: a wave is as slow as its longest walk."""
+        o, d = self._rays(origins, "origins"), self._rays(directions, "directions")
+        if o.shape != d.shape:
+            raise ValueError("origins and directions must have one shape, got %s and %s" % (tuple(o.shape), tuple(d.shape)))
+        R, dev = o.shape[0], self.device
+        skip = None
+        if skip_vertex is not None:
+            skip = torch.as_tensor(skip_vertex)
+            if skip.shape != (R,) or skip.is_floating_point() or skip.dtype == torch.bool:
+                raise ValueError("skip_vertex must be an integer [%d] array" % R)
+            skip = skip.to(device=dev, dtype=torch.int64).contiguous()
+        t = torch.full((R,), float("inf"), dtype=torch.float64, device=dev)
+        face = torch.full((R,), -1, dtype=torch.int64, device=dev)
+        tests = torch.zeros(R, dtype=torch.int32, device=dev) if return_tests else None
+        if R > 0:
+            a = self._geometry(lib.VdnRayCastArgs())
+            a.origins, a.directions, a.skip_vertex = o.data_ptr(), d.data_ptr(), (None if skip is None else skip.data_ptr())
+            a.t, a.face, a.tests, a.R = t.data_ptr(), face.data_ptr(), (tests.data_ptr() if return_tests else None), R
+            a.t_min, a.t_max, a.any_hit = float(t_min), float(t_max), 1 if any_hit else 0
+            with torch.cuda.device(dev):
+                _call_sized("vdn_ray_cast", a, lib.stream_handle())
+        return (t, face, tests) if return_tests else (t, face)
+
+
+def camera_centres(P):
+    """P float [N,3,4] = [M | p4] -> centres float64 [N,3] numpy, c = -M^-1 p4 (the point every ray of the camera passes through),
+    on the host. ValueError when an M is singular."""
+    P = np.asarray(P.detach().cpu() if torch.is_tensor(P) else P, dtype=np.float64)
+    if P.ndim != 3 or P.shape[1:] != (3, 4):
+        raise ValueError("P must be a float [N,3,4] array, got %s" % (P.shape,))
+    c = np.empty((P.shape[0], 3))
+    for n in range(P.shape[0]):
+        M = P[n, :, :3]
+        # (rank by the singular values: a determinant's size says nothing about a matrix in pixels x metres)
+        if not np.isfinite(P[n]).all() or np.linalg.matrix_rank(M) < 3:
+            raise ValueError("camera %d has a singular 3 x 3 block: it has no centre" % n)
+        c[n] = -np.linalg.solve(M, P[n, :, 3])
+    return c
+
+
+def visibility_votes(vertices, triangles, P, image_size, eps=1e-4, grid=None):
+    """vertices [V,3] CUDA float, triangles [F,3] CUDA int64 or int32, P [N,3,4] float64 (as mask_votes takes it), image_size
+    (H, W) -> (n_in_image [V] int32, n_visible [V] int32) (vdn_visibility_votes): the cameras a vertex projects into - mask_votes'
+    rule - and those of them that see it: no triangle without the vertex as a corner is hit by the segment from the camera's
+    centre c to the vertex x, c + t (x - c) with 0 < t < 1 - eps. eps keeps a position-duplicated, unwelded vertex of a foreign
+    PLY (and the triangles around it) from hiding its twin; 1e-4 is an interface default, not a measurement. fp64 Moller-Trumbore
+    has no watertight edge rule: a segment can in principle pass between two triangles along their shared edge, which adds one
+    vote. grid: a MeshGrid of the same mesh (built here when None)."""
+    _check_triangles("visibility_votes", triangles)
+    _check_vertices("visibility_votes", vertices, triangles)
+    try:
+        H, W = (int(x) for x in image_size)
+    except (TypeError, ValueError):
+        raise ValueError("image_size must be (H, W), got %r" % (image_size,))
+    if H < 1 or W < 1:
+        raise ValueError("image_size must be positive, got %r" % (image_size,))
+    if not (0.0 <= float(eps) < 1.0):
+        raise ValueError("eps must be in [0, 1), got %r" % (eps,))
+    centres = camera_centres(P)
+    dev = vertices.device
+    if grid is None:
+        grid = MeshGrid(vertices, triangles)
+    if not isinstance(grid, MeshGrid) or grid.device != dev or (grid.V, grid.F) != (vertices.shape[0], triangles.shape[0]):
+        raise ValueError("grid must be a MeshGrid of this mesh")
+    v = vertices.detach().float().contiguous()
+    Pd = torch.as_tensor(P).detach().to(device=dev, dtype=torch.float64).contiguous()
+    cd = torch.from_numpy(centres).to(dev)
+    V, N = v.shape[0], Pd.shape[0]
+    n_img, n_vis = torch.zeros(V, dtype=torch.int32, device=dev), torch.zeros(V, dtype=torch.int32, device=dev)
+    if V == 0 or N == 0:
+        return n_img, n_vis
+    a = grid._geometry(lib.VdnVisibilityArgs())
+    a.vertices, a.P, a.centres, a.n_in_image, a.n_visible = v.data_ptr(), Pd.data_ptr(), cd.data_ptr(), n_img.data_ptr(), n_vis.data_ptr()
+    a.V, a.N, a.H, a.W, a.eps = V, N, H, W, float(eps)
+    with torch.cuda.device(dev):
+        _call_sized("vdn_visibility_votes", a, lib.stream_handle())
+    return n_img, n_vis
 
 
 def fused_point_shading(renderer):

@@ -3,8 +3,12 @@ project outside the (dilated) object masks, then keep the largest connected piec
 and cv.dilate on the host; here the labelling, the dilation, the votes and the compaction are kernels: vdn_hip/mesh.py,
 csrc/mesh_clean.hip; INTEGRATION.md "Mesh cleaning").
 
+A third, optional stage drops what no camera sees: an SDF network closes its surface where nothing looked (the underside of an
+object on a table, the inside of a cavity), that geometry is attached to the real surface and projects inside the masks, and a scan
+cannot contain it. The occlusion queries are rays against the mesh itself (vdn_hip.mesh.visibility_votes, csrc/mesh_ray.hip).
+
 select_components is the policy on a component table, plain arithmetic that runs anywhere; vote_keep is the rule on the mask
-votes; clean_mesh strings the stages together and reports what each removed."""
+votes, visible_keep the rule on the visibility votes; clean_mesh strings the stages together and reports what each removed."""
 import numpy as np
 import torch
 
@@ -49,6 +53,45 @@ def vote_keep(n_in_image, n_in_mask, min_inside=1, max_outside=0):
     return (n_in_mask >= int(min_inside)) & ((n_in_image - n_in_mask) <= int(max_outside))
 
 
+def visible_keep(n_visible, min_visible=1):
+    """The rule on vdn_hip.mesh.visibility_votes' count (a tensor or numpy): a vertex stays iff at least `min_visible` cameras see
+    it unoccluded."""
+    if min_visible < 0:
+        raise ValueError("min_visible must be >= 0, got %r" % (min_visible,))
+    return n_visible >= int(min_visible)
+
+
+VISIBILITY_DEFAULTS = {"min_visible": 1, "eps": 1e-4, "cell_size": None}
+
+
+def _visibility_options(visibility):
+    """clean_mesh's `visibility` dict with its defaults filled in; ValueError on anything else"""
+    if not isinstance(visibility, dict):
+        raise ValueError("visibility must be None or a dict with the keys %s, got %r" % (sorted(VISIBILITY_DEFAULTS), visibility))
+    unknown = sorted(set(visibility) - set(VISIBILITY_DEFAULTS))
+    if unknown:
+        raise ValueError("visibility has unknown keys %s (known: %s)" % (unknown, sorted(VISIBILITY_DEFAULTS)))
+    opt = dict(VISIBILITY_DEFAULTS, **visibility)
+    if int(opt["min_visible"]) != opt["min_visible"]:
+        raise ValueError("min_visible must be an integer, got %r" % (opt["min_visible"],))
+    visible_keep(0, opt["min_visible"])
+    if not (0.0 <= float(opt["eps"]) < 1.0):
+        raise ValueError("visibility eps must be in [0, 1), got %r" % (opt["eps"],))
+    if opt["cell_size"] is not None and not (0.0 < float(opt["cell_size"]) < float("inf")):
+        raise ValueError("visibility cell_size must be positive and finite, got %r" % (opt["cell_size"],))
+    return opt
+
+
+def _image_size(image_size):
+    try:
+        H, W = (int(x) for x in image_size)
+    except (TypeError, ValueError):
+        raise ValueError("image_size must be (H, W), got %r" % (image_size,))
+    if H < 1 or W < 1:
+        raise ValueError("image_size must be positive, got %r" % (image_size,))
+    return H, W
+
+
 def masks_to_uint8(masks, device=None):
     """Object masks in any of the shapes a scene holds them -> uint8 [N,H,W] tensor, 1 = set: bool, integers (nonzero = set) or
     floats (> 0.5), [N,H,W] or [N,H,W,1|3] (channel 0 of a 3-channel mask: vdn_train.dataset.SceneData.masks)."""
@@ -70,19 +113,32 @@ def _device_of(*xs):
 
 
 def clean_mesh(vertices, triangles, *, keep="largest", by="faces", min_faces=0, min_area_fraction=0.0, cameras=None, masks=None,
-               dilate=0, min_inside=1, max_outside=0, attributes=()):
+               dilate=0, min_inside=1, max_outside=0, attributes=(), visibility=None, image_size=None):
     """vertices [V,3] float, triangles [F,3] integer (numpy arrays or CUDA tensors) -> dict(vertices, triangles, attributes,
     vertex_index, report), arrays of the inputs' kind and dtypes.
       1. with `cameras` (float64 [N,3,4], the mesh's frame -> (u w, v w, w): SceneData.projection_matrices) and `masks`
          ([N,H,W] or [N,H,W,1|3]; bool, integer nonzero = set, float > 0.5): masks dilated by the (2 dilate + 1)^2 square, votes
          per vertex, vote_keep(min_inside, max_outside); a face goes when one of its corners does;
       2. connected components of what is left, select_components(keep, by, min_faces, min_area_fraction); the faces of the
-         dropped components go.
+         dropped components go;
+      3. with `visibility` (None: the stage is off; or a dict with the keys min_visible (1), eps (1e-4) and cell_size (None: the
+         grid's default)): the visibility votes of `cameras` on the mesh that survived 1 and 2 - what was dropped casts no
+         shadow - and visible_keep(min_visible): a vertex no camera sees unoccluded goes, and a face with it. The stage needs
+         `cameras` but not `masks`; without masks, image_size = (H, W) says where the images end.
     Vertices no surviving face uses are dropped, the rest keep their order; vertex_index [V'] int64 holds their old indices and
     `attributes` (a sequence of [V,...] arrays: normals, colours) come back gathered by it. `report` is plain JSON data."""
     from vdn_hip import mesh
-    if (cameras is None) != (masks is None):
-        raise ValueError("cameras and masks go together: got only one of them")
+    if visibility is None:
+        if (cameras is None) != (masks is None):
+            raise ValueError("cameras and masks go together: got only one of them")
+    else:
+        visibility = _visibility_options(visibility)
+        if cameras is None:
+            raise ValueError("visibility culling needs `cameras`")
+        if masks is None and image_size is None:
+            raise ValueError("visibility culling without masks needs image_size = (H, W)")
+    if image_size is not None:
+        image_size = _image_size(image_size)
     select_components({"n_faces": np.zeros(0, np.int64), "area": np.zeros(0)}, keep, by, min_faces, min_area_fraction)   # argument errors first
     vote_keep(0, 0, min_inside, max_outside)
     if int(dilate) != dilate or dilate < 0:
@@ -108,10 +164,13 @@ def clean_mesh(vertices, triangles, *, keep="largest", by="faces", min_faces=0, 
     report = {"vertices_in": V0, "faces_in": F0, "components_in": int(torch.unique(mesh.connected_components(t, V0)).numel())}
     index = torch.arange(V0, device=dev)
 
-    if cameras is not None:
+    if masks is not None:
         m = masks_to_uint8(masks, dev)
         if dilate:
             m = mesh.dilate_masks(m, int(dilate))
+        if image_size is not None and tuple(m.shape[1:]) != image_size:
+            raise ValueError("image_size %s does not match the masks' %s" % (image_size, tuple(m.shape[1:])))
+        image_size = tuple(int(x) for x in m.shape[1:])
         n_img, n_msk = mesh.mask_votes(v, cameras, m)
         v, t, idx = mesh.filter_mesh(v, t, keep_vertices=vote_keep(n_img, n_msk, min_inside, max_outside))
         index = index[idx]
@@ -127,6 +186,16 @@ def clean_mesh(vertices, triangles, *, keep="largest", by="faces", min_faces=0, 
     report["components"] = {"keep": keep, "by": by, "min_faces": int(min_faces), "min_area_fraction": float(min_area_fraction),
                             "before": int(chosen.numel()), "after": int(chosen.sum()), "vertices_removed": V1 - v.shape[0],
                             "faces_removed": F1 - t.shape[0], "kept_area_fraction": kept / total if total > 0 else None}
+
+    if visibility is not None:
+        V2, F2 = v.shape[0], t.shape[0]
+        grid = mesh.MeshGrid(v, t, cell_size=visibility["cell_size"])
+        _, n_vis = mesh.visibility_votes(v, t, cameras, image_size, eps=visibility["eps"], grid=grid)
+        v, t, idx = mesh.filter_mesh(v, t, keep_vertices=visible_keep(n_vis, visibility["min_visible"]))
+        index = index[idx]
+        report["visibility_culling"] = {"cameras": int(len(cameras)), "min_visible": int(visibility["min_visible"]), "eps": float(visibility["eps"]),
+                                        "vertices_removed": V2 - v.shape[0], "faces_removed": F2 - t.shape[0],
+                                        "components_after": int(torch.unique(mesh.connected_components(t, v.shape[0])).numel())}
     report.update(vertices_out=int(v.shape[0]), faces_out=int(t.shape[0]))
 
     t = t.to(t_dtype)

@@ -188,11 +188,15 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
 def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, **kw):
     """validate_mesh for a vdn_train.dataset.SceneData: its object bounding box and scale_mats_np[0], the runner's file name
     meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711). A `clean` dict with a true "use_masks" entry gets
-    the scene's object-space cameras and its masks (cleaning happens in object space)."""
+    the scene's object-space cameras and its masks (cleaning happens in object space); a true "use_cameras" entry gets the cameras
+    and the image size without the masks - what a "visibility" entry needs (either of the two satisfies it)."""
     if clean is not None:
         clean = dict(clean)
-        if clean.pop("use_masks", False):
+        use_masks, use_cameras = clean.pop("use_masks", False), clean.pop("use_cameras", False)
+        if use_masks:
             clean.update(cameras=scene.projection_matrices(world_space=False), masks=scene.masks)
+        elif use_cameras:
+            clean.update(cameras=scene.projection_matrices(world_space=False), image_size=(int(scene.H), int(scene.W)))
     bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
     bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
     return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
