@@ -812,6 +812,63 @@ typedef struct {
 int vdn_mesh_mc_count(const VdnMeshMcArgs* args_host, void* stream);
 int vdn_mesh_mc_emit(const VdnMeshMcArgs* args_host, void* stream);
 
+/* ---- the same mesh from the cells near the surface only (csrc/mesh_sparse.hip; vdn_hip/mesh.py: marching_cubes_sparse) ---------
+ * The (R-1)^3 cells are cut into nb^3 bricks of brick^3 cells, nb = ceil((R-1) / brick), brick number (bi*nb + bj)*nb + bk; the last
+ * brick per axis may be partial. The caller chooses the ACTIVE bricks (one field value per brick against a Lipschitz
+ * bound), lists them in ascending brick number in `active` [A] and evaluates the field at their nodes only:
+ *   vdn_mesh_sparse_nodes: points[p - first][xyz] for first <= p < first + n_points, p = slot * E^3 + (a*E + b)*E + c with
+ *                          E = brick + 1: the world coordinates (X[.], Y[.], Z[.]) of lattice node (bi*brick + a, bj*brick + b,
+ *                          bk*brick + c) of brick active[slot], each index clamped to R - 1. X, Y, Z are the lattice's three
+ *                          coordinate vectors [R], so the floats are the dense lattice's.
+ * `values` [A][E][E][E] holds the field at those points. The cells of the active bricks are then triangulated as vdn_mesh_mc_*
+ * triangulates the full lattice. The per-cell arrays are COMPACT: a cell's slot is its rank among the active cells in ascending
+ * global cell number (i*(R-1) + j)*(R-1) + k - the dense visiting order with the skipped cells left out - so the caller's two
+ * exclusive prefix sums over the compact arrays are the dense offsets. The rank of cell (i, j, k) of active brick (bi, bj, bk) is
+ *   cell_base[brick] + (i - bi*brick) * row_cells[bi] + (j - bj*brick) * col_cells[bi*nb + bj] + (k - bk*brick)
+ * with col_cells[bi][bj] = active cells of one (i, j) column through brick column (bi, bj), row_cells[bi] = active cells of one
+ * i-plane through brick layer bi, cell_base = the active cells before the brick's first plane + before its first column in that
+ * plane + below it in its own column (the caller's prefix sums over the brick tables). brick_map [nb^3] = slot in `active` or -1.
+ *   vdn_mesh_sparse_count: cube_case / n_verts / n_tris at each active cell's rank, and *missed += 1 (the caller zeroes it) for
+ *                          every (active cell, cut edge of it, existing cell round that edge that lies in a dropped brick): there
+ *                          the surface leaves the evaluated region, i.e. the caller's bound does not hold.
+ *   vdn_mesh_sparse_emit:  vertices and triangles as vdn_mesh_mc_emit writes them; a triangle corner whose owner cell lies in a
+ *                          dropped brick (a missed edge) is left unwritten and nothing is read for it.
+ * A rank outside [0, n_cells), a vertex offset outside [0, V) or a triangle offset outside [0, F) is skipped, never dereferenced.
+ * Status -10: nb^3, A * (brick+1)^3 (and with it A * brick^3) do not fit 32-bit indexing, or brick > 1024. */
+typedef struct {
+    const float* X;                /* [R] */
+    const float* Y;                /* [R] */
+    const float* Z;                /* [R] */
+    const int32_t* active;         /* [A] brick numbers, ascending */
+    float* points;                 /* [n_points][3] */
+    int64_t first, n_points;       /* the range of p this call writes */
+    int32_t R, brick, nb, A;
+} VdnMeshSparseNodesArgs;
+int vdn_mesh_sparse_nodes(const VdnMeshSparseNodesArgs* args_host, void* stream);
+
+typedef struct {
+    const float* values;           /* [A][brick+1][brick+1][brick+1] */
+    double isovalue;
+    int32_t R, brick, nb, A;
+    const int32_t* active;         /* [A] */
+    const int32_t* brick_map;      /* [nb^3] */
+    const int32_t* cell_base;      /* [nb^3]  (read at active bricks only) */
+    const int32_t* col_cells;      /* [nb^2] */
+    const int32_t* row_cells;      /* [nb] */
+    int64_t n_cells;               /* active cells inside the lattice = the length of the compact arrays */
+    uint8_t* cube_case;            /* [n_cells]   written by the count pass, read by the emit pass */
+    int32_t* n_verts;              /* [n_cells]   (count pass) */
+    int32_t* n_tris;               /* [n_cells]   (count pass) */
+    int32_t* missed;               /* [1]         (count pass) */
+    const int64_t* vert_offsets;   /* [n_cells] exclusive prefix sum of n_verts   (emit pass) */
+    const int64_t* tri_offsets;    /* [n_cells] exclusive prefix sum of n_tris    (emit pass) */
+    int64_t V, F;                  /* the sums (emit pass) */
+    double* vertices;              /* [V][3] */
+    int64_t* triangles;            /* [F][3] */
+} VdnMeshSparseArgs;
+int vdn_mesh_sparse_count(const VdnMeshSparseArgs* args_host, void* stream);
+int vdn_mesh_sparse_emit(const VdnMeshSparseArgs* args_host, void* stream);
+
 /* ---- mesh evaluation: area-weighted surface samples of a triangle mesh (csrc/mesh_eval.hip; vdn_hip/mesh.py: sample_surface) ---
  * The sample set an accuracy / completeness / Chamfer figure against a scanned cloud is taken over (vdn_train/mesh_eval.py).
  * Deterministic, no random state. Two passes around an exclusive prefix sum the caller makes:

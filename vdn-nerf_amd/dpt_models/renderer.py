@@ -46,18 +46,63 @@ def extract_fields(bound_min, bound_max, resolution, query_func, device=None):
     return extract_fields_device(bound_min, bound_max, resolution, query_func, device).cpu().numpy()
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, method=None):
+def parse_sparse(sparse, method=None):
+    """The `sparse` argument of extract_geometry -> None (dense) or marching_cubes_sparse's keyword dict. None / False: the
+    environment decides - VDN_MESH_SPARSE unset, "" or "0": dense; "1": sparse with the defaults; "brick:lipschitz" (e.g. "8:2.5"):
+    those two. True: the defaults. A dict: keys from {"brick", "lipschitz", "chunk_points"}. ValueError on anything else, on
+    values vdn_hip.mesh.check_sparse_options declines, and on sparse together with method "tets". Touches no device."""
+    from vdn_hip import mesh
+    if sparse is None or sparse is False:
+        env = os.environ.get("VDN_MESH_SPARSE", "")
+        if env in ("", "0"):
+            return None
+        if env == "1":
+            opts = {}
+        else:
+            parts = env.split(":")
+            try:
+                if len(parts) != 2:
+                    raise ValueError
+                opts = {"brick": int(parts[0]), "lipschitz": float(parts[1])}
+            except ValueError:
+                raise ValueError("VDN_MESH_SPARSE must be 0, 1 or brick:lipschitz (e.g. 8:2.5), got %r" % (env,))
+    elif sparse is True:
+        opts = {}
+    elif isinstance(sparse, dict):
+        unknown = sorted(set(sparse) - set(mesh.SPARSE_KEYS))
+        if unknown:
+            raise ValueError("sparse has unknown keys %r (known: %r)" % (unknown, mesh.SPARSE_KEYS))
+        opts = dict(sparse)
+    else:
+        raise ValueError("sparse must be None, a bool or a dict, got %r" % (sparse,))
+    opts = dict(zip(mesh.SPARSE_KEYS, mesh.check_sparse_options(**opts)))
+    if (method or os.environ.get("VDN_MESH_METHOD", "cubes")) == "tets":
+        raise ValueError("sparse extraction is marching cubes only: method='tets' cannot be combined with it")
+    return opts
+
+
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, method=None, sparse=None):
     """renderer.py:33-41 -> (vertices [V,3] float64 in world coordinates, triangles [F,3]). The reference triangulates with
     `mcubes.marching_cubes(u, threshold)` (third-party PyMCubes): vdn_hip.mesh.marching_cubes extracts the same mesh on the
     device - the classic 256-case tables with the library's sequential vertex / triangle numbering, float64 vertices (restated
     from its published source in oracle/marching_cubes.py; the package itself is absent here). `method="tets"` (or
-    VDN_MESH_METHOD=tets): rounds 3-5's marching tetrahedra - the same level set, a finer, different triangulation."""
+    VDN_MESH_METHOD=tets): rounds 3-5's marching tetrahedra - the same level set, a finer, different triangulation.
+    `sparse` (not a reference argument; parse_sparse, or VDN_MESH_SPARSE): evaluate query_func only in the bricks near the surface
+    (vdn_hip.mesh.marching_cubes_sparse, DESIGN.md 3n) - the same two arrays as long as |grad f| stays below the `lipschitz` bound;
+    SparseExtractionError where the surface is seen to leave the evaluated bricks."""
     from vdn_hip import mesh
+    opts = parse_sparse(sparse, method)
     method = method or os.environ.get("VDN_MESH_METHOD", "cubes")
     if method not in ("cubes", "tets"):
         raise ValueError("method must be 'cubes' or 'tets', got %r" % (method,))
-    u = extract_fields_device(bound_min, bound_max, resolution, query_func)
-    vertices, triangles = mesh.marching_cubes(u, threshold) if method == "cubes" else mesh.marching_tets(u, threshold)
+    if opts is not None:
+        device = bound_min.device if torch.is_tensor(bound_min) and bound_min.is_cuda else torch.device("cuda")
+        # the dense lattice's own coordinate vectors (extract_fields_device), moved to the device as it moves its points
+        X, Y, Z = (torch.linspace(float(a), float(b), resolution).to(device) for a, b in zip(bound_min, bound_max))
+        vertices, triangles, _ = mesh.marching_cubes_sparse(query_func, X, Y, Z, threshold, **opts)
+    else:
+        u = extract_fields_device(bound_min, bound_max, resolution, query_func)
+        vertices, triangles = mesh.marching_cubes(u, threshold) if method == "cubes" else mesh.marching_tets(u, threshold)
     b_max_np = np.asarray([float(v) for v in bound_max])
     b_min_np = np.asarray([float(v) for v in bound_min])
     vertices = vertices.cpu().numpy().astype(np.float64) / (resolution - 1.0) * (b_max_np - b_min_np)[None, :] + b_min_np[None, :]
@@ -817,19 +862,20 @@ class NeuSRenderer:
     def extract_fields(self, bound_min, bound_max, resolution):
         return extract_fields(bound_min, bound_max, resolution, lambda pts: -self.sdf_network.sdf(pts))
 
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method=None):
-        """renderer.py:441-446. `method` (not a reference argument): "cubes" (default, PyMCubes' mesh) or "tets"."""
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method=None, sparse=None):
+        """renderer.py:441-446. `method` (not a reference argument): "cubes" (default, PyMCubes' mesh) or "tets". `sparse` (not a
+        reference argument): None / False, True or a dict - the module-level extract_geometry's brick-sparse mode."""
         return extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold,
-                                query_func=lambda pts: -self.sdf_network.sdf(pts), method=method)
+                                query_func=lambda pts: -self.sdf_network.sdf(pts), method=method, sparse=sparse)
 
-    def extract_colored_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method=None):
+    def extract_colored_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method=None, sparse=None):
         """extract_geometry plus the vertex attributes a mesh on disk wants (not in the reference, whose validate_mesh writes bare
         geometry): -> (vertices, triangles, normals [V,3] float32, colors [V,3] uint8 RGB). vertices / triangles are
         extract_geometry's own arrays, winding included. Each vertex (object space, cast to fp32) is shaded looking straight down
         its normal (vdn_hip.mesh.shade_points): normals = g / max(|g|, 1e-12) of the raw SDF gradient g, colors = the colour
         network's BGR output reversed and quantised as rint(clip(c, 0, 1) * 255)."""
         from vdn_hip import mesh
-        vertices, triangles = self.extract_geometry(bound_min, bound_max, resolution, threshold=threshold, method=method)
+        vertices, triangles = self.extract_geometry(bound_min, bound_max, resolution, threshold=threshold, method=method, sparse=sparse)
         dev = lib.first_param(self.sdf_network).device
         x = torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float32)).reshape(-1, 3).to(dev)
         if x.shape[0] == 0:

@@ -2,6 +2,8 @@
   marching_cubes  - vdn_mesh_mc_count / vdn_mesh_mc_emit: the classic 256-case marching cubes with PyMCubes' own vertex and
                     triangle numbering (include/vdn_render.h; the default of extract_geometry since round 6);
   marching_tets   - vdn_mesh_count / vdn_mesh_emit: marching tetrahedra on the Kuhn decomposition (rounds 3-5), kept as an option.
+  marching_cubes_sparse - vdn_mesh_sparse_*: marching_cubes' arrays from the bricks near the surface only; the field is given as a
+                    function and evaluated at those bricks' nodes, never on the full lattice (csrc/mesh_sparse.hip).
 The prefix sums (and the tetrahedra form's vertex welding) are torch ops on the device; nothing runs on the host.
 
 shade_points evaluates the networks at free-standing surface points - the vertex attributes of a mesh that goes to disk
@@ -82,6 +84,168 @@ def marching_cubes(u, threshold=0.0):
     a.vert_offsets, a.tri_offsets, a.vertices, a.triangles = vo.data_ptr(), to.data_ptr(), vertices.data_ptr(), triangles.data_ptr()
     lib.call("vdn_mesh_mc_emit", a, st)
     return vertices, triangles
+
+
+class SparseExtractionError(RuntimeError):
+    """marching_cubes_sparse found the surface leaving the bricks it evaluated: the Lipschitz bound does not hold for this field."""
+
+
+# The default bound on |grad f| that decides which bricks marching_cubes_sparse evaluates. A POLICY, not a measurement: the eikonal
+# term trains |grad f| of the SDF network towards 1, and 2 is a factor of two over that. A field steeper than the bound is caught
+# only where the surface leaves an evaluated brick (the missed-edge check); tools/time_mesh_extract.py records the largest
+# |grad f| it sees on the lattice nodes so that a reader can judge the margin.
+SPARSE_LIPSCHITZ = 2.0
+# A brick's radius is inflated by this relative slack, plus one fp32 ulp of the largest |coordinate| of the lattice, before the
+# test: the brick's midpoint is rounded to fp32 (at most half an ulp per axis) and the radius is computed from rounded nodes.
+SPARSE_RADIUS_SLACK = 1e-5
+SPARSE_KEYS = ("brick", "lipschitz", "chunk_points")
+
+
+def check_sparse_options(brick=8, lipschitz=SPARSE_LIPSCHITZ, chunk_points=1 << 22):
+    """-> (brick, lipschitz, chunk_points) as int, float, int; ValueError on brick < 1, lipschitz <= 0 or NaN (inf is legal: every
+    brick is evaluated), chunk_points < 1. Touches no device."""
+    try:
+        b, L, c = int(brick), float(lipschitz), int(chunk_points)
+    except (TypeError, ValueError):
+        raise ValueError("brick, lipschitz and chunk_points must be numbers, got %r, %r, %r" % (brick, lipschitz, chunk_points))
+    if b != brick or b < 1:
+        raise ValueError("brick must be an integer >= 1, got %r" % (brick,))
+    if not L > 0.0:                                          # (NaN fails every comparison)
+        raise ValueError("lipschitz must be positive (inf allowed), got %r" % (lipschitz,))
+    if c != chunk_points or c < 1:
+        raise ValueError("chunk_points must be an integer >= 1, got %r" % (chunk_points,))
+    return b, L, c
+
+
+def _query(query_func, pts, counter):
+    counter[0] += pts.shape[0]
+    val = query_func(pts)
+    if not (torch.is_tensor(val) and val.numel() == pts.shape[0]):
+        raise ValueError("query_func must return one value per point")
+    return val.reshape(-1).float()
+
+
+def marching_cubes_sparse(query_func, X, Y, Z, threshold=0.0, brick=8, lipschitz=SPARSE_LIPSCHITZ, chunk_points=1 << 22):
+    """marching_cubes(u, threshold) of the lattice u[i,j,k] = query_func((X[i], Y[j], Z[k])) without ever filling u ->
+    (vertices [V,3] float64 in lattice index coordinates, triangles [F,3] int64, stats). X, Y, Z: the lattice's coordinate
+    vectors, fp32 [R] CUDA tensors of one length (torch.linspace(lo, hi, R) per axis reproduces extract_fields_device's floats);
+    query_func maps [P,3] device points to P values, each row on its own (the same point must give the same bits in any batch).
+
+    The (R-1)^3 cells are cut into bricks of brick^3 cells (the last per axis may be partial; R - 1 < brick gives one brick).
+    Coarse pass: one evaluation per brick at the midpoint c of its closed node box; the brick is ACTIVE when
+    |f(c) - level| <= lipschitz * r, r = half the world-space diagonal of that box, in double, inflated by SPARSE_RADIUS_SLACK
+    (relative) plus one fp32 ulp of the largest |coordinate|. If |grad f| <= lipschitz inside a dropped brick, f keeps one sign on it
+    and none of its cells is cut. lipschitz = inf keeps every brick. Fine pass: the nodes of the active bricks, (brick+1)^3 per
+    brick (shared faces are evaluated once per brick), at most chunk_points per query_func call. The active cells are then
+    triangulated in ascending global cell number (csrc/mesh_sparse.hip), which makes the two arrays equal to marching_cubes' on
+    the dense lattice, element for element, whenever no dropped brick holds a cut cell.
+
+    stats = {"bricks", "active_bricks", "points_evaluated" (every point handed to query_func, coarse pass included),
+    "missed_edges"}. The check behind missed_edges: for every cut lattice edge of an active cell, every existing cell that contains
+    the edge must lie in an active brick. A violation means the surface leaves the evaluated region - the bound is too small for
+    this field - and raises SparseExtractionError. What it cannot see: a component of the surface that lies WHOLLY inside dropped
+    bricks (no active cell touches it); only a true bound excludes that.
+
+    Two host reads: the number of active bricks, then (V, F, missed). ValueError on CPU tensors, wrong shapes, bad options, or
+    sizes beyond 32-bit indexing (status -10 of the entry points)."""
+    brick, lipschitz, chunk_points = check_sparse_options(brick, lipschitz, chunk_points)
+    for name, t in (("X", X), ("Y", Y), ("Z", Z)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 1 and t.dtype == torch.float32):
+            raise ValueError("marching_cubes_sparse needs %s as an fp32 [R] CUDA tensor" % name)
+    if not (X.shape == Y.shape == Z.shape and X.device == Y.device == Z.device):
+        raise ValueError("X, Y and Z must have one length and one device")
+    R, dev = X.shape[0], X.device
+    if R < 2:
+        raise ValueError("lattice resolution must be at least 2")
+    X, Y, Z = X.contiguous(), Y.contiguous(), Z.contiguous()
+    n = R - 1
+    B = min(brick, n)                                        # (one brick when R - 1 < brick: its block is the lattice)
+    nb, E = -(-n // B), B + 1
+    if nb ** 3 >= 1 << 31:
+        raise ValueError("marching_cubes_sparse: the sizes do not fit 32-bit indexing")
+    level = float(torch.tensor(float(threshold), dtype=torch.float32).item())      # a C float, as marching_cubes takes it
+    counter = [0]
+    with torch.cuda.device(dev), torch.no_grad():
+        st = lib.stream_handle()
+        # ---- coarse pass: one value per brick against lipschitz * radius
+        lo_i = torch.arange(nb, device=dev) * B
+        hi_i = (lo_i + B).clamp_max(n)
+        ends = [(A[lo_i].double(), A[hi_i].double()) for A in (X, Y, Z)]
+        mid = [((a + b) * 0.5).float() for a, b in ends]
+        ext = [b - a for a, b in ends]
+        ulp = torch.stack([X.abs().max(), Y.abs().max(), Z.abs().max()]).max().double() * 2.0 ** -23
+        width = (hi_i - lo_i).to(torch.int64)                # cells per brick along one axis
+        active = torch.empty(nb ** 3, dtype=torch.bool, device=dev)
+        for s in range(0, nb ** 3, chunk_points):
+            b = torch.arange(s, min(s + chunk_points, nb ** 3), device=dev)
+            bi, bj, bk = b // (nb * nb), (b // nb) % nb, b % nb
+            f = _query(query_func, torch.stack([mid[0][bi], mid[1][bj], mid[2][bk]], dim=-1), counter)
+            r = 0.5 * torch.sqrt(ext[0][bi] ** 2 + ext[1][bj] ** 2 + ext[2][bk] ** 2)
+            # closed test, written so that a NaN value keeps its brick
+            active[s:s + b.numel()] = ~((f.double() - level).abs() > lipschitz * (r * (1.0 + SPARSE_RADIUS_SLACK) + ulp))
+        act = torch.nonzero(active).reshape(-1)              # host read 1: the number of active bricks
+        A = int(act.shape[0])
+        stats = {"bricks": nb ** 3, "active_bricks": A, "points_evaluated": counter[0], "missed_edges": 0}
+        vertices = torch.empty(0, 3, dtype=torch.float64, device=dev)
+        triangles = torch.empty(0, 3, dtype=torch.int64, device=dev)
+        if A == 0:
+            return vertices, triangles, stats
+        if A * E ** 3 >= 1 << 31:
+            raise ValueError("marching_cubes_sparse: %d active bricks of %d^3 nodes do not fit 32-bit indexing" % (A, E))
+        act32 = act.to(torch.int32)
+        # ---- fine pass: the nodes of the active bricks, in chunks
+        values = torch.empty(A * E ** 3, dtype=torch.float32, device=dev)
+        na = lib.VdnMeshSparseNodesArgs()
+        na.X, na.Y, na.Z, na.active = X.data_ptr(), Y.data_ptr(), Z.data_ptr(), act32.data_ptr()
+        na.R, na.brick, na.nb, na.A = R, B, nb, A
+        pts = torch.empty(min(chunk_points, A * E ** 3), 3, dtype=torch.float32, device=dev)
+        for s in range(0, A * E ** 3, chunk_points):
+            m = min(chunk_points, A * E ** 3 - s)
+            na.points, na.first, na.n_points = pts.data_ptr(), s, m
+            _call_sized("vdn_mesh_sparse_nodes", na, st)
+            values[s:s + m] = _query(query_func, pts[:m], counter)
+        del pts
+        stats["points_evaluated"] = counter[0]
+        # ---- the brick tables of the compact cell order (include/vdn_render.h: the rank formula)
+        act3 = active.reshape(nb, nb, nb).to(torch.int64)
+        zcells = act3 * width[None, None, :]                 # active cells of one (i, j) column inside each brick
+        col = zcells.sum(dim=2)                              # [nb, nb]  col_cells
+        colw = col * width[None, :]
+        row = colw.sum(dim=1)                                # [nb]      row_cells
+        roww = row * width
+        base = ((torch.cumsum(roww, 0) - roww)[:, None, None] + (torch.cumsum(colw, 1) - colw)[:, :, None] + (torch.cumsum(zcells, 2) - zcells))
+        # the compact arrays' length: exact when no brick is partial, else an upper bound whose unused tail stays zero (the true
+        # count is a device value; zeros add nothing to the prefix sums)
+        n_cells = A * B ** 3
+        brick_map = torch.full((nb ** 3,), -1, dtype=torch.int32, device=dev)
+        brick_map[act] = torch.arange(A, dtype=torch.int32, device=dev)
+        base32, col32, row32 = base.reshape(-1).to(torch.int32), col.reshape(-1).to(torch.int32), row.to(torch.int32)
+        case = torch.zeros(n_cells, dtype=torch.uint8, device=dev)
+        nv, nt = torch.zeros(n_cells, dtype=torch.int32, device=dev), torch.zeros(n_cells, dtype=torch.int32, device=dev)
+        missed = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = lib.VdnMeshSparseArgs()
+        a.values, a.isovalue, a.R, a.brick, a.nb, a.A = values.data_ptr(), level, R, B, nb, A
+        a.active, a.brick_map, a.cell_base = act32.data_ptr(), brick_map.data_ptr(), base32.data_ptr()
+        a.col_cells, a.row_cells, a.n_cells = col32.data_ptr(), row32.data_ptr(), n_cells
+        a.cube_case, a.n_verts, a.n_tris, a.missed = case.data_ptr(), nv.data_ptr(), nt.data_ptr(), missed.data_ptr()
+        _call_sized("vdn_mesh_sparse_count", a, st)
+        iv, it = torch.cumsum(nv, 0, dtype=torch.int64), torch.cumsum(nt, 0, dtype=torch.int64)
+        V, F, bad = torch.stack([iv[-1], it[-1], missed[0].long()]).tolist()       # host read 2: the output sizes and the check
+        stats["missed_edges"] = int(bad)
+        if bad:
+            raise SparseExtractionError(
+                "sparse extraction missed the surface at %d lattice edges: a cut edge of an evaluated cell borders a brick that "
+                "lipschitz = %g dropped. Raise `lipschitz` (the field is steeper than the bound) or extract densely (sparse=None)."
+                % (bad, lipschitz))
+        vertices = torch.empty(int(V), 3, dtype=torch.float64, device=dev)
+        triangles = torch.empty(int(F), 3, dtype=torch.int64, device=dev)
+        if F == 0:
+            return vertices, triangles, stats
+        vo, to = (iv - nv).contiguous(), (it - nt).contiguous()
+        a.vert_offsets, a.tri_offsets, a.V, a.F = vo.data_ptr(), to.data_ptr(), int(V), int(F)
+        a.vertices, a.triangles = vertices.data_ptr(), triangles.data_ptr()
+        _call_sized("vdn_mesh_sparse_emit", a, st)
+    return vertices, triangles, stats
 
 
 def sample_surface(vertices, triangles, spacing, max_samples=1 << 26):

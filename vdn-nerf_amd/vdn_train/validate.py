@@ -150,22 +150,24 @@ def val_img(renderer, scene, rays_gen, idx, resolution_level=1, batch_size=512, 
 
 
 def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, threshold=0.0, world_space=False, scale_mat=None,
-                  vertex_colors=True, vertex_normals=True, clean=None):
+                  vertex_colors=True, vertex_normals=True, clean=None, sparse=None):
     """Runner.validate_mesh (dpt_runner.py:699-713) without trimesh: the iso-surface of the SDF network inside the box, written
     to `out_path` as a binary PLY (vdn_train/meshio.py) -> (out_path, V, F). `world_space` maps the vertices by
     v * scale_mat[0,0] + scale_mat[:3,3] (708; a uniform scale and a translation: unit normals are unchanged). Beyond the
     reference's bare mesh, each vertex carries its unit normal and its colour seen straight down that normal
     (NeuSRenderer.extract_colored_geometry); with both flags off the file is the reference's and no network runs past the lattice.
     `clean` (a dict of vdn_train.mesh_clean.clean_mesh's keyword arguments, or None: the raw surface) cleans the mesh in object
-    space, before the world_space map; normals and colours follow their vertices, and V, F are the cleaned mesh's."""
+    space, before the world_space map; normals and colours follow their vertices, and V, F are the cleaned mesh's. `sparse` is
+    extract_geometry's: None (dense, or what VDN_MESH_SPARSE says), True or a dict - the same file from the bricks near the surface."""
     from vdn_train import meshio
     normals = colors = None
     if vertex_colors or vertex_normals:
-        vertices, triangles, normals, colors = renderer.extract_colored_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+        vertices, triangles, normals, colors = renderer.extract_colored_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold,
+                                                                                   sparse=sparse)
         normals = normals if vertex_normals else None
         colors = colors if vertex_colors else None
     else:
-        vertices, triangles = renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold)
+        vertices, triangles = renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold, sparse=sparse)
     if clean is not None:
         from vdn_train import mesh_clean
         attrs = [x for x in (normals, colors) if x is not None]
