@@ -925,6 +925,31 @@ typedef struct {
 int vdn_nn_bin(const VdnNnArgs* args_host, void* stream);
 int vdn_nn_query(const VdnNnArgs* args_host, void* stream);
 
+/* ---- mesh evaluation: greedy radius thinning of a cloud (csrc/mesh_eval.hip; vdn_hip/nn.py: thin_points) -----------------------
+ * One round of the parallel form of "visit the points in index order; a point that is still there removes every other point within
+ * `radius` (inclusive)". The cloud is in the sorted 16-byte records and cell_start table of the grid above (vdn_nn_bin's cells,
+ * h >= radius + the binning margin, so the 27 cells around a point hold all its neighbours). state[t] belongs to record t:
+ * 0 undecided, 1 kept, 2 removed; the caller zeroes it before the first round.
+ *   vdn_thin_round: one lane per record. A decided lane does nothing. An undecided one scans the nine (y, z) rows around its cell,
+ *                   each as one record range over its three x-cells, for points with a LOWER original index and
+ *                   dx^2 + dy^2 + dz^2 <= radius^2 in fp32 (the difference form of vdn_nn_query): one of them kept -> this point is
+ *                   removed; all of them removed (or none there) -> kept; otherwise it stays undecided and is counted in
+ *                   *undecided (one atomic add per wave; the caller zeroes the word before each round). States are updated in
+ *                   place: a decision is final and depends on final decisions only, so reading a neighbour's state late delays a
+ *                   decision and never changes it. No lane waits for another. The caller repeats rounds until *undecided == 0;
+ *                   every round decides at least the lowest undecided index.
+ * Status -10: N or the cell count do not fit 32-bit indexing. */
+typedef struct {
+    const float* rec;              /* [N][4] sorted packed records {x, y, z, original index as bits} */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1] */
+    int32_t* state;                /* [N] in / out, per record */
+    int32_t* undecided;            /* [1] in / out */
+    int64_t N;
+    float lo_x, lo_y, lo_z, h, radius;
+    int32_t nx, ny, nz;
+} VdnThinArgs;
+int vdn_thin_round(const VdnThinArgs* args_host, void* stream);
+
 /* ---- mesh cleaning: connected components of a triangle mesh (csrc/mesh_clean.hip; vdn_hip/mesh.py: connected_components) --------
  * Two triangles are connected when they share a vertex INDEX (no welding by position). A lock-free union-find over the index
  * buffer in `parent` [V], which the caller initialises to 0, 1, .., V - 1:

@@ -4,7 +4,12 @@
     python tools/eval_mesh.py meshes/00300000.ply scan.ply --spacing 0.2 --max-dist 20 --thresholds 1 2
 
 The mesh is a PLY of vdn_train.meshio.write_ply (validate_mesh(world_space=True) writes one in the scan's frame); the cloud is any
-binary little-endian PLY whose first element is `vertex` with x, y, z. Prints one JSON line."""
+binary little-endian PLY whose first element is `vertex` with x, y, z. The DTU protocol's steps are optional:
+
+    ... --thin 0.2 --obs-mask ObsMask24_10.mat --plane Plane24.mat [--patch 60]
+
+--thin R thins the mesh samples to pairwise more than R apart, --obs-mask FILE (.npz or .mat with ObsMask, BB, Res) leaves unobserved
+samples out of the accuracy, --plane FILE (.npz or .mat with P) leaves the scan's table out of the completeness. Prints one JSON line."""
 import argparse
 import os
 import sys
@@ -22,10 +27,15 @@ def main():
     ap.add_argument("--spacing", type=float, required=True, help="one mesh sample per spacing^2 of area")
     ap.add_argument("--max-dist", type=float, required=True, help="distances beyond it are outliers: left out of the means")
     ap.add_argument("--thresholds", type=float, nargs="*", default=[], help="F-score thresholds (each <= --max-dist)")
+    ap.add_argument("--thin", type=float, default=None, metavar="R", help="thin the mesh samples: no two kept samples within R")
+    ap.add_argument("--obs-mask", default=None, metavar="FILE", help=".npz / .mat with ObsMask, BB, Res (the DTU observation mask)")
+    ap.add_argument("--plane", default=None, metavar="FILE", help=".npz / .mat with P (the DTU ground plane)")
+    ap.add_argument("--patch", type=float, default=60.0, metavar="X", help="the band around the observation mask's box")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     from vdn_train import mesh_eval
-    res = mesh_eval.evaluate_ply(a.mesh, a.ground_truth, a.spacing, a.max_dist, a.thresholds, device=a.device)
+    res = mesh_eval.evaluate_ply(a.mesh, a.ground_truth, a.spacing, a.max_dist, a.thresholds, device=a.device,
+                                 thin=a.thin, obs_mask=a.obs_mask, patch=a.patch, plane=a.plane)
     print(mesh_eval.to_json(dict(res, mesh=a.mesh, ground_truth=a.ground_truth, spacing=a.spacing, max_dist=a.max_dist)))
 
 

@@ -1,7 +1,8 @@
-// Mesh evaluation on the device (include/vdn_render.h: vdn_surf_*, vdn_nn_*): area-weighted surface sampling of a triangle mesh
-// and exact nearest neighbours on a uniform grid - the two halves of an accuracy / completeness / Chamfer figure against a scanned
-// point cloud (vdn_train/mesh_eval.py). Gather-bound integer / float work, no LDS: one thread per triangle, per sample, per point
-// or per query. The prefix sum, the stable sorts and the cell-start table between the passes are the caller's torch ops.
+// Mesh evaluation on the device (include/vdn_render.h: vdn_surf_*, vdn_nn_*, vdn_thin_round): area-weighted surface sampling of a
+// triangle mesh, exact nearest neighbours on a uniform grid - the two halves of an accuracy / completeness / Chamfer figure against a
+// scanned point cloud (vdn_train/mesh_eval.py) - and greedy radius thinning of a cloud on the same grid. Gather-bound integer / float
+// work, no LDS: one thread per triangle, per sample, per point or per query. The prefix sum, the stable sorts and the cell-start
+// table between the passes are the caller's torch ops.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <climits>
@@ -125,6 +126,52 @@ __global__ void nn_query_kernel(VdnNnArgs a) {
     if (a.rings != nullptr) a.rings[q] = k + 1;
 }
 
+// ---- greedy radius thinning: one round -----------------------------------------------------------------------------------------
+enum { kThinUndecided = 0, kThinKept = 1, kThinRemoved = 2 };
+
+// the state of record t after looking at every lower-index point within the radius, as far as those are decided themselves
+__device__ inline int thin_decide(const VdnThinArgs& a, int t) {
+    const float4* rec = (const float4*)a.rec;
+    const float4 me = rec[t];
+    const int my_id = __float_as_int(me.w);
+    // the record's own cell: vdn_nn_bin's expression on the same fp32 bits, so the cell it was sorted into
+    const int cx = nn_axis(me.x, a.lo_x, a.h, a.nx), cy = nn_axis(me.y, a.lo_y, a.h, a.ny), cz = nn_axis(me.z, a.lo_z, a.h, a.nz);
+    const float r2 = a.radius * a.radius;
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, a.nx - 1);
+    bool waiting = false;
+    for (int z = max(cz - 1, 0); z <= min(cz + 1, a.nz - 1); ++z) {
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, a.ny - 1); ++y) {
+            const int row = (z * a.ny + y) * a.nx;
+            // the three x-cells of a row are one contiguous record range (nn_scan's trick)
+            const int begin = max(a.cell_start[row + x0], 0), end = min(a.cell_start[row + x1 + 1], (int)a.N);
+            for (int r = begin; r < end; ++r) {
+                const float4 p = rec[r];
+                if (__float_as_int(p.w) >= my_id) continue;          // (also the record itself)
+                const float dx = me.x - p.x, dy = me.y - p.y, dz = me.z - p.z;
+                if (!(dx * dx + dy * dy + dz * dz <= r2)) continue;
+                // another lane may be storing this word right now: any of its values is a valid, final-or-undecided state
+                const int s = __hip_atomic_load(&a.state[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (s == kThinKept) return kThinRemoved;
+                waiting |= s == kThinUndecided;
+            }
+        }
+    }
+    return waiting ? kThinUndecided : kThinKept;
+}
+
+__global__ void thin_round_kernel(VdnThinArgs a) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool undecided = false;
+    if (t < (long)a.N && __hip_atomic_load(&a.state[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kThinUndecided) {
+        const int s = thin_decide(a, (int)t);
+        if (s != kThinUndecided) __hip_atomic_store(&a.state[t], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        undecided = s == kThinUndecided;
+    }
+    // every lane of the wave is here again (no early return above): one add per wave that has something to add
+    const unsigned long long left = __ballot(undecided);
+    if ((threadIdx.x & 63) == 0 && left != 0) atomicAdd(a.undecided, (int)__popcll(left));
+}
+
 }  // namespace vdn
 
 static inline unsigned grid_of(long n) { return (unsigned)((n + 255) / 256); }
@@ -166,5 +213,13 @@ extern "C" int vdn_nn_query(const VdnNnArgs* a, void* stream) {
         !(a->max_dist >= 0.0f)) return -1;
     if (a->R > INT_MAX) return -10;
     hipLaunchKernelGGL(vdn::nn_query_kernel, dim3(grid_of(a->N)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_thin_round(const VdnThinArgs* a, void* stream) {
+    if (a == nullptr || a->rec == nullptr || a->cell_start == nullptr || a->state == nullptr || a->undecided == nullptr || a->N < 1 ||
+        a->nx < 1 || a->ny < 1 || a->nz < 1 || !(a->h > 0.0f) || !(a->h < INFINITY) || !(a->radius > 0.0f) || !(a->radius < INFINITY)) return -1;
+    if (a->N > INT_MAX || (int64_t)a->nx * a->ny * a->nz >= (int64_t)INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::thin_round_kernel, dim3(grid_of(a->N)), dim3(256), 0, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }

@@ -5,6 +5,10 @@ figure (vdn_train/mesh_eval.py), usable on its own:
     grid = PointGrid(ref)                 # ref [R,3] fp32 CUDA
     dist, idx = grid.query(q, max_dist)   # dist [Q] fp32, idx [Q] int64 into ref; +inf / -1 beyond max_dist
 
+and, on the same grid construction, greedy radius thinning of a cloud to a fixed density (vdn_thin_round):
+
+    keep = thin_points(points, radius)    # keep [N] bool: kept points are pairwise more than `radius` apart
+
 The kernels bin and search; the stable sorts and the cell-start table between them are torch ops on the device (the convention of
 vdn_hip/mesh.py). The cell size changes the speed only, never a result (the stopping rule and its margin)."""
 import math
@@ -38,8 +42,8 @@ def _fp32_at_most(x):
 
 class PointGrid:
     """The reference cloud `ref` [R,3] sorted into a dense uniform grid over its bounding box.
-    cell_size: the cells' edge (default: DEFAULT_CELL_FACTOR * largest extent / sqrt(R)); raised until the grid has at most
-    max_cells cells. Each axis has floor(extent / h) + 1 cells, so a flat or single-point cloud has one cell across."""
+    cell_size: the cells' edge (default: DEFAULT_CELL_FACTOR * largest extent / sqrt(R)), or a function (largest extent, R) -> edge for
+    a caller whose edge depends on the box (thin_points); raised until the grid has at most max_cells cells. Each axis has floor(extent / h) + 1 cells, so a flat or single-point cloud has one cell across."""
 
     def __init__(self, ref, cell_size=None, max_cells=1 << 24):
         ref = _check_points(ref, "ref")
@@ -48,7 +52,7 @@ class PointGrid:
             raise ValueError("the reference cloud is empty")
         if max_cells < 1:
             raise ValueError("max_cells must be at least 1")
-        if cell_size is not None and not (float(cell_size) > 0.0 and float(cell_size) < float("inf")):
+        if cell_size is not None and not callable(cell_size) and not (float(cell_size) > 0.0 and float(cell_size) < float("inf")):
             raise ValueError("cell_size must be positive and finite, got %r" % (cell_size,))
         box = torch.stack([ref.amin(0), ref.amax(0)]).tolist()                # one host read
         lo, hi = box
@@ -56,7 +60,10 @@ class PointGrid:
             raise ValueError("the reference cloud has non-finite coordinates")
         ext = [float(np.float32(h_) - np.float32(l_)) for l_, h_ in zip(lo, hi)]
         L = max(ext)
-        h = float(cell_size) if cell_size is not None else DEFAULT_CELL_FACTOR * L / math.sqrt(R)
+        if callable(cell_size):
+            h = float(cell_size(L, R))
+        else:
+            h = float(cell_size) if cell_size is not None else DEFAULT_CELL_FACTOR * L / math.sqrt(R)
         h = float(np.float32(h))
         if not (h > 0.0 and math.isfinite(h)):
             h = 1.0                                                           # (all points equal: any size gives the one cell)
@@ -122,3 +129,100 @@ class PointGrid:
 def nearest(q, ref, max_dist=None, cell_size=None):
     """dist [Q] fp32, idx [Q] int64: PointGrid(ref, cell_size).query(q, max_dist)."""
     return PointGrid(ref, cell_size=cell_size).query(q, max_dist)
+
+
+def _thin_min_cell(radius, extent):
+    """The smallest fp32 cell edge h with h >= radius + PointGrid's margin at that h (margin = m (extent + h), m = 16 * 2^-24):
+    then two points within `radius` of each other are at most one cell apart on every axis, the fp32 binning included."""
+    m = MARGIN_ULPS * 2.0 ** -24
+    h = np.float32((radius + m * extent) / (1.0 - m))
+    while not (float(h) >= radius + float(np.float32(m * (extent + float(h))))):
+        h = np.nextafter(h, np.float32(np.inf))
+    return float(np.nextafter(h, np.float32(np.inf)))            # (one more: the margin itself is rounded to fp32)
+
+
+def _rounds_to_fixpoint(one_round, N):
+    """Calls one_round() -> the number of points still undecided, until it says 0 -> the number of calls. Every round of a correct
+    kernel decides at least the lowest undecided index (the first one: point 0), so the number strictly decreases from N and the
+    loop ends within N rounds; anything else is a defect and raises RuntimeError instead of looping."""
+    rounds, before = 0, N
+    while True:
+        now = one_round()
+        rounds += 1
+        if now == 0:
+            return rounds
+        if not (0 < now < before):
+            raise RuntimeError("thin_points: round %d left %d points undecided after %d: no progress" % (rounds, now, before))
+        before = now
+
+
+def thin_points(points, radius, cell_size=None, max_cells=1 << 24, return_rounds=False):
+    """points [N,3] float CUDA -> keep [N] bool (with return_rounds: (keep, rounds)): greedy radius thinning, exactly this loop over
+    the caller's index order, on the device (vdn_thin_round, include/vdn_render.h):
+
+        keep = ones(N)
+        for i in 0..N-1:
+            if keep[i]: keep[j] = False for every j != i with |p_i - p_j| <= radius
+
+    - the lexicographically first maximal set of points that are pairwise more than `radius` apart. `<=` is inclusive, the distance
+    is (dx*dx + dy*dy + dz*dz) <= radius*radius in fp32 (PointGrid.query's difference form), of two equal points the later one goes.
+    Another visiting order: permute the points first.
+
+    The parallel form runs in rounds: a point is removed once a lower-index neighbour is kept, kept once all its lower-index
+    neighbours are removed, and waits for the next round otherwise; the fixpoint is the loop's result whatever the scheduling.
+    Every round costs one host read of the number of points still waiting. How many rounds depends on the index order, not only on
+    the cloud: surface samples at radius = sample spacing took 5 to 10 rounds in sample_surface's own order and in a random order
+    (10^6 and 10^7 samples, measured), 19 and 32 in a strip-like order (sorted into bands; 2 * 10^4 and 2 * 10^5 points, counted on
+    the CPU by tools/count_thin_rounds.py), while points on a line in index order need about N / 2 - legal and slow; permute such a
+    cloud.
+
+    The number of rounds is NOT a function of the cloud alone: inside a round a lane may or may not see what another wave has just
+    stored, so `rounds` can differ by a few between two calls on the same points (197 to 200 on the 200-point line of the tests).
+    `keep` never differs.
+
+    cell_size: the grid's cell edge; raised to the minimum radius + margin (the 27 cells around a point then hold all its
+    neighbours) and further until the grid has at most max_cells cells. Default: the larger of that minimum and extent / sqrt(N),
+    which suits a surface cloud; a cloud that fills its box gets fuller cells than it needs where radius is far below the point
+    spacing - pass cell_size there. It changes the speed only.
+
+    ValueError for a radius that is not positive and finite (in fp32 too), a non-CUDA or non-[N,3] tensor or non-finite
+    coordinates; RuntimeError if a round decides nothing (a defect: the loop never spins). N = 0 launches nothing."""
+    if not (float(radius) > 0.0 and math.isfinite(float(radius))):
+        raise ValueError("radius must be positive and finite, got %r" % (radius,))
+    with np.errstate(over="ignore"):
+        r32 = float(np.float32(float(radius)))
+    if not (r32 > 0.0 and math.isfinite(r32)):
+        raise ValueError("radius %r is not a positive finite fp32 number" % (radius,))
+    radius = r32
+    if cell_size is not None and not (float(cell_size) > 0.0 and float(cell_size) < float("inf")):
+        raise ValueError("cell_size must be positive and finite, got %r" % (cell_size,))
+    points = _check_points(points, "points")
+    N, dev = points.shape[0], points.device
+    if N == 0:
+        keep = torch.zeros(0, dtype=torch.bool, device=dev)
+        return (keep, 0) if return_rounds else keep
+    # the edge needs the box's extent: PointGrid reads and checks the box once and asks back
+    edge = lambda extent, n: max(_thin_min_cell(radius, extent), float(cell_size) if cell_size is not None else extent / math.sqrt(n))
+    try:
+        grid = PointGrid(points, cell_size=edge, max_cells=max_cells)
+    except ValueError as e:
+        raise ValueError(str(e).replace("the reference cloud", "the cloud"))
+    if not (grid.h >= radius + grid.margin):
+        raise RuntimeError("thin_points: cell edge %r does not cover radius %r + margin %r" % (grid.h, radius, grid.margin))
+    with torch.cuda.device(dev):
+        state = torch.zeros(N, dtype=torch.int32, device=dev)
+        left = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = lib.VdnThinArgs()
+        a.rec, a.cell_start, a.state, a.undecided, a.N = grid.records.data_ptr(), grid.cell_start.data_ptr(), state.data_ptr(), left.data_ptr(), N
+        a.lo_x, a.lo_y, a.lo_z, a.h, a.radius = grid.lo[0], grid.lo[1], grid.lo[2], grid.h, radius
+        a.nx, a.ny, a.nz = grid.dims
+
+        def one_round():
+            left.zero_()
+            _call_sized("vdn_thin_round", a, lib.stream_handle())
+            return int(left.item())
+
+        rounds = _rounds_to_fixpoint(one_round, N)
+        keep = torch.empty(N, dtype=torch.bool, device=dev)
+        keep[grid.records.view(torch.int32)[:, 3].long()] = state == 1
+    return (keep, rounds) if return_rounds else keep

@@ -4,7 +4,8 @@ third-party `trimesh`; this module writes the same kind of file with numpy alone
 Layout (`binary_little_endian 1.0`):
   element vertex V:  float x y z, [float nx ny nz], [uchar red green blue]
   element face F:    property list uchar int vertex_indices   (always 3 indices: 13 bytes per face)
-Both elements are written from numpy structured arrays; read_ply reads exactly this layout and raises on anything else."""
+Both elements are written from numpy structured arrays; read_ply reads exactly this layout and raises on anything else.
+read_points_ply reads the positions of a scanned cloud, read_dtu_aux the arrays the DTU evaluation keeps beside one."""
 import numpy as np
 
 _POS = ("x", "y", "z")
@@ -169,3 +170,49 @@ def read_ply(path):
                     return {"vertices": col(_POS), "triangles": face["v"].astype(np.int32).reshape(F, 3),
                             "normals": col(_NRM) if has_n else None, "colors": col(_COL) if has_c else None}
     raise ValueError("%s: the header is not one write_ply writes" % path)
+
+
+def read_dtu_aux(path):
+    """-> dict with those of ObsMask (bool [X,Y,Z]), BB (float32 [2,3]), Res (float), P (float64 [4]) the file holds: the arrays
+    the DTU evaluation reads beside a scan (the observation mask with its box and voxel pitch, the ground plane), for
+    vdn_train.mesh_eval's observed_mask / above_plane. `.npz`: numpy's archive with those names; `.mat`: a MATLAB file with the same
+    names, read through scipy.io.loadmat - a ValueError says so where scipy is not installed (convert the file to .npz elsewhere).
+    ValueError on a v7.3 (HDF5) .mat file, on any other suffix and on an array of the wrong shape; other names in the file are ignored."""
+    p = str(path)
+    if p.lower().endswith(".npz"):
+        with np.load(p, allow_pickle=False) as z:
+            raw = {k: z[k] for k in ("ObsMask", "BB", "Res", "P") if k in z.files}
+    elif p.lower().endswith(".mat"):
+        try:
+            from scipy.io import loadmat
+        except ImportError:
+            raise ValueError("%s: a .mat file needs scipy (scipy.io.loadmat), which cannot be imported; convert it to .npz" % p)
+        try:
+            m = loadmat(p)
+        except NotImplementedError:
+            raise ValueError("%s: a MATLAB v7.3 (HDF5) file, which scipy.io.loadmat does not read; save it with -v7 or convert it to .npz" % p)
+        raw = {k: np.asarray(m[k]) for k in ("ObsMask", "BB", "Res", "P") if k in m}
+    else:
+        raise ValueError("%s: expected a .npz or .mat file" % p)
+    out = {}
+    if "ObsMask" in raw:
+        a = raw["ObsMask"]
+        if a.ndim != 3 or a.dtype.kind not in "bui":
+            raise ValueError("%s: ObsMask must be a 3-D bool or integer array, got %s %r" % (p, a.dtype, a.shape))
+        out["ObsMask"] = np.ascontiguousarray(a != 0)
+    if "BB" in raw:
+        a = raw["BB"]
+        if a.shape != (2, 3) or a.dtype.kind not in "fui":
+            raise ValueError("%s: BB must be [2,3] numbers, got %s %r" % (p, a.dtype, a.shape))
+        out["BB"] = np.ascontiguousarray(a, dtype=np.float32)
+    if "Res" in raw:
+        a = raw["Res"]
+        if a.size != 1 or a.dtype.kind not in "fui":
+            raise ValueError("%s: Res must be one number, got %s %r" % (p, a.dtype, a.shape))
+        out["Res"] = float(a.reshape(-1)[0])
+    if "P" in raw:
+        a = raw["P"]
+        if a.size != 4 or a.ndim > 2 or a.dtype.kind not in "fui":
+            raise ValueError("%s: P must be 4 numbers, got %s %r" % (p, a.dtype, a.shape))
+        out["P"] = np.ascontiguousarray(a, dtype=np.float64).reshape(4)
+    return out
