@@ -1122,6 +1122,86 @@ typedef struct {
 } VdnVisibilityArgs;
 int vdn_visibility_votes(const VdnVisibilityArgs* args_host, void* stream);
 
+/* ---- mesh simplification: quadric vertex clustering (csrc/mesh_simplify.hip; vdn_hip/mesh.py: cluster_quadrics, simplify_mesh) ----
+ * Rossignac-Borrel cells with Lindstrom's per-cell quadric. The grid has nx * ny * nz cubic cells of edge h; cell (ix, iy, iz) of a
+ * point p is floor((double(p) - origin) / h) per axis (a division), the grid covers the cell indices lo_k .. lo_k + n_k - 1, and
+ * key = (ix - lo_x) + nx * ((iy - lo_y) + ny * (iz - lo_z)) as int64 (lo = 0 when origin is the box's minimum corner). All arithmetic
+ * is double on the widened fp32 vertices, every product and sum rounded on its own (the file is built without contraction). No float
+ * atomics: every sum has a fixed order. The sorts, scans and `unique` between the passes are the caller's torch ops.
+ *   vdn_simplify_mark:    one thread per triangle. live[f] = 1 iff its three corners are finite; a live triangle stores 1 to
+ *                         vertex_used of its corners (the caller zeroes it; plain byte stores of one value). A corner index outside
+ *                         [0, V) sets *error = 1 (the caller zeroes it first), the triangle is not live, nothing is touched out of
+ *                         bounds.
+ *   vdn_simplify_keys:    one thread per vertex: key[v] as above; -1 for a vertex that is not finite or lies outside the grid.
+ *   vdn_simplify_records: one thread per triangle. corner_cluster[3 f + c] = vertex_cluster of corner c for a live triangle, else
+ *                         the sentinel C (so that a sort by cluster id puts the dead records last); survive[f] = 1 iff the triangle
+ *                         is live and its three clusters are pairwise distinct; canonical[f] = the three cluster ids rotated so
+ *                         that the smallest comes first (orientation preserved; C, C, C where the triangle does not survive).
+ *   vdn_segment_mean:     one wave per segment s: out[s][k] = (sum over j in [start[s], start[s+1]) of rows[members[j]][k]) / count
+ *                         in double, generic over K fp32 columns (positions and per-vertex attributes alike); an empty segment gives
+ *                         NaN (0 / 0). `members` is the inverted index a stable sort by cluster id gives: ascending vertex index
+ *                         inside a segment.
+ *   vdn_cluster_quadrics: one wave per cluster over its corner records, `members` = the stable sort of corner_cluster, i.e.
+ *                         (triangle, corner) order inside a cluster. Record e = 3 f + c adds triangle f's plane quadric, recomputed
+ *                         from the triangle: with pa, pb, pc the corners in the triangle's own order MINUS centre[s],
+ *                             n = (pb - pa) x (pc - pa) = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0),
+ *                             d = -((n0 pa0 + n1 pa1) + n2 pa2),
+ *                             (n0 n0, n0 n1, n0 n2, n1 n1, n1 n2, n2 n2, n0 d, n1 d, n2 d, d d)
+ *                         (n unnormalised: area-squared weights; a degenerate triangle adds zeros) -> quadric [C][10] double.
+ *   The summation order of both segmented sums: lane l of 64 adds its list's entries j = l, l + 64, l + 128, .. in increasing j,
+ *   starting from +0.0; then for s = 32, 16, 8, 4, 2, 1: partial[l] += partial[l + s] for l < s. Bitwise reproducible.
+ *   vdn_cluster_place:    one thread per cluster. m = mean[s] (relative to the cell centre), A, b from the quadric,
+ *                         tr = (Axx + Ayy) + Azz. tr not positive and finite: x = m, status 1. Otherwise (A + eps tr I) delta =
+ *                         -b - A m solved directly in double (cofactors), x = m + delta; x not finite or |x_k| > h / 2 on an axis:
+ *                         x = m, status 2. position[s] = centre[s] + x, status[s] as a byte.
+ * Status -10: V, F, C or K * the row count do not fit 32-bit indexing. */
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes) */
+    uint8_t* live;                 /* [F] out (mark), in (records) */
+    uint8_t* vertex_used;          /* [V] in / out   (mark) */
+    int32_t* error;                /* [1]   (mark) */
+    int64_t* key;                  /* [V] out   (keys) */
+    const int64_t* vertex_cluster; /* [V] cluster id or -1   (records) */
+    int64_t* corner_cluster;       /* [3 F] out   (records) */
+    int64_t* canonical;            /* [F][3] out   (records) */
+    uint8_t* survive;              /* [F] out   (records) */
+    int64_t V, F, C;
+    double origin_x, origin_y, origin_z, h;
+    int64_t lo_x, lo_y, lo_z, nx, ny, nz;
+    int32_t index_bytes, _pad;
+} VdnSimplifyArgs;
+int vdn_simplify_mark(const VdnSimplifyArgs* args_host, void* stream);
+int vdn_simplify_keys(const VdnSimplifyArgs* args_host, void* stream);
+int vdn_simplify_records(const VdnSimplifyArgs* args_host, void* stream);
+
+typedef struct {
+    const float* rows;             /* [N][K] */
+    const int64_t* members;        /* [M] row numbers, segment by segment */
+    const int64_t* start;          /* [C + 1] ascending, start[C] <= M */
+    double* out;                   /* [C][K] */
+    int64_t N, M, C;
+    int32_t K, _pad;
+} VdnSegmentMeanArgs;
+int vdn_segment_mean(const VdnSegmentMeanArgs* args_host, void* stream);
+
+typedef struct {
+    const float* vertices;         /* [V][3] */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes); the records' triangles are live: corners in range */
+    const int64_t* members;        /* [M] record numbers 3 f + c, cluster by cluster   (quadrics) */
+    const int64_t* start;          /* [C + 1]   (quadrics) */
+    const double* centre;          /* [C][3] */
+    double* quadric;               /* [C][10] out (quadrics), in (place) */
+    const double* mean;            /* [C][3] relative to the centre   (place) */
+    double* position;              /* [C][3] out   (place) */
+    uint8_t* status;               /* [C] out   (place) */
+    int64_t V, F, M, C;
+    double h, eps;
+    int32_t index_bytes, _pad;
+} VdnClusterQuadricArgs;
+int vdn_cluster_quadrics(const VdnClusterQuadricArgs* args_host, void* stream);
+int vdn_cluster_place(const VdnClusterQuadricArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

@@ -874,15 +874,21 @@ class NeuSRenderer:
         extract_geometry's own arrays, winding included. Each vertex (object space, cast to fp32) is shaded looking straight down
         its normal (vdn_hip.mesh.shade_points): normals = g / max(|g|, 1e-12) of the raw SDF gradient g, colors = the colour
         network's BGR output reversed and quantised as rint(clip(c, 0, 1) * 255)."""
-        from vdn_hip import mesh
         vertices, triangles = self.extract_geometry(bound_min, bound_max, resolution, threshold=threshold, method=method, sparse=sparse)
+        normals, colors = self.shade_vertices(vertices)
+        return vertices, triangles, normals, colors
+
+    def shade_vertices(self, vertices):
+        """The attributes extract_colored_geometry gives its vertices, for any [V,3] array of object-space points (a mesh that was
+        simplified after the extraction is shaded at its new vertices): -> (normals [V,3] float32, colors [V,3] uint8 RGB)."""
+        from vdn_hip import mesh
         dev = lib.first_param(self.sdf_network).device
         x = torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float32)).reshape(-1, 3).to(dev)
         if x.shape[0] == 0:
-            return vertices, triangles, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
         _, g, c = mesh.shade_points(self, x)
         normals = (g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)).cpu().numpy()
-        return vertices, triangles, normals, mesh.quantize_colors_bgr(c.cpu().numpy())
+        return normals, mesh.quantize_colors_bgr(c.cpu().numpy())
 
 
 class RenderPlan:

@@ -14,7 +14,11 @@ the pieces of a mesh, dilate_masks / mask_votes count in how many object masks a
 vertices and renumbers the rest.
 
 Ray casting (csrc/mesh_ray.hip): MeshGrid references the triangles from a uniform grid and casts rays against them (closest hit
-or any hit, two-sided Moller-Trumbore in double); visibility_votes counts the cameras that see each vertex unoccluded."""
+or any hit, two-sided Moller-Trumbore in double); visibility_votes counts the cameras that see each vertex unoccluded.
+
+Simplification (csrc/mesh_simplify.hip; the front door is vdn_train/mesh_simplify.py): cluster_quadrics groups the vertices by the
+cells of a uniform grid and sums each cluster's quadric in a fixed order, simplify_mesh places one vertex per cluster and emits the
+triangles that survive, count_simplified_faces is the count-only pass a face budget is searched with."""
 import math
 import os
 
@@ -737,3 +741,247 @@ def shade_points(renderer, points, batch=1 << 20):
             sdf[s:s + n], grad[s:s + n] = out[:, 0], g
             col[s:s + n] = cn(x, g, view_from_gradient(g), feat)
     return sdf, grad, col
+
+
+# ---- simplification: quadric vertex clustering (csrc/mesh_simplify.hip) -----------------------------------------------
+SIMPLIFY_EPS = 1e-3          # the regulariser of the placement solve, relative to the quadric's trace: an interface default
+
+
+def _positive_finite(name, x):
+    try:
+        x = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, x))
+    if not (x > 0.0 and x < float("inf")):
+        raise ValueError("%s must be positive and finite, got %r" % (name, x))
+    return x
+
+
+def _first_of_each(codes, n):
+    """codes [n] int64 -> bool [n]: True at the first position of each distinct value"""
+    uniq, inv = torch.unique(codes, return_inverse=True)
+    first = torch.full((uniq.numel(),), n, dtype=torch.int64, device=codes.device)
+    first.scatter_reduce_(0, inv, torch.arange(n, device=codes.device), reduce="amin")
+    out = torch.zeros(n, dtype=torch.bool, device=codes.device)
+    out[first] = True
+    return out
+
+
+def _segments(ids, n_segments):
+    """ids [N] int64 in [0, n_segments] (n_segments = the sentinel of entries in no segment) -> (members [N] int64: a stable sort by
+    id, so ascending position inside a segment; start [n_segments + 1] int64)"""
+    members = torch.sort(ids, stable=True)[1].contiguous()
+    count = torch.bincount(ids, minlength=n_segments + 1)[:n_segments]
+    start = torch.zeros(n_segments + 1, dtype=torch.int64, device=ids.device)
+    start[1:] = torch.cumsum(count, 0)
+    return members, start
+
+
+def _cluster_stage(name, vertices, triangles, cell_size, origin):
+    """The part simplify_mesh, cluster_quadrics and count_simplified_faces share: mark, keys, clusters, corner records and the
+    duplicate rule -> dict (None-valued arrays for an empty mesh). Two host reads."""
+    _check_triangles(name, triangles)
+    _check_vertices(name, vertices, triangles)
+    h = _positive_finite("cell_size", cell_size)
+    if origin is not None:
+        try:
+            origin = [float(x) for x in (origin.tolist() if hasattr(origin, "tolist") else origin)]
+        except (TypeError, ValueError):
+            raise ValueError("origin must be three numbers, got %r" % (origin,))
+        if len(origin) != 3 or not all(math.isfinite(x) for x in origin):
+            raise ValueError("origin must be three finite numbers, got %r" % (origin,))
+    dev = vertices.device
+    v, t = vertices.detach().float().contiguous(), triangles.contiguous()
+    V, F = v.shape[0], t.shape[0]
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError("%s: the sizes do not fit 32-bit indexing" % name)
+    if F > 0 and V == 0:
+        raise ValueError("a triangle refers to a vertex outside [0, 0)")
+    s = {"v": v, "t": t, "V": V, "F": F, "h": h, "origin": origin, "C": 0, "n_live": 0,
+         "vertex_cluster": torch.full((V,), -1, dtype=torch.int64, device=dev)}
+    if F == 0:
+        return s
+    with torch.cuda.device(dev):
+        st = lib.stream_handle()
+        live = torch.empty(F, dtype=torch.uint8, device=dev)
+        used = torch.zeros(V, dtype=torch.uint8, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = lib.VdnSimplifyArgs()
+        a.vertices, a.triangles, a.live, a.vertex_used, a.error = v.data_ptr(), t.data_ptr(), live.data_ptr(), used.data_ptr(), err.data_ptr()
+        a.V, a.F, a.index_bytes, a.h = V, F, t.element_size(), h
+        _call_sized("vdn_simplify_mark", a, st)
+        ub = used.bool()
+        inf = torch.full((1, 3), float("inf"), device=dev)
+        lo = torch.where(ub[:, None], v, inf).amin(dim=0).double()
+        hi = torch.where(ub[:, None], v, -inf).amax(dim=0).double()
+        stats = torch.cat([lo, hi, torch.stack([err[0].long(), live.sum(), used.sum()]).double()]).tolist()    # host read 1: box, flag, counts
+        if stats[6]:
+            raise ValueError("a triangle refers to a vertex outside [0, %d)" % V)
+        n_live, n_used = int(stats[7]), int(stats[8])
+        s["n_live"] = n_live
+        if n_live == 0:
+            return s
+        if origin is None:
+            origin = stats[0:3]
+        # the grid covers the cells of the referenced finite vertices; floor is monotone, so the box's corners give the range
+        i_lo = [math.floor((stats[k] - origin[k]) / h) for k in range(3)]
+        i_hi = [math.floor((stats[3 + k] - origin[k]) / h) for k in range(3)]
+        dims = [b - c + 1 for b, c in zip(i_hi, i_lo)]
+        if max(abs(x) for x in i_lo + i_hi) >= 1 << 52 or dims[0] * dims[1] * dims[2] >= 1 << 62:
+            raise ValueError("%s: a cell size of %g gives a grid of %s cells, more than 62 bits hold" % (name, h, "x".join(str(d) for d in dims)))
+        key = torch.empty(V, dtype=torch.int64, device=dev)
+        a.key, a.origin_x, a.origin_y, a.origin_z = key.data_ptr(), origin[0], origin[1], origin[2]
+        a.lo_x, a.lo_y, a.lo_z, a.nx, a.ny, a.nz = i_lo[0], i_lo[1], i_lo[2], dims[0], dims[1], dims[2]
+        _call_sized("vdn_simplify_keys", a, st)
+        # clusters = the distinct keys of the referenced vertices, ascending; an unreferenced vertex sorts first as -1
+        uniq, inv = torch.unique(torch.where(ub, key, torch.full_like(key, -1)), sorted=True, return_inverse=True)
+        if n_used < V:
+            uniq, inv = uniq[1:], inv - 1
+        C = int(uniq.shape[0])
+        vertex_cluster = inv.contiguous()
+        cell = torch.stack([uniq % dims[0] + i_lo[0], (uniq // dims[0]) % dims[1] + i_lo[1], uniq // (dims[0] * dims[1]) + i_lo[2]], dim=1)
+        corner = torch.empty(3 * F, dtype=torch.int64, device=dev)
+        canonical = torch.empty(F, 3, dtype=torch.int64, device=dev)
+        survive = torch.empty(F, dtype=torch.uint8, device=dev)
+        a.vertex_cluster, a.corner_cluster, a.canonical, a.survive, a.C = (vertex_cluster.data_ptr(), corner.data_ptr(), canonical.data_ptr(),
+                                                                             survive.data_ptr(), C)
+        _call_sized("vdn_simplify_records", a, st)
+        # the duplicate rule: among the survivors with one canonical triple the first in input order is emitted
+        idx = torch.nonzero(survive).reshape(-1)
+        emit = torch.zeros(F, dtype=torch.bool, device=dev)
+        if idx.numel() > 0:
+            tri = canonical[idx]
+            if C <= 1 << 21:
+                codes = (tri[:, 0] * C + tri[:, 1]) * C + tri[:, 2]
+            else:                                            # (three 31-bit ids do not fit one word: pair the first two, then the third)
+                pair = torch.unique(tri[:, 0] * C + tri[:, 1], return_inverse=True)[1]
+                codes = pair * C + tri[:, 2]
+            emit[idx[_first_of_each(codes, idx.numel())]] = True
+        s.update(origin=origin, C=C, vertex_cluster=vertex_cluster, cell=cell, corner=corner, survive=survive, emit=emit, live=live,
+                 centre=(torch.tensor(origin, dtype=torch.float64, device=dev)[None] + (cell.double() + 0.5) * h).contiguous())
+    return s
+
+
+def _segment_mean(rows, members, start, C):
+    """rows fp32 [N,K] -> fp64 [C,K] by vdn_segment_mean"""
+    rows = rows.contiguous()
+    out = torch.empty(C, rows.shape[1], dtype=torch.float64, device=rows.device)
+    a = lib.VdnSegmentMeanArgs()
+    a.rows, a.members, a.start, a.out = rows.data_ptr(), members.data_ptr(), start.data_ptr(), out.data_ptr()
+    a.N, a.M, a.C, a.K = rows.shape[0], members.shape[0], C, rows.shape[1]
+    _call_sized("vdn_segment_mean", a, lib.stream_handle())
+    return out
+
+
+def _vertex_members(s):
+    vc = s["vertex_cluster"]
+    return _segments(torch.where(vc < 0, torch.full_like(vc, s["C"]), vc), s["C"])
+
+
+def _quadric_stage(s):
+    """-> (quadric [C,10], mean [C,3] relative to the centre, vertex members, start) of a non-empty cluster stage"""
+    v, t, C = s["v"], s["t"], s["C"]
+    with torch.cuda.device(v.device):
+        vm, vstart = _vertex_members(s)
+        mean = _segment_mean(v, vm, vstart, C) - s["centre"]
+        rm, rstart = _segments(s["corner"], C)
+        quadric = torch.empty(C, 10, dtype=torch.float64, device=v.device)
+        a = lib.VdnClusterQuadricArgs()
+        a.vertices, a.triangles, a.members, a.start = v.data_ptr(), t.data_ptr(), rm.data_ptr(), rstart.data_ptr()
+        a.centre, a.quadric = s["centre"].data_ptr(), quadric.data_ptr()
+        a.V, a.F, a.M, a.C, a.index_bytes = s["V"], s["F"], rm.shape[0], C, t.element_size()
+        _call_sized("vdn_cluster_quadrics", a, lib.stream_handle())
+    return quadric, mean.contiguous(), vm, vstart
+
+
+def cluster_quadrics(vertices, triangles, cell_size, origin=None):
+    """The clusters of vertex clustering on a grid of cubic cells of edge cell_size from `origin` (default: the minimum corner of the
+    box of the referenced finite vertices), and Lindstrom's quadric of each (vdn_simplify_*, vdn_segment_mean, vdn_cluster_quadrics:
+    include/vdn_render.h) -> dict of device tensors: vertex_cluster [V] int64 (-1 for a vertex in no cluster: not finite, or used
+    by no live triangle), cell [C,3] int64 (floor((v - origin) / cell_size) per axis), quadric [C,10] float64 (Axx, Axy, Axz, Ayy,
+    Ayz, Azz, bx, by, bz, c of sum (n.x + d)^2 over the cluster's corner records, n the unnormalised normal, coordinates relative to
+    the cell centre origin + (cell + 0.5) cell_size), mean [C,3] float64 (the members' mean position, relative to the cell centre)
+    and origin (3 floats). A triangle is live when its three corners are finite; clusters are numbered in ascending key order.
+    Both sums have a fixed order: two calls give the same bits. ValueError as simplify_mesh."""
+    s = _cluster_stage("cluster_quadrics", vertices, triangles, cell_size, origin)
+    dev = vertices.device
+    if s["C"] == 0:
+        return {"vertex_cluster": s["vertex_cluster"], "cell": torch.empty(0, 3, dtype=torch.int64, device=dev),
+                "quadric": torch.empty(0, 10, dtype=torch.float64, device=dev), "mean": torch.empty(0, 3, dtype=torch.float64, device=dev),
+                "origin": s["origin"]}
+    quadric, mean, _, _ = _quadric_stage(s)
+    return {"vertex_cluster": s["vertex_cluster"], "cell": s["cell"], "quadric": quadric, "mean": mean, "origin": s["origin"]}
+
+
+def count_simplified_faces(vertices, triangles, cell_size, origin=None):
+    """The number of triangles simplify_mesh(vertices, triangles, cell_size, origin=origin) emits, without the quadrics, the means or
+    the output: keys, corner records and the duplicate rule only (what a search for a cell size needs)."""
+    s = _cluster_stage("count_simplified_faces", vertices, triangles, cell_size, origin)
+    return int(s["emit"].sum()) if s["C"] > 0 else 0
+
+
+def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="quadric", eps=SIMPLIFY_EPS, attributes=()):
+    """Vertex clustering with quadric error placement: vertices [V,3] CUDA float (taken as fp32), triangles [F,3] CUDA int64 or int32
+    -> dict(vertices [V',3] (the input's float dtype), triangles [F',3] (the input's integer dtype), attributes, vertex_cluster [V]
+    int64 (the NEW vertex of each old one, -1 where it has none), status [V'] uint8, report).
+
+    Every cluster of cluster_quadrics becomes one vertex. placement="mean": the members' mean position (status 0).
+    placement="quadric": x = m + delta with (A + eps tr(A) I) delta = -b - A m, m the mean relative to the cell centre - the
+    minimiser of the cluster's quadric, its free directions pulled to the mean (status 0); x = m where tr(A) is not positive and
+    finite (status 1) or where x is not finite or leaves the cell, |x_k| > cell_size / 2 (status 2).
+    A triangle SURVIVES when it is live (three finite corners) and its corners fall into three different clusters. A triangle is
+    emitted iff it survives and is the first in input order among the survivors with its canonical triple (the three cluster ids
+    rotated so that the smallest comes first). Emitted triangles keep the input's order and their corner order. A triangle and its
+    mirror image have different canonical triples: coincident triangles of opposite orientation - a thin sheet collapsed onto
+    itself - both stay. Clusters no emitted triangle uses are dropped (filter_mesh). `attributes`: a sequence of [V] or [V,...]
+    CUDA tensors, averaged per cluster by the same segmented mean as the positions (fp64 mean of the fp32 values): float attributes
+    come back in their dtype, uint8 ones as the float mean rounded to nearest, halves to even.
+    report: vertices_in, faces_in, clusters, vertices_out, faces_out, faces_collapsed, faces_duplicate, faces_non_finite,
+    cell_size, origin, placement, eps, status (the count of each status value).
+    ValueError on CPU tensors, wrong shapes, a corner index outside [0, V), a cell_size or eps that is not positive and finite, or a
+    grid whose nx ny nz does not fit 62 bits. An empty mesh (or one without a live triangle) returns an empty mesh."""
+    if placement not in ("quadric", "mean"):
+        raise ValueError("placement must be 'quadric' or 'mean', got %r" % (placement,))
+    eps = _positive_finite("eps", eps)
+    attributes = list(attributes)
+    V = vertices.shape[0] if torch.is_tensor(vertices) and vertices.dim() > 0 else 0
+    for x in attributes:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.shape[0] == V and (x.is_floating_point() or x.dtype == torch.uint8)):
+            raise ValueError("an attribute must be a float or uint8 CUDA tensor with one row per vertex")
+    s = _cluster_stage("simplify_mesh", vertices, triangles, cell_size, origin)
+    dev, C, F = vertices.device, s["C"], s["F"]
+    report = {"vertices_in": s["V"], "faces_in": F, "clusters": C, "cell_size": s["h"], "origin": s["origin"], "placement": placement,
+              "eps": eps, "faces_non_finite": F - s["n_live"]}
+    if C == 0:
+        report.update(vertices_out=0, faces_out=0, faces_collapsed=0, faces_duplicate=0, status={"0": 0, "1": 0, "2": 0})
+        return {"vertices": torch.empty(0, 3, dtype=vertices.dtype, device=dev), "triangles": torch.empty(0, 3, dtype=triangles.dtype, device=dev),
+                "attributes": [torch.empty((0,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in attributes],
+                "vertex_cluster": s["vertex_cluster"], "status": torch.empty(0, dtype=torch.uint8, device=dev), "report": report}
+    with torch.cuda.device(dev):
+        status = torch.zeros(C, dtype=torch.uint8, device=dev)
+        if placement == "mean":
+            vm, vstart = _vertex_members(s)
+            position = _segment_mean(s["v"], vm, vstart, C)          # (= centre + the mean relative to it, without the round trip)
+        else:
+            quadric, mean, vm, vstart = _quadric_stage(s)
+            position = torch.empty(C, 3, dtype=torch.float64, device=dev)
+            a = lib.VdnClusterQuadricArgs()
+            a.centre, a.quadric, a.mean, a.position, a.status = (s["centre"].data_ptr(), quadric.data_ptr(), mean.data_ptr(), position.data_ptr(),
+                                                                 status.data_ptr())
+            a.V, a.F, a.C, a.h, a.eps = s["V"], F, C, s["h"], eps
+            _call_sized("vdn_cluster_place", a, lib.stream_handle())
+        # (the records of a triangle that is not emitted may hold the sentinel C: not an index filter_mesh accepts)
+        corner = torch.where(s["emit"][:, None], s["corner"].reshape(F, 3), torch.zeros((), dtype=torch.int64, device=dev)).to(triangles.dtype)
+        new_v, new_t, kept = filter_mesh(position, corner, keep_faces=s["emit"])
+        out_attrs = []
+        for x in attributes:
+            m = _segment_mean(x.reshape(V, -1).float(), vm, vstart, C)[kept].reshape((kept.shape[0],) + tuple(x.shape[1:]))
+            out_attrs.append(torch.round(m).clamp_(0, 255).to(torch.uint8) if x.dtype == torch.uint8 else m.to(x.dtype))
+        new_of_cluster = torch.full((C + 1,), -1, dtype=torch.int64, device=dev)
+        new_of_cluster[kept] = torch.arange(kept.shape[0], device=dev)
+        status = status[kept]
+        n_surv, n_stat = int(s["survive"].sum()), torch.bincount(status.long(), minlength=3).tolist()       # host read 3
+    report.update(vertices_out=int(new_v.shape[0]), faces_out=int(new_t.shape[0]), faces_collapsed=s["n_live"] - n_surv,
+                  faces_duplicate=n_surv - int(new_t.shape[0]), status={str(k): int(n) for k, n in enumerate(n_stat)})
+    return {"vertices": new_v.to(vertices.dtype), "triangles": new_t, "attributes": out_attrs,
+            "vertex_cluster": new_of_cluster[s["vertex_cluster"]], "status": status, "report": report}

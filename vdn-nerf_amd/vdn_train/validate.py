@@ -150,7 +150,7 @@ def val_img(renderer, scene, rays_gen, idx, resolution_level=1, batch_size=512, 
 
 
 def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, threshold=0.0, world_space=False, scale_mat=None,
-                  vertex_colors=True, vertex_normals=True, clean=None, sparse=None):
+                  vertex_colors=True, vertex_normals=True, clean=None, sparse=None, simplify=None):
     """Runner.validate_mesh (dpt_runner.py:699-713) without trimesh: the iso-surface of the SDF network inside the box, written
     to `out_path` as a binary PLY (vdn_train/meshio.py) -> (out_path, V, F). `world_space` maps the vertices by
     v * scale_mat[0,0] + scale_mat[:3,3] (708; a uniform scale and a translation: unit normals are unchanged). Beyond the
@@ -158,10 +158,30 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     (NeuSRenderer.extract_colored_geometry); with both flags off the file is the reference's and no network runs past the lattice.
     `clean` (a dict of vdn_train.mesh_clean.clean_mesh's keyword arguments, or None: the raw surface) cleans the mesh in object
     space, before the world_space map; normals and colours follow their vertices, and V, F are the cleaned mesh's. `sparse` is
-    extract_geometry's: None (dense, or what VDN_MESH_SPARSE says), True or a dict - the same file from the bricks near the surface."""
+    extract_geometry's: None (dense, or what VDN_MESH_SPARSE says), True or a dict - the same file from the bricks near the surface.
+    `simplify` (a dict of vdn_train.mesh_simplify.simplify_mesh's keyword arguments - cell_size or target_faces, in object-space
+    units - or None: the file as it always was) thins the mesh after `clean` and before the world_space map. The vertices are then
+    shaded AFTER the simplification, at their new positions (renderer.shade_vertices): normals and colours come from the networks,
+    not from averages, and the fine surface is never shaded at all - one shading pass, over the vertices that reach the file."""
     from vdn_train import meshio
     normals = colors = None
-    if vertex_colors or vertex_normals:
+    if simplify is not None:
+        from vdn_train import mesh_simplify
+        if "attributes" in simplify:
+            raise ValueError("validate_mesh shades the simplified vertices itself: `simplify` takes no attributes")
+        vertices, triangles = renderer.extract_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold, sparse=sparse)
+        if clean is not None:
+            from vdn_train import mesh_clean
+            res = mesh_clean.clean_mesh(vertices, triangles, **clean)
+            vertices, triangles = res["vertices"], res["triangles"]
+        res = mesh_simplify.simplify_mesh(vertices, triangles, **simplify)
+        vertices, triangles = res["vertices"], res["triangles"]
+        if vertex_colors or vertex_normals:
+            normals, colors = renderer.shade_vertices(vertices)
+            normals = normals if vertex_normals else None
+            colors = colors if vertex_colors else None
+        clean = None
+    elif vertex_colors or vertex_normals:
         vertices, triangles, normals, colors = renderer.extract_colored_geometry(bound_min, bound_max, resolution=resolution, threshold=threshold,
                                                                                    sparse=sparse)
         normals = normals if vertex_normals else None
@@ -187,11 +207,12 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     return out_path, int(vertices.shape[0]), int(triangles.shape[0])
 
 
-def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, **kw):
+def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simplify=None, **kw):
     """validate_mesh for a vdn_train.dataset.SceneData: its object bounding box and scale_mats_np[0], the runner's file name
     meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711). A `clean` dict with a true "use_masks" entry gets
     the scene's object-space cameras and its masks (cleaning happens in object space); a true "use_cameras" entry gets the cameras
-    and the image size without the masks - what a "visibility" entry needs (either of the two satisfies it)."""
+    and the image size without the masks - what a "visibility" entry needs (either of the two satisfies it). `simplify` is
+    validate_mesh's, in object-space units."""
     if clean is not None:
         clean = dict(clean)
         use_masks, use_cameras = clean.pop("use_masks", False), clean.pop("use_cameras", False)
@@ -202,4 +223,4 @@ def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, **kw)
     bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
     bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
     return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
-                         scale_mat=scene.scale_mats_np[0], clean=clean, **kw)
+                         scale_mat=scene.scale_mats_np[0], clean=clean, simplify=simplify, **kw)
