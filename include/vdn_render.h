@@ -549,7 +549,8 @@ typedef struct {
     float scale, bscale;
     /* optional second source for ONE target row: target[xrow, cmap[j]] gets  + xscale * sum_s xsum[s, cmap[j]]  on top of the slab
      * sums (the sdf row of the last SDF layer also collects colsum(ub_8), k_sdf_bwd.h) - instead of a '+=' descriptor and
-     * a second launch */
+     * a second launch. The sums are indexed by the TARGET column cmap[j] (< xM), not by the image column j, and ride on the slab's
+     * column loop: they are applied only where the descriptor has a target and N > 0 (the one user, the lin8 entry, has N = 256) */
     const float* xsum;                     /* [xsplits, xM] or NULL */
     int32_t xsplits, xM, xrow;
     float xscale;
