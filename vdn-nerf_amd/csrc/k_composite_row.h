@@ -1,10 +1,13 @@
 // The per-ray compositor (reference dpt_models/renderer.py:262-315): NeuS alpha from (sdf, normal), inside / outside blend with
 // the background pass, exclusive transmittance scan, weighted colour sums, eikonal partial sums - one 64-lane wavefront per ray,
-// T = N + n_outside <= 256 samples, lane l owns samples 4l .. 4l+3.
+// T = N + n_outside <= 256 samples, lane l owns samples 4l .. 4l+3. The VDN feature channels are not its business: their weighted
+// sums are a streaming launch of their own (feat_composite_kernel, rays.hip), built on the feature blend below.
 //
-// One body, two callers: composite_kernel (rays.hip; sdf / normals / colours of the ray read from HBM) and the fused shading kernel
-// (k_sdf_fwd2.h MODE 2: the workgroup that evaluated the ray's 128 points hands them over in LDS). The body carries
-// `#pragma clang fp contract(off)` like k_ray_rows.h, so both callers round like rays.hip's -ffp-contract=off build.
+// One body, three callers: composite_kernel (rays.hip) and composite_train_kernel (train_rays.hip) read sdf / normals / colours of
+// the ray from HBM; the fused shading kernel (k_sdf_fwd2.h MODE 2, k_shade_f32.h) gets them from the workgroup that evaluated the
+// ray's 128 points, in LDS. The bodies carry `#pragma clang fp contract(off)` like k_ray_rows.h, so every caller rounds like
+// rays.hip's -ffp-contract=off build. Also here, because both the forward and the adjoint (train_rays.hip) need them: the feature
+// blend and the argument checks of the compositor's entry points.
 #pragma once
 #include "k_ray_rows.h"
 
@@ -33,31 +36,25 @@ struct CompositeLdsSrc {
 struct RowOut { float num, den, c[3]; };
 typedef RowOut EikPair;
 
-// s_w / s_in: kMaxT floats of LDS scratch each (this wave's): the ray's weights and inside flags for the feature channels.
-// eik_partial may be NULL (the fused kernel publishes the returned pair itself).
+// eik_partial may be NULL (the fused kernel publishes the returned pair itself). a.feat_out is not looked at.
 template <class Src>
-VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src& src, float* s_w, float* s_in) {
+VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src& src) {
 #pragma clang fp contract(off)
     const int N = a.N, T = a.T;
     const bool has_bg = a.bg_density != nullptr;
     float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        o[k] = a.rays_o[r * 3 + k];
-        d[k] = a.rays_d[r * 3 + k];
-    }
+    load_ray(a.rays_o, a.rays_d, r, o, d);
     float inv_s = expf(a.variance[0] * 10.0f);                     // fields.py:364
     inv_s = fminf(fmaxf(inv_s, 1e-6f), 1e6f);                      // renderer.py:262
     const float car = a.cos_anneal_dev != nullptr ? a.cos_anneal_dev[0] : a.cos_anneal_ratio;      // (device scalar: graph-captured launches)
 
-    float alpha[kEPL], f[kEPL], Tr[kEPL], wgt[kEPL], col[kEPL][3], ins[kEPL];
+    float alpha[kEPL], f[kEPL], Tr[kEPL], wgt[kEPL], col[kEPL][3];
     double eik_num = 0.0, eik_den = 0.0;
 #pragma unroll
     for (int e = 0; e < kEPL; ++e) {
         const int i = kEPL * lane + e;
         alpha[e] = 0.0f;
         f[e] = 1.0f;
-        ins[e] = 0.0f;
         col[e][0] = col[e][1] = col[e][2] = 0.0f;
         if (i < T) {
             float bg_a = 0.0f;
@@ -77,17 +74,11 @@ VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src&
                 const float next_cdf = sigmoidf_(est_next * inv_s);
                 float al = ((prev_cdf - next_cdf) + 1e-5f) / (prev_cdf + 1e-5f);
                 al = fminf(fmaxf(al, 0.0f), 1.0f);
-                const float mz = a.mid_z[q];
-                const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, w = o[2] + d[2] * mz;
-                const float pn = sqrtf(x * x + y * y + w * w);
+                const float pn = sample_norm(o, d, a.mid_z[q]);
                 const float inside = pn < 1.0f ? 1.0f : 0.0f;
-                const float relax = pn < 1.2f ? 1.0f : 0.0f;
-                const float gn = sqrtf(g0 * g0 + g1 * g1 + g2 * g2) - 1.0f;
-                eik_num += (double)(relax * (gn * gn));
-                eik_den += (double)relax;
+                eikonal_add(pn, g0, g1, g2, eik_num, eik_den);
                 a.cdf[q] = prev_cdf;
                 a.inside_sphere[q] = inside;
-                ins[e] = inside;
                 float c0 = src.color(q, i, 0), c1 = src.color(q, i, 1), c2 = src.color(q, i, 2);
                 if (has_bg) {
                     const long qb = (long)r * T + i;
@@ -117,8 +108,6 @@ VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src&
             wgt[e] = alpha[e] * Tr[e];
             a.weights[(long)r * T + i] = wgt[e];
             if (a.alpha_out != nullptr) a.alpha_out[(long)r * T + i] = alpha[e];
-            s_w[i] = wgt[e];
-            s_in[i] = ins[e];
             ws += (double)wgt[e];
             c0 += (double)(col[e][0] * wgt[e]);
             c1 += (double)(col[e][1] * wgt[e]);
@@ -146,54 +135,75 @@ VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src&
             a.eik_partial[r * 2 + 1] = (float)eik_den;
         }
     }
-    // 96-channel VDN features: lanes over channels, samples streamed (weights / inside from LDS)
-    if (a.feat_out != nullptr) {
-        __builtin_amdgcn_wave_barrier();
-        const int C = a.feat_ch;
-        // lanes over channels (this lane: ch0 = lane, ch1 = lane + 64; up to 128 channels per pass), samples in groups of 8 with
-        // all 32 loads of a group issued before the first use - the plain loop waited out one memory round trip per sample and
-        // channel pass (160 us for 160 samples x 96 channels). Each channel's sum keeps the samples' order.
-        for (int c0 = 0; c0 < C; c0 += 128) {
-            const int ch0 = c0 + lane, ch1 = c0 + lane + 64;
-            const bool v0 = ch0 < C, v1 = ch1 < C;
-            double acc0 = 0.0, acc1 = 0.0;
-            for (int i0 = 0; i0 < T; i0 += 8) {
-                float fa[8][2], fb[8][2];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k;
-                    const bool fg = i < N, bg = i < T && (has_bg || i >= N) && a.bg_feat != nullptr;
-                    const long qf = ((long)r * N + i) * C, qb = ((long)r * T + i) * C;
-                    fa[k][0] = (fg && v0) ? a.feat[qf + ch0] : 0.0f;
-                    fa[k][1] = (fg && v1) ? a.feat[qf + ch1] : 0.0f;
-                    fb[k][0] = (bg && v0) ? a.bg_feat[qb + ch0] : 0.0f;
-                    fb[k][1] = (bg && v1) ? a.bg_feat[qb + ch1] : 0.0f;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k;
-                    if (i >= T) break;
-                    float f0, f1;
-                    if (i < N) {
-                        f0 = fa[k][0]; f1 = fa[k][1];
-                        if (has_bg) {
-                            const float inside = s_in[i];
-                            f0 = f0 * inside + fb[k][0] * (1.0f - inside);   // renderer.py:297-298
-                            f1 = f1 * inside + fb[k][1] * (1.0f - inside);
-                        }
-                    } else {
-                        f0 = fb[k][0]; f1 = fb[k][1];
-                    }
-                    const float wi = s_w[i];
-                    acc0 += (double)(f0 * wi);
-                    acc1 += (double)(f1 * wi);
-                }
-            }
-            if (v0) a.feat_out[(long)r * C + ch0] = (float)acc0;
-            if (v1) a.feat_out[(long)r * C + ch1] = (float)acc1;
-        }
-    }
     return RowOut{(float)eik_num, (float)eik_den, {cr, cg, cb}};
+}
+
+// ------------------------------------------------------------------------------------------
+// The VDN feature channels of a sample, lanes over channels (this lane: ch0 and ch1), blended with the background pass like the
+// colour (renderer.py:297-298). A = CompositeArgs or CompositeBwdArgs (same field names).
+// ------------------------------------------------------------------------------------------
+struct FeatRaw { float fg[2], bg[2]; };      // what memory holds for the two channels: foreground / background feature (0 where absent)
+struct FeatPair { float f0, f1; };
+template <class A>
+VDN_DEV FeatRaw feat_load(const A& a, int r, int i, int ch0, int ch1) {
+    const int N = a.N, T = a.T, C = a.feat_ch;
+    const bool v0 = ch0 < C, v1 = ch1 < C;
+    const bool fg = i < N, bg = i < T && (a.bg_density != nullptr || i >= N) && a.bg_feat != nullptr;
+    const long qf = ((long)r * N + i) * C, qb = ((long)r * T + i) * C;
+    FeatRaw v;
+    v.fg[0] = (fg && v0) ? a.feat[qf + ch0] : 0.0f;
+    v.fg[1] = (fg && v1) ? a.feat[qf + ch1] : 0.0f;
+    v.bg[0] = (bg && v0) ? a.bg_feat[qb + ch0] : 0.0f;
+    v.bg[1] = (bg && v1) ? a.bg_feat[qb + ch1] : 0.0f;
+    return v;
+}
+// inside: the sample's inside-sphere flag (1 / 0; only looked at for i < N with a background pass)
+template <class A>
+VDN_DEV FeatPair feat_mix(const A& a, int i, const FeatRaw& v, float inside) {
+#pragma clang fp contract(off)
+    if (i >= a.N) return FeatPair{v.bg[0], v.bg[1]};
+    if (a.bg_density == nullptr) return FeatPair{v.fg[0], v.fg[1]};
+    return FeatPair{v.fg[0] * inside + v.bg[0] * (1.0f - inside), v.fg[1] * inside + v.bg[1] * (1.0f - inside)};
+}
+// blended feature pair of sample i
+template <class A>
+VDN_DEV FeatPair feat_pair(const A& a, int r, int i, int ch0, int ch1, float inside) {
+    return feat_mix(a, i, feat_load(a, r, i, ch0, ch1), inside);
+}
+// ... of the 8 samples i0 .. i0+7 (those below i_end; zero behind), all 32 loads of the group issued before the first use: a plain
+// loop waits out one memory round trip per sample (160 us for 160 samples x 96 channels inside the per-ray kernel)
+template <class A>
+VDN_DEV void feat_group(const A& a, int r, int i0, int i_end, int ch0, int ch1, const float (&inside)[8], FeatPair (&f)[8]) {
+    FeatRaw v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = i0 + k < i_end ? feat_load(a, r, i0 + k, ch0, ch1) : FeatRaw{};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = i0 + k < i_end ? feat_mix(a, i0 + k, v[k], inside[k]) : FeatPair{};
+}
+
+// ------------------------------------------------------------------------------------------
+// Argument errors of the compositor's entry points (host side; include/vdn_render.h lists the codes): -1 sizes, -2 inputs,
+// -3 outputs, -4 background pass, -5 feature channels; the entry points add what is theirs behind these.
+// ------------------------------------------------------------------------------------------
+// bwd_bg_ok: the fused forward + adjoint launch also needs the adjoint's background outputs
+inline int composite_fwd_check(const VdnCompositeArgs* a, bool need_alpha_out, bool need_eik_out, bool bwd_bg_ok = true) {
+    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxT) return -1;
+    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance) return -2;
+    if (!a->weights || (need_alpha_out && !a->alpha_out) || !a->cdf || !a->inside_sphere || !a->color_out || !a->weight_sum ||
+        !a->weight_max || !a->eik_partial || (need_eik_out && !a->eik_out)) return -3;
+    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists || !bwd_bg_ok)) return -4;
+    return 0;
+}
+// what the feature channels' launch needs besides feat_out
+inline bool composite_feat_ok(const VdnCompositeArgs* a) { return a->feat && a->feat_ch > 0 && !(a->T > a->N && !a->bg_feat); }
+inline int composite_bwd_check(const VdnCompositeBwdArgs* a, bool need_eik) {
+    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxT) return -1;
+    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance ||
+        !a->alpha || !a->weights || (need_eik && !a->eik)) return -2;
+    if (!a->d_sdf || !a->d_normals || !a->d_color || !a->d_var_partial) return -3;
+    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists || !a->d_bg_density || !a->d_bg_rgb)) return -4;
+    if (a->d_feat && (!a->feat || a->feat_ch <= 0 || a->feat_ch > 128)) return -5;
+    return 0;
 }
 
 }  // namespace vdn

@@ -14,7 +14,49 @@ namespace vdn {
 
 constexpr int kRayWaves = 4;      // rays per workgroup
 constexpr int kMaxT = 256;        // max samples per ray handled (4 per lane)
-constexpr int kEPL = 4;
+constexpr int kEPL = 4;           // samples per lane: lane l owns samples kEPL*l .. kEPL*l + kEPL-1
+
+// one wave per ray, kRayWaves rays per workgroup: this wave's slot in the workgroup, this lane, the wave's ray; false when the ray
+// does not exist (the whole wave then leaves the kernel together; the per-ray kernels use no block-level barrier)
+VDN_DEV bool ray_of_wave(int B, int& wave, int& lane, int& r) {
+    wave = threadIdx.x >> 6;
+    lane = threadIdx.x & 63;
+    r = blockIdx.x * kRayWaves + wave;
+    return r < B;
+}
+__host__ __device__ inline int ray_blocks(int B) { return (B + kRayWaves - 1) / kRayWaves; }
+// host side: launch n_blocks workgroups of kRayWaves waves / a one-wave-per-ray kernel over B rays
+template <class Kernel, class... Args>
+inline void launch_ray_blocks(Kernel kernel, int n_blocks, void* stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRayWaves * 64), 0, (hipStream_t)stream, args...);
+}
+template <class Kernel, class... Args>
+inline void launch_rays(Kernel kernel, int B, void* stream, Args... args) {
+    launch_ray_blocks(kernel, ray_blocks(B), stream, args...);
+}
+
+VDN_DEV void load_ray(const float* rays_o, const float* rays_d, int r, float (&o)[3], float (&d)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o[k] = rays_o[r * 3 + k];
+        d[k] = rays_d[r * 3 + k];
+    }
+}
+// |o + d z|: THE norm every inside / relaxed-sphere test, work list and gate of the renderer compares (against 1, 1.2 or a radius);
+// one body, so that all of them round alike
+VDN_DEV float sample_norm(const float (&o)[3], const float (&d)[3], float z) {
+#pragma clang fp contract(off)
+    const float x = o[0] + d[0] * z, y = o[1] + d[1] * z, w = o[2] + d[2] * z;
+    return sqrtf(x * x + y * y + w * w);
+}
+// one sample's share of the eikonal sums (renderer.py:313-315): relax * (|n| - 1)^2 and relax, relax = [|p| < 1.2]; pn = |p|
+VDN_DEV void eikonal_add(float pn, float g0, float g1, float g2, double& num, double& den) {
+#pragma clang fp contract(off)
+    const float relax = pn < 1.2f ? 1.0f : 0.0f;
+    const float gn = sqrtf(g0 * g0 + g1 * g1 + g2 * g2) - 1.0f;
+    num += (double)(relax * (gn * gn));
+    den += (double)relax;
+}
 
 VDN_DEV double wave_incl_scan_mul(double v, int lane) {
 #pragma clang fp contract(off)
@@ -63,6 +105,26 @@ VDN_DEV void ray_excl_cumprod(const float (&f)[kEPL], float (&T)[kEPL], int lane
         run *= (double)f[e];
     }
 }
+// exclusive suffix sums over a ray: S[e] = sum_{k>i} v_k (the compositor's adjoint: sum_{j>i} dL/dw_j w_j)
+VDN_DEV void ray_excl_suffix_sum(const double (&v)[kEPL], double (&S)[kEPL], int lane) {
+#pragma clang fp contract(off)
+    double loc = 0.0;
+#pragma unroll
+    for (int e = 0; e < kEPL; ++e) loc += v[e];
+    double incl = loc;                       // inclusive suffix over lanes
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = __shfl_down(incl, off);
+        if (lane + off < 64) incl += t;
+    }
+    double run = __shfl_down(incl, 1);       // sum over higher lanes
+    if (lane == 63) run = 0.0;
+#pragma unroll
+    for (int e = kEPL - 1; e >= 0; --e) {
+        S[e] = run;
+        run += v[e];
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // one up-sampling round: z[M], sdf[M] -> n_imp new z per ray  (renderer.py:147-191, 44-74)
@@ -72,18 +134,7 @@ VDN_DEV void upsample_row(const UpsampleArgs& a, int r, int lane, int M, const f
 #pragma clang fp contract(off)
     const bool given_w = a.weights != nullptr;
     float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f};
-    if (!given_w) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o[k] = a.rays_o[r * 3 + k];
-            d[k] = a.rays_d[r * 3 + k];
-        }
-    }
-    auto radius = [&](float zz) {
-#pragma clang fp contract(off)
-        const float x = o[0] + d[0] * zz, y = o[1] + d[1] * zz, w = o[2] + d[2] * zz;
-        return sqrtf(x * x + y * y + w * w);
-    };
+    if (!given_w) load_ray(a.rays_o, a.rays_d, r, o, d);
     float alpha[kEPL], f[kEPL], T[kEPL];
 #pragma unroll
     for (int e = 0; e < kEPL; ++e) {
@@ -92,7 +143,7 @@ VDN_DEV void upsample_row(const UpsampleArgs& a, int r, int lane, int M, const f
         f[e] = 1.0f;
         if (i < M - 1) {
             const float z0 = z[i], z1 = z[i + 1], s0 = sd[i], s1 = sd[i + 1];
-            const bool inside = (radius(z0) < 1.0f) | (radius(z1) < 1.0f);
+            const bool inside = (sample_norm(o, d, z0) < 1.0f) | (sample_norm(o, d, z1) < 1.0f);
             const float mid_sdf = (s0 + s1) * 0.5f;
             float cosv = (s1 - s0) / (z1 - z0 + 1e-5f);
             const float prev_cos = (i == 0) ? 0.0f : (s0 - sd[i - 1]) / (z0 - z[i - 1] + 1e-5f);
@@ -225,6 +276,66 @@ VDN_DEV void merge_row(const MergeArgs& a, int r, int lane, float* za, float* zb
         a.z_out[(long)r * a.ld_out + npos] = nz;
         if (has_sdf) a.sdf_out[(long)r * a.ld_out + npos] = ns;
         if (lz != nullptr) { lz[npos] = nz; ls[npos] = ns; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// section length and mid-point of sample i of a sorted row z[n] (renderer.py:228-230 and 107-109); the last section is
+// sample_dist long
+// ------------------------------------------------------------------------------------------
+struct Section { float dist, mid; };
+VDN_DEV Section section(const float* z, int i, int n, float sample_dist) {
+#pragma clang fp contract(off)
+    const float z0 = z[i];
+    const float dist = (i + 1 < n) ? z[i + 1] - z0 : sample_dist;
+    return Section{dist, z0 + dist * 0.5f};
+}
+
+// ------------------------------------------------------------------------------------------
+// work lists (see include/vdn_render.h): background samples whose NeRF++ output the compositor does not multiply by
+// zero, and - for the training step - foreground samples inside the relaxed sphere. The norm test is the compositor's
+// own (sample_norm).
+// ------------------------------------------------------------------------------------------
+struct ActiveJob {
+    const float* rays_o;
+    const float* rays_d;
+    const float* mid_z;     // [B,N]
+    int B, N, T;            // T samples listed per ray; samples s >= N are always active (background mode)
+    float radius;           // background: active iff !(norm < 1); foreground (T == N): active iff norm < radius
+    bool background;
+    bool complement;        // foreground only: list what the test rejects
+    int32_t* active_idx;
+    int32_t* n_active;
+    int32_t* ray_counts;
+};
+
+VDN_DEV bool sample_active(const ActiveJob& a, int r, int s, const float (&o)[3], const float (&d)[3]) {
+    if (s >= a.N) return true;
+    const float pn = sample_norm(o, d, a.mid_z[(long)r * a.N + s]);
+    return a.background ? !(pn < 1.0f) : (pn < a.radius) != a.complement;
+}
+
+// one ray of a work list. FILL = false: count the ray's active samples into ray_counts[r]; FILL = true: write their ids behind
+// those of the rays before (ascending dense order, deterministic), the last ray also the list's length
+template <bool FILL>
+VDN_DEV void active_list_row(const ActiveJob& a, int r, int lane, const float (&o)[3], const float (&d)[3]) {
+    int base = 0;
+    if (FILL) {      // offset of this ray = sum of the counts of the rays before it
+        int acc = 0;
+        for (int i = lane; i < r; i += 64) acc += a.ray_counts[i];
+        base = (int)wave_sum((double)acc);
+    }
+    int n = 0;
+    for (int s0 = 0; s0 < a.T; s0 += 64) {
+        const int s = s0 + lane;
+        const bool act = s < a.T && sample_active(a, r, s, o, d);
+        const unsigned long long m = __ballot(act);
+        if (FILL && act) a.active_idx[base + n + __popcll(m & ((1ull << lane) - 1ull))] = r * a.T + s;
+        n += __popcll(m);
+    }
+    if (lane == 0) {
+        if (!FILL) a.ray_counts[r] = n;
+        else if (r == a.B - 1) a.n_active[0] = base + n;
     }
 }
 

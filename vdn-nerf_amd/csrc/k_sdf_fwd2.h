@@ -812,7 +812,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
         CompositeArgs cm = ex.cm;
         float* eik_partial = cm.eik_partial;
         cm.eik_partial = nullptr;                   // (stored below, write-through, ahead of the arrival count)
-        const EikPair ep = composite_row(cm, ray, lane, CompositeLdsSrc{rows, 128}, rows + 7 * 128, rows + 7 * 128 + kMaxT);
+        const EikPair ep = composite_row(cm, ray, lane, CompositeLdsSrc{rows, 128});
         // gradient_error = sum(num) / (sum(den) + 1e-5) over ALL rays (renderer.py:313-315) without a launch of its own: every ray
         // publishes its partial sums (one 8-byte write-through store, drained) and then counts itself in; the ray whose count comes
         // back last reads all partials (sc1 loads: served by L2 / memory, never by this CU's L1) and reduces them exactly as

@@ -61,8 +61,7 @@ __global__ __launch_bounds__(F32::kWaves * 64, 1) void shade_f32_kernel(SdfArgs 
     const int ray = blockIdx.x;
     float* eik_partial = cm.eik_partial;
     cm.eik_partial = nullptr;                   // (published below, ahead of the arrival count)
-    float* scratch = reinterpret_cast<float*>(smem);
-    const RowOut ep = composite_row(cm, ray, lane, CompositeGlobalSrc{cm.sdf, cm.normals, cm.color}, scratch, scratch + kMaxT);
+    const RowOut ep = composite_row(cm, ray, lane, CompositeGlobalSrc{cm.sdf, cm.normals, cm.color});
     eikonal_by_the_last_ray(cm, eik_partial, ray, ep, ticket, lane);
 }
 

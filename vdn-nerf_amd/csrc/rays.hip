@@ -11,6 +11,7 @@
 #include "k_ray_rows.h"
 #include "k_composite_row.h"
 #include "k_pixel_gather.h"
+#include "k_loss_grad.h"
 
 namespace vdn {
 
@@ -42,9 +43,8 @@ __global__ void coarse_z_kernel(CoarseArgs a) {
 
 __global__ __launch_bounds__(kRayWaves * 64) void upsample_kernel(UpsampleArgs a) {
     __shared__ float s_z[kRayWaves][kMaxT], s_sdf[kRayWaves][kMaxT], s_cdf[kRayWaves][kMaxT];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= a.B) return;            // whole wave exits together; no block-level barrier is used
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     const int M = a.M;
     float* z = s_z[wave];
     float* sd = s_sdf[wave];
@@ -59,9 +59,8 @@ __global__ __launch_bounds__(kRayWaves * 64) void upsample_kernel(UpsampleArgs a
 
 __global__ __launch_bounds__(kRayWaves * 64) void merge_kernel(MergeArgs a) {
     __shared__ float s_a[kRayWaves][kMaxT], s_b[kRayWaves][kMaxT];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= a.B) return;
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     merge_row(a, r, lane, s_a[wave], s_b[wave], nullptr, nullptr);
 }
 
@@ -69,9 +68,8 @@ __global__ __launch_bounds__(kRayWaves * 64) void merge_kernel(MergeArgs a) {
 // (renderer.py:372-386: cat_z_vals, then up_sample of the next iteration): one launch instead of two
 __global__ __launch_bounds__(kRayWaves * 64) void merge_upsample_kernel(MergeArgs m, UpsampleArgs u) {
     __shared__ float s_a[kRayWaves][kMaxT], s_b[kRayWaves][kMaxT], s_z[kRayWaves][kMaxT], s_sdf[kRayWaves][kMaxT];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= m.B) return;
+    int wave, lane, r;
+    if (!ray_of_wave(m.B, wave, lane, r)) return;
     merge_row(m, r, lane, s_a[wave], s_b[wave], s_z[wave], s_sdf[wave]);
     __builtin_amdgcn_wave_barrier();
     upsample_row(u, r, lane, m.M + m.K, s_z[wave], s_sdf[wave], s_a[wave]);     // the old row's scratch serves as the cdf row
@@ -84,10 +82,9 @@ __global__ void sections_kernel(SectionArgs a) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.B * a.n) return;
     const int r = idx / a.n, i = idx % a.n;
-    const float z0 = a.z[(long)r * a.ld + i];
-    const float dist = (i + 1 < a.n) ? a.z[(long)r * a.ld + i + 1] - z0 : a.sample_dist;
-    a.dists[(long)r * a.n + i] = dist;
-    a.mid_z[(long)r * a.n + i] = z0 + dist * 0.5f;
+    const Section sc = section(a.z + (long)r * a.ld, i, a.n, a.sample_dist);
+    a.dists[(long)r * a.n + i] = sc.dist;
+    a.mid_z[(long)r * a.n + i] = sc.mid;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -95,29 +92,25 @@ __global__ void sections_kernel(SectionArgs a) {
 // scan and weighted sums (renderer.py:262-315). One wave per ray, T = N + n_outside <= 256.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kRayWaves * 64) void composite_kernel(CompositeArgs a) {
-    __shared__ float s_w[kRayWaves][kMaxT], s_in[kRayWaves][kMaxT];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= a.B) return;
-    composite_row(a, r, lane, CompositeGlobalSrc{a.sdf, a.normals, a.color}, s_w[wave], s_in[wave]);
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
+    composite_row(a, r, lane, CompositeGlobalSrc{a.sdf, a.normals, a.color});
 }
 
 // d_feats = sum_i w_i * feature_i (renderer.py:306-308) as its own launch, four waves per ray (the per-ray compositor has two
 // waves per CU: 44 us for these 56 MB inside it): wave w sums its quarter of the samples in order, lanes over channels, the
 // four partial sums are added in wave order.
 // fl (the training step with the VDN head, vdn_composite_fwd_train): also d loss / d render_feats of the depth-feature term
-// (dpt_runner.py:239-243 with mask = 1: loss_kernel's expressions, train_opt.hip) from the sums this block has just made
+// (dpt_runner.py:239-243 with mask = 1: l1_grad, k_loss_grad.h, as in loss_kernel) from the sums this block has just made
 struct FeatLoss {
     const float* gt_feats;     // [B,C] or NULL
     float* g_feats;            // [B,C]
     float depth_weight, grad_scale;
 };
 VDN_DEV void feat_loss_grad(const CompositeArgs& a, const FeatLoss& fl, long idx, float f) {
-    const float mask_sum = (float)a.B + 1e-5f;                     // dpt_runner.py:213 with mask = ones
     const float m = 1.0f;
     const float e = (f - fl.gt_feats[idx]) * m;
-    const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-    fl.g_feats[idx] = sgn * m / mask_sum * fl.depth_weight * fl.grad_scale;
+    fl.g_feats[idx] = l1_grad(e, m, mask_sum_of_ones(a.B)) * fl.depth_weight * fl.grad_scale;
 }
 
 __global__ __launch_bounds__(256) void feat_composite_kernel(CompositeArgs a, FeatLoss fl) {
@@ -125,42 +118,26 @@ __global__ __launch_bounds__(256) void feat_composite_kernel(CompositeArgs a, Fe
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x;
     const int N = a.N, T = a.T, C = a.feat_ch;
-    const bool has_bg = a.bg_density != nullptr;
     const int per = (T + 3) / 4, i_begin = wave * per, i_end = min(T, i_begin + per);
     for (int c0 = 0; c0 < C; c0 += 128) {
         const int ch0 = c0 + lane, ch1 = c0 + lane + 64;
         const bool v0 = ch0 < C, v1 = ch1 < C;
         double acc0 = 0.0, acc1 = 0.0;
         for (int i0 = i_begin; i0 < i_end; i0 += 8) {
-            float fa[8][2], fb[8][2], wi[8], ins[8];
+            float wi[8], ins[8];
+            FeatPair f[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int i = i0 + k;
-                const bool in = i < i_end, fg = in && i < N, bg = in && (has_bg || i >= N) && a.bg_feat != nullptr;
-                const long qf = ((long)r * N + i) * C, qb = ((long)r * T + i) * C;
-                fa[k][0] = (fg && v0) ? a.feat[qf + ch0] : 0.0f;
-                fa[k][1] = (fg && v1) ? a.feat[qf + ch1] : 0.0f;
-                fb[k][0] = (bg && v0) ? a.bg_feat[qb + ch0] : 0.0f;
-                fb[k][1] = (bg && v1) ? a.bg_feat[qb + ch1] : 0.0f;
-                wi[k] = in ? a.weights[(long)r * T + i] : 0.0f;
-                ins[k] = fg ? a.inside_sphere[(long)r * N + i] : 0.0f;
+                wi[k] = i < i_end ? a.weights[(long)r * T + i] : 0.0f;
+                ins[k] = (i < i_end && i < N) ? a.inside_sphere[(long)r * N + i] : 0.0f;
             }
+            feat_group(a, r, i0, i_end, ch0, ch1, ins, f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const int i = i0 + k;
-                if (i >= i_end) break;
-                float f0, f1;
-                if (i < N) {
-                    f0 = fa[k][0]; f1 = fa[k][1];
-                    if (has_bg) {
-                        f0 = f0 * ins[k] + fb[k][0] * (1.0f - ins[k]);   // renderer.py:297-298
-                        f1 = f1 * ins[k] + fb[k][1] * (1.0f - ins[k]);
-                    }
-                } else {
-                    f0 = fb[k][0]; f1 = fb[k][1];
-                }
-                acc0 += (double)(f0 * wi[k]);
-                acc1 += (double)(f1 * wi[k]);
+                if (i0 + k >= i_end) break;
+                acc0 += (double)(f[k].f0 * wi[k]);          // each channel's sum keeps the samples' order
+                acc1 += (double)(f[k].f1 * wi[k]);
             }
         }
         s_part[wave][lane] = acc0;
@@ -199,19 +176,14 @@ __global__ void eikonal_reduce_kernel(const float* partial, int B, float* out3) 
     }
 }
 
-// The eikonal sums of composite_kernel on their own (same element -> lane mapping, same expressions, same double-precision
-// wave sums: bit-identical partials), for the data-parallel step, which reduces them over the ranks early (vdn_eikonal_terms).
+// The eikonal sums of composite_kernel on their own (same element -> lane mapping, the same sample_norm / eikonal_add, same
+// double-precision wave sums: bit-identical partials), for the data-parallel step, which reduces them over the ranks early (vdn_eikonal_terms).
 __global__ __launch_bounds__(kRayWaves * 64) void eikonal_terms_kernel(VdnEikonalArgs a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= a.B) return;
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     const int N = a.N;
     float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        o[k] = a.rays_o[r * 3 + k];
-        d[k] = a.rays_d[r * 3 + k];
-    }
+    load_ray(a.rays_o, a.rays_d, r, o, d);
     double eik_num = 0.0, eik_den = 0.0;
 #pragma unroll
     for (int e = 0; e < kEPL; ++e) {
@@ -219,13 +191,7 @@ __global__ __launch_bounds__(kRayWaves * 64) void eikonal_terms_kernel(VdnEikona
         if (i < N) {
             const long q = (long)r * N + i;
             const float g0 = a.normals[q * 3], g1 = a.normals[q * 3 + 1], g2 = a.normals[q * 3 + 2];
-            const float mz = a.mid_z[q];
-            const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, w = o[2] + d[2] * mz;
-            const float pn = sqrtf(x * x + y * y + w * w);
-            const float relax = pn < 1.2f ? 1.0f : 0.0f;
-            const float gn = sqrtf(g0 * g0 + g1 * g1 + g2 * g2) - 1.0f;
-            eik_num += (double)(relax * (gn * gn));
-            eik_den += (double)relax;
+            eikonal_add(sample_norm(o, d, a.mid_z[q]), g0, g1, g2, eik_num, eik_den);
         }
     }
     eik_num = wave_sum(eik_num);
@@ -294,7 +260,7 @@ extern "C" int vdn_upsample_round(const VdnUpsampleArgs* a, void* stream) {
     if (!a || a->B <= 0 || !a->z || !a->new_z || !a->u) return -1;
     if (a->weights == nullptr ? (!a->sdf || !a->rays_o || !a->rays_d) : a->w_ld < a->M - 1) return -1;
     if (a->M < 2 || a->M > kMaxT || a->n_imp < 1 || a->n_imp > 64 || a->ld < a->M) return -2;
-    hipLaunchKernelGGL(upsample_kernel, dim3((a->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *a);
+    launch_rays(upsample_kernel, a->B, stream, *a);
     return (int)hipGetLastError();
 }
 
@@ -302,71 +268,25 @@ extern "C" int vdn_merge_sorted(const VdnMergeArgs* a, void* stream) {
     if (!a || a->B <= 0 || !a->z || !a->new_z || !a->z_out) return -1;
     if (a->M < 1 || a->K < 1 || a->K > 64 || a->M + a->K > kMaxT || a->ld < a->M || a->ld_out < a->M + a->K) return -2;
     if (a->sdf && (!a->new_sdf || !a->sdf_out)) return -3;
-    hipLaunchKernelGGL(merge_kernel, dim3((a->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *a);
+    launch_rays(merge_kernel, a->B, stream, *a);
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
-// work lists (see include/vdn_render.h): background samples whose NeRF++ output the compositor does not multiply by
-// zero, and - for the training step - foreground samples inside the relaxed sphere. The norm test is the compositor's
-// own (composite_kernel above: same expression, same -ffp-contract=off file).
+// work lists (include/vdn_render.h; ActiveJob / active_list_row: k_ray_rows.h): a count launch, then a fill launch
 // ------------------------------------------------------------------------------------------
-struct ActiveJob {
-    const float* rays_o;
-    const float* rays_d;
-    const float* mid_z;     // [B,N]
-    int B, N, T;            // T samples listed per ray; samples s >= N are always active (background mode)
-    float radius;           // background: active iff !(norm < 1); foreground (T == N): active iff norm < radius
-    bool background;
-    bool complement;        // foreground only: list what the test rejects
-    int32_t* active_idx;
-    int32_t* n_active;
-    int32_t* ray_counts;
-};
-
-VDN_DEV bool sample_active(const ActiveJob& a, int r, int s, const float (&o)[3], const float (&d)[3]) {
-    if (s >= a.N) return true;
-    const float mz = a.mid_z[(long)r * a.N + s];
-    const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, w = o[2] + d[2] * mz;
-    const float pn = sqrtf(x * x + y * y + w * w);
-    return a.background ? !(pn < 1.0f) : (pn < a.radius) != a.complement;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(kRayWaves * 64) void active_list_kernel(ActiveJob a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRayWaves + wave;
-    if (r >= a.B) return;
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        o[k] = a.rays_o[r * 3 + k];
-        d[k] = a.rays_d[r * 3 + k];
-    }
-    int base = 0;
-    if (FILL) {      // offset of this ray = sum of the counts of the rays before it (ascending dense order, deterministic)
-        int acc = 0;
-        for (int i = lane; i < r; i += 64) acc += a.ray_counts[i];
-        base = (int)wave_sum((double)acc);
-    }
-    int n = 0;
-    for (int s0 = 0; s0 < a.T; s0 += 64) {
-        const int s = s0 + lane;
-        const bool act = s < a.T && sample_active(a, r, s, o, d);
-        const unsigned long long m = __ballot(act);
-        if (FILL && act) a.active_idx[base + n + __popcll(m & ((1ull << lane) - 1ull))] = r * a.T + s;
-        n += __popcll(m);
-    }
-    if (lane == 0) {
-        if (!FILL) a.ray_counts[r] = n;
-        else if (r == a.B - 1) a.n_active[0] = base + n;
-    }
+    load_ray(a.rays_o, a.rays_d, r, o, d);
+    active_list_row<FILL>(a, r, lane, o, d);
 }
 
 static int launch_active(const ActiveJob& j, void* stream) {
-    const dim3 grid((j.B + kRayWaves - 1) / kRayWaves), block(kRayWaves * 64);
-    hipLaunchKernelGGL(active_list_kernel<false>, grid, block, 0, (hipStream_t)stream, j);
-    hipLaunchKernelGGL(active_list_kernel<true>, grid, block, 0, (hipStream_t)stream, j);
+    launch_rays(active_list_kernel<false>, j.B, stream, j);
+    launch_rays(active_list_kernel<true>, j.B, stream, j);
     return (int)hipGetLastError();
 }
 
@@ -386,21 +306,17 @@ extern "C" int vdn_foreground_active(const VdnForegroundActiveArgs* a, void* str
 
 // The training step's per-ray preparation fused (include/vdn_render.h: VdnTrainPrepArgs): every one of the launches it
 // replaces costs ~4.5 us of fixed time for a few hundred bytes per ray. Pass 0: both section sets + both per-ray counts;
-// pass 1 (blocks [0, nb): foreground, [nb, 2 nb): background): the fill passes. Same expressions as sections_kernel /
-// active_list_kernel (this file is built with -ffp-contract=off: the norm tests are the compositor's own).
+// pass 1 (blocks [0, nb): foreground, [nb, 2 nb): background): the fill passes. The same section / active_list_row as
+// sections_kernel / active_list_kernel.
 template <int PASS>
 __global__ __launch_bounds__(kRayWaves * 64) void train_prep_kernel(TrainPrepArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int nb = (a.B + kRayWaves - 1) / kRayWaves;
+    const int nb = ray_blocks(a.B);
     const bool second = PASS == 1 && (int)blockIdx.x >= nb;
     const int r = ((int)blockIdx.x - (second ? nb : 0)) * kRayWaves + wave;
     if (r >= a.B) return;
     float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        o[k] = a.rays_o[r * 3 + k];
-        d[k] = a.rays_d[r * 3 + k];
-    }
+    load_ray(a.rays_o, a.rays_d, r, o, d);
     if (PASS == 0) {
         // z_feed = stable merge of the inside and the outside depths; both rows and the merged one stay in LDS for the sections
         __shared__ float s_a[kRayWaves][kMaxT], s_b[kRayWaves][kMaxT], s_f[kRayWaves][kMaxT], s_x[kRayWaves][kMaxT], s_z[kRayWaves][kMaxT];
@@ -421,48 +337,26 @@ __global__ __launch_bounds__(kRayWaves * 64) void train_prep_kernel(TrainPrepArg
         const float* zi = s_a[wave];
         const float* zf = s_f[wave];
         for (int i = lane; i < a.N; i += 64) {
-            const float z0 = zi[i];
-            const float dist = (i + 1 < a.N) ? zi[i + 1] - z0 : a.sample_dist;
-            a.dists[(long)r * a.N + i] = dist;
-            a.mid_z[(long)r * a.N + i] = z0 + dist * 0.5f;
+            const Section sc = section(zi, i, a.N, a.sample_dist);
+            a.dists[(long)r * a.N + i] = sc.dist;
+            a.mid_z[(long)r * a.N + i] = sc.mid;
         }
         for (int i = lane; i < a.T; i += 64) {
-            const float z0 = zf[i];
-            const float dist = (i + 1 < a.T) ? zf[i + 1] - z0 : a.sample_dist;
-            a.bg_dists[(long)r * a.T + i] = dist;
-            a.bg_mid[(long)r * a.T + i] = z0 + dist * 0.5f;
+            const Section sc = section(zf, i, a.T, a.sample_dist);
+            a.bg_dists[(long)r * a.T + i] = sc.dist;
+            a.bg_mid[(long)r * a.T + i] = sc.mid;
         }
         __builtin_amdgcn_s_waitcnt(0);          // this wave reads back its own mid_z row below
         __builtin_amdgcn_wave_barrier();
     }
     // the two lists: foreground (inside samples with |p| < radius) and background (not inside the unit sphere, plus every
-    // outside sample)
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (PASS == 1 && (which == 1) != second) continue;
-        if (which == 0 && a.fg_active_idx == nullptr) continue;
-        const ActiveJob j = which == 0
-            ? ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.N, a.fg_radius, false, false, a.fg_active_idx, a.fg_n_active, a.fg_ray_counts}
-            : ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.T, 1.0f, true, false, a.bg_active_idx, a.bg_n_active, a.bg_ray_counts};
-        int base = 0;
-        if (PASS == 1) {
-            int acc = 0;
-            for (int i = lane; i < r; i += 64) acc += j.ray_counts[i];
-            base = (int)wave_sum((double)acc);
-        }
-        int n = 0;
-        for (int s0 = 0; s0 < j.T; s0 += 64) {
-            const int s = s0 + lane;
-            const bool act = s < j.T && sample_active(j, r, s, o, d);
-            const unsigned long long m = __ballot(act);
-            if (PASS == 1 && act) j.active_idx[base + n + __popcll(m & ((1ull << lane) - 1ull))] = r * j.T + s;
-            n += __popcll(m);
-        }
-        if (lane == 0) {
-            if (PASS == 0) j.ray_counts[r] = n;
-            else if (r == j.B - 1) j.n_active[0] = base + n;
-        }
-    }
+    // outside sample); pass 1 fills one of them per block
+    if (a.fg_active_idx != nullptr && !second)
+        active_list_row<PASS == 1>(ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.N, a.fg_radius, false, false, a.fg_active_idx, a.fg_n_active, a.fg_ray_counts},
+                                   r, lane, o, d);
+    if (PASS == 0 || second)
+        active_list_row<PASS == 1>(ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.T, 1.0f, true, false, a.bg_active_idx, a.bg_n_active, a.bg_ray_counts},
+                                   r, lane, o, d);
 }
 
 extern "C" int vdn_train_prep(const VdnTrainPrepArgs* a, void* stream) {
@@ -472,9 +366,8 @@ extern "C" int vdn_train_prep(const VdnTrainPrepArgs* a, void* stream) {
     if (a->new_z && (a->M_old < 1 || a->M_old >= a->N || a->N - a->M_old > 64)) return -2;
     if (!a->bg_active_idx || !a->bg_n_active || !a->bg_ray_counts) return -3;
     if (a->fg_active_idx && (!a->fg_n_active || !a->fg_ray_counts || !(a->fg_radius > 0.0f))) return -4;
-    const int nb = (a->B + kRayWaves - 1) / kRayWaves;
-    hipLaunchKernelGGL(train_prep_kernel<0>, dim3(nb), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *a);
-    hipLaunchKernelGGL(train_prep_kernel<1>, dim3(2 * nb), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *a);
+    launch_rays(train_prep_kernel<0>, a->B, stream, *a);
+    launch_ray_blocks(train_prep_kernel<1>, 2 * ray_blocks(a->B), stream, *a);      // one set of blocks per list
     return (int)hipGetLastError();
 }
 
@@ -483,7 +376,7 @@ extern "C" int vdn_merge_upsample(const VdnMergeArgs* m, const VdnUpsampleArgs* 
     if (m->M < 1 || m->K < 1 || m->K > 64 || m->M + m->K > kMaxT || m->ld < m->M || m->ld_out < m->M + m->K) return -2;
     if (u->B != m->B || u->M != m->M + m->K || u->weights || !u->rays_o || !u->rays_d || !u->u || !u->new_z ||
         u->n_imp < 1 || u->n_imp > 64) return -3;
-    hipLaunchKernelGGL(merge_upsample_kernel, dim3((m->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *m, *u);
+    launch_rays(merge_upsample_kernel, m->B, stream, *m, *u);
     return (int)hipGetLastError();
 }
 
@@ -497,7 +390,7 @@ extern "C" int vdn_sections(const VdnSectionArgs* a, void* stream) {
 extern "C" int vdn_eikonal_terms(const VdnEikonalArgs* a, void* stream) {
     if (!a || a->B <= 0 || a->N <= 0 || a->N > kMaxT) return -1;
     if (!a->rays_o || !a->rays_d || !a->mid_z || !a->normals || !a->eik_partial || !a->eik_out) return -2;
-    hipLaunchKernelGGL(eikonal_terms_kernel, dim3((a->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, *a);
+    launch_rays(eikonal_terms_kernel, a->B, stream, *a);
     hipLaunchKernelGGL(eikonal_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->eik_partial, a->B, a->eik_out);
     return (int)hipGetLastError();
 }
@@ -521,29 +414,19 @@ extern "C" int vdn_feat_composite(const VdnCompositeArgs* a, void* stream) {
 // (vdn_composite_bwd_train) takes the denominator from the foreground work list, the scalars are reduced off the critical path.
 extern "C" int vdn_composite_fwd_train(const VdnCompositeArgs* a, const float* gt_feats, float* g_feats, float depth_weight, float grad_scale,
                                        void* stream) {
-    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxT || !gt_feats || !g_feats) return -1;
-    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance) return -2;
-    if (!a->weights || !a->cdf || !a->inside_sphere || !a->color_out || !a->weight_sum || !a->weight_max || !a->eik_partial) return -3;
-    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists)) return -4;
-    if (!a->feat_out || !a->feat || a->feat_ch <= 0 || (a->T > a->N && !a->bg_feat)) return -5;
-    VdnCompositeArgs per_ray = *a;
-    per_ray.feat_out = nullptr;
-    hipLaunchKernelGGL(composite_kernel, dim3((a->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, per_ray);
+    if (!gt_feats || !g_feats) return -1;
+    if (const int err = composite_fwd_check(a, false, false)) return err;
+    if (!a->feat_out || !composite_feat_ok(a)) return -5;
+    launch_rays(composite_kernel, a->B, stream, *a);
     hipLaunchKernelGGL(feat_composite_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a, FeatLoss{gt_feats, g_feats, depth_weight, grad_scale});
     return (int)hipGetLastError();
 }
 
 extern "C" int vdn_alpha_composite_fwd(const VdnCompositeArgs* a, void* stream) {
-    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxT) return -1;
-    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance) return -2;
-    if (!a->weights || !a->cdf || !a->inside_sphere || !a->color_out || !a->weight_sum || !a->weight_max ||
-        !a->eik_partial || !a->eik_out) return -3;
-    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists)) return -4;
-    if (a->feat_out && (!a->feat || a->feat_ch <= 0 || (a->T > a->N && !a->bg_feat))) return -5;
-    VdnCompositeArgs per_ray = *a;
-    per_ray.feat_out = nullptr;                   // the feature channels have their own launch (feat_composite_kernel)
-    hipLaunchKernelGGL(composite_kernel, dim3((a->B + kRayWaves - 1) / kRayWaves), dim3(kRayWaves * 64), 0, (hipStream_t)stream, per_ray);
-    if (a->feat_out != nullptr)
+    if (const int err = composite_fwd_check(a, false, true)) return err;
+    if (a->feat_out && !composite_feat_ok(a)) return -5;
+    launch_rays(composite_kernel, a->B, stream, *a);
+    if (a->feat_out != nullptr)                   // the feature channels have their own launch
         hipLaunchKernelGGL(feat_composite_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a, FeatLoss{});
     hipLaunchKernelGGL(eikonal_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->eik_partial, a->B, a->eik_out);
     return (int)hipGetLastError();

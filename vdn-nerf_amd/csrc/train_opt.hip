@@ -1,6 +1,7 @@
 // Loss + output gradients (dpt_runner.py:208-243) and Adam (dpt_runner.py:144,254) as single launches.
 #include "vdn_common.h"
 #include "vdn_kernels.h"
+#include "k_loss_grad.h"
 
 namespace vdn {
 
@@ -31,8 +32,7 @@ __global__ __launch_bounds__(1024) void loss_kernel(LossArgs a) {
             const float e = diff * m;
             l1 += (double)fabsf(e);
             sq += (double)(diff * diff * m);
-            const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-            a.g_color[r * 3 + k] = sgn * m / mask_sum * a.grad_scale;
+            a.g_color[r * 3 + k] = l1_grad(e, m, mask_sum) * a.grad_scale;
         }
         if (a.mask_weight != 0.0f && a.g_weights != nullptr) {
             // weight_sum in double, like the compositor's own: next to the upper clip gate 1 - ws is ~1e-3, so the BCE
@@ -67,8 +67,7 @@ __global__ __launch_bounds__(1024) void loss_kernel(LossArgs a) {
                 if (idx >= n) break;
                 const float e = (fv[k] - gv[k]) * mv[k];
                 dl1 += (double)fabsf(e);
-                const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-                a.g_feats[idx] = sgn * mv[k] / mask_sum * a.depth_weight * a.grad_scale;
+                a.g_feats[idx] = l1_grad(e, mv[k], mask_sum) * a.depth_weight * a.grad_scale;
             }
         }
     }

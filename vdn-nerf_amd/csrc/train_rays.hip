@@ -6,18 +6,9 @@
 #include "vdn_common.h"
 #include "vdn_kernels.h"
 #include "k_composite_row.h"
+#include "k_loss_grad.h"
 
 namespace vdn {
-
-constexpr int kRW = 4;
-constexpr int kMaxTB = 256;
-constexpr int kE = 4;
-
-VDN_DEV double wsum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // The 96 feature channels outside the per-ray kernel (CompositeBwdArgs.feat_scratch = [fd (B*T) | cf (B*N) | cb (B*T)]):
 // one wave per sample row, lanes over channels, many waves per CU - plain streaming kernels.
@@ -29,31 +20,16 @@ __global__ __launch_bounds__(256) void feat_dot_kernel(CompositeBwdArgs a) {
     const int N = a.N, T = a.T, C = a.feat_ch;
     if (row >= (long)a.B * T) return;
     const int r = (int)(row / T), i = (int)(row - (long)r * T);
-    const bool has_bg = a.bg_density != nullptr;
-    float v0 = 0.0f, v1 = 0.0f;
-    float b0 = 0.0f, b1 = 0.0f;
-    if (has_bg && a.bg_feat != nullptr) {
-        if (lane < C) b0 = a.bg_feat[row * C + lane];
-        if (lane + 64 < C) b1 = a.bg_feat[row * C + lane + 64];
+    float inside = 0.0f;
+    if (i < N && a.bg_density != nullptr) {
+        float o[3], d[3];
+        load_ray(a.rays_o, a.rays_d, r, o, d);
+        inside = sample_norm(o, d, a.mid_z[(long)r * N + i]) < 1.0f ? 1.0f : 0.0f;
     }
-    if (i < N) {
-        const long q = (long)r * N + i;
-        if (lane < C) v0 = a.feat[q * C + lane];
-        if (lane + 64 < C) v1 = a.feat[q * C + lane + 64];
-        if (has_bg) {
-            const float mz = a.mid_z[q];
-            const float x = a.rays_o[r * 3] + a.rays_d[r * 3] * mz, y = a.rays_o[r * 3 + 1] + a.rays_d[r * 3 + 1] * mz,
-                        zz = a.rays_o[r * 3 + 2] + a.rays_d[r * 3 + 2] * mz;
-            const float inside = sqrtf(x * x + y * y + zz * zz) < 1.0f ? 1.0f : 0.0f;
-            v0 = v0 * inside + b0 * (1.0f - inside);
-            v1 = v1 * inside + b1 * (1.0f - inside);
-        }
-    } else {
-        v0 = b0; v1 = b1;
-    }
+    const FeatPair v = feat_pair(a, r, i, lane, lane + 64, inside);
     float part = 0.0f;
-    if (lane < C) part += a.g_feat[(long)r * C + lane] * v0;
-    if (lane + 64 < C) part += a.g_feat[(long)r * C + lane + 64] * v1;
+    if (lane < C) part += a.g_feat[(long)r * C + lane] * v.f0;
+    if (lane + 64 < C) part += a.g_feat[(long)r * C + lane + 64] * v.f1;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
     if (lane == 0) a.feat_scratch[row] = part;
@@ -94,10 +70,9 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
     const bool has_bg = a.bg_density != nullptr;
     const bool has_feat = a.d_feat != nullptr && a.g_feat != nullptr;
     float o[3], d[3], gc[3] = {0.0f, 0.0f, 0.0f};
+    load_ray(a.rays_o, a.rays_d, r, o, d);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        o[k] = a.rays_o[r * 3 + k];
-        d[k] = a.rays_d[r * 3 + k];
         if (ov.on) gc[k] = ov.gc[k];
         else if (a.g_color != nullptr) gc[k] = a.g_color[r * 3 + k];
     }
@@ -117,7 +92,7 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
     // instead of by the sample's owner lane walking its own row (64 lanes on 64 different rows: 268 us per launch).
     // s_fd[i] = sum_ch g_feat[ch] * blended feature(i, ch): the features' share of dL/dw_i; s_cf / s_cb: the coefficients of
     // g_feat in d_feat[i, :] / d_bg_feat[i, :], filled by the owner lanes below.
-    __shared__ float s_fd[kRW][kMaxTB], s_cf[kRW][kMaxTB], s_cb[kRW][kMaxTB];
+    __shared__ float s_fd[kRayWaves][kMaxT], s_cf[kRayWaves][kMaxT], s_cb[kRayWaves][kMaxT];
     float gfa = 0.0f, gfb = 0.0f;               // this lane's channels of g_feat: lane, lane + 64
     const bool ext_feat = has_feat && a.feat_scratch != nullptr;       // feat_dot_kernel ran before, feat_outer_kernel runs after
     if (ext_feat) {
@@ -127,42 +102,16 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
         if (lane < C) gfa = a.g_feat[(long)r * C + lane];
         if (lane + 64 < C) gfb = a.g_feat[(long)r * C + lane + 64];
         for (int i0 = 0; i0 < T; i0 += 8) {
-            float fa[8][2], fb[8][2], insd[8];
+            float insd[8];
+            FeatPair v[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int i = i0 + k;
-                fa[k][0] = fa[k][1] = fb[k][0] = fb[k][1] = 0.0f;
-                insd[k] = 0.0f;
-                if (i >= T) continue;
-                const long qt = (long)r * T + i;
-                if (i < N) {
-                    const long q = (long)r * N + i;
-                    const float mz = a.mid_z[q];
-                    const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, zz = o[2] + d[2] * mz;
-                    insd[k] = sqrtf(x * x + y * y + zz * zz) < 1.0f ? 1.0f : 0.0f;
-                    if (lane < C) fa[k][0] = a.feat[q * C + lane];
-                    if (lane + 64 < C) fa[k][1] = a.feat[q * C + lane + 64];
-                }
-                if (has_bg && a.bg_feat != nullptr) {
-                    if (lane < C) fb[k][0] = a.bg_feat[qt * C + lane];
-                    if (lane + 64 < C) fb[k][1] = a.bg_feat[qt * C + lane + 64];
-                }
-            }
+            for (int k = 0; k < 8; ++k) insd[k] = i0 + k < N ? (sample_norm(o, d, a.mid_z[(long)r * N + i0 + k]) < 1.0f ? 1.0f : 0.0f) : 0.0f;
+            feat_group(a, r, i0, T, lane, lane + 64, insd, v);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int i = i0 + k;
                 if (i >= T) break;
-                float v0, v1;
-                if (i < N) {
-                    v0 = fa[k][0]; v1 = fa[k][1];
-                    if (has_bg) {
-                        v0 = v0 * insd[k] + fb[k][0] * (1.0f - insd[k]);
-                        v1 = v1 * insd[k] + fb[k][1] * (1.0f - insd[k]);
-                    }
-                } else {
-                    v0 = fb[k][0]; v1 = fb[k][1];
-                }
-                float part = gfa * v0 + gfb * v1;
+                float part = gfa * v[k].f0 + gfb * v[k].f1;
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
                 if (lane == 0) s_fd[wave][i] = part;
@@ -170,12 +119,12 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
         }
         __builtin_amdgcn_wave_barrier();
     }
-    float alpha[kE], w[kE], f[kE], Tr[kE], Wb[kE], ins[kE];
+    float alpha[kEPL], w[kEPL], f[kEPL], Tr[kEPL], Wb[kEPL], ins[kEPL], pn[kEPL];
     // pass 1: dL/dw_i
 #pragma unroll
-    for (int e = 0; e < kE; ++e) {
-        const int i = kE * lane + e;
-        alpha[e] = 0.0f; w[e] = 0.0f; f[e] = 1.0f; Wb[e] = 0.0f; ins[e] = 0.0f;
+    for (int e = 0; e < kEPL; ++e) {
+        const int i = kEPL * lane + e;
+        alpha[e] = 0.0f; w[e] = 0.0f; f[e] = 1.0f; Wb[e] = 0.0f; ins[e] = 0.0f; pn[e] = 0.0f;
         if (i < T) {
             const long qt = (long)r * T + i;
             alpha[e] = a.alpha[qt];
@@ -185,9 +134,8 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
             float inside = 0.0f;
             if (i < N) {
                 const long q = (long)r * N + i;
-                const float mz = a.mid_z[q];
-                const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, zz = o[2] + d[2] * mz;
-                inside = sqrtf(x * x + y * y + zz * zz) < 1.0f ? 1.0f : 0.0f;
+                pn[e] = sample_norm(o, d, a.mid_z[q]);              // the sample's norm, once: inside here, relax below
+                inside = pn[e] < 1.0f ? 1.0f : 0.0f;
                 c0 = a.color[q * 3]; c1 = a.color[q * 3 + 1]; c2 = a.color[q * 3 + 2];
                 if (has_bg) {
                     c0 = c0 * inside + a.bg_rgb[qt * 3] * (1.0f - inside);
@@ -205,48 +153,16 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
         }
     }
     // transmittance (exclusive product) and suffix sums S_i = sum_{j>i} Wb_j w_j
-    {
-        double loc = 1.0;
+    ray_excl_cumprod(f, Tr, lane);
+    double ww[kEPL], suf[kEPL];
 #pragma unroll
-        for (int e = 0; e < kE; ++e) loc *= (double)f[e];
-        double incl = loc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double t = __shfl_up(incl, off);
-            if (lane >= off) incl *= t;
-        }
-        double run = __shfl_up(incl, 1);
-        if (lane == 0) run = 1.0;
-#pragma unroll
-        for (int e = 0; e < kE; ++e) {
-            Tr[e] = (float)run;
-            run *= (double)f[e];
-        }
-    }
-    double suf[kE];
-    {
-        double loc = 0.0;
-#pragma unroll
-        for (int e = 0; e < kE; ++e) loc += (double)Wb[e] * (double)w[e];
-        double incl = loc;                       // inclusive suffix over lanes
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double t = __shfl_down(incl, off);
-            if (lane + off < 64) incl += t;
-        }
-        double run = __shfl_down(incl, 1);       // sum over higher lanes
-        if (lane == 63) run = 0.0;
-#pragma unroll
-        for (int e = kE - 1; e >= 0; --e) {
-            suf[e] = run;
-            run += (double)Wb[e] * (double)w[e];
-        }
-    }
+    for (int e = 0; e < kEPL; ++e) ww[e] = (double)Wb[e] * (double)w[e];
+    ray_excl_suffix_sum(ww, suf, lane);
     double dvar = 0.0;
     float ddir[3] = {0.0f, 0.0f, 0.0f};        // sum_i d true_cos_i * normal_i  (true_cos = rays_d . normal, renderer.py:265)
 #pragma unroll
-    for (int e = 0; e < kE; ++e) {
-        const int i = kE * lane + e;
+    for (int e = 0; e < kEPL; ++e) {
+        const int i = kEPL * lane + e;
         if (i >= T) continue;
         const long qt = (long)r * T + i;
         const float dalpha = Wb[e] * Tr[e] - (float)(suf[e] / (double)f[e]);
@@ -291,9 +207,7 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
                 ddir[0] += dtc * g0; ddir[1] += dtc * g1; ddir[2] += dtc * g2;
             }
             // eikonal: d/dn of relax*(|n|-1)^2 / (den+1e-5)
-            const float mz = a.mid_z[q];
-            const float x = o[0] + d[0] * mz, y = o[1] + d[1] * mz, zz = o[2] + d[2] * mz;
-            const float relax = sqrtf(x * x + y * y + zz * zz) < 1.2f ? 1.0f : 0.0f;
+            const float relax = pn[e] < 1.2f ? 1.0f : 0.0f;
             const float gn = sqrtf(g0 * g0 + g1 * g1 + g2 * g2);
             const float ke = gn > 0.0f ? g_eik * relax * 2.0f * (gn - 1.0f) / (gn * eik_den) : 0.0f;
             a.d_normals[q * 3] = dtc * d[0] + ke * g0;
@@ -339,102 +253,88 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
             }
         }
     }
-    dvar = wsum_d(dvar);
+    dvar = wave_sum(dvar);
     if (lane == 0) a.d_var_partial[r] = s_unclipped ? (float)(dvar * 10.0 * (double)inv_s) : 0.0f;
     if (a.d_dir_cos != nullptr) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float s = (float)wsum_d((double)ddir[k]);
+            const float s = (float)wave_sum((double)ddir[k]);
             if (lane == 0) a.d_dir_cos[r * 3 + k] = s;
         }
     }
 }
 
-__global__ __launch_bounds__(kRW * 64) void composite_bwd_kernel(CompositeBwdArgs a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRW + wave;
-    if (r >= a.B) return;
+__global__ __launch_bounds__(kRayWaves * 64) void composite_bwd_kernel(CompositeBwdArgs a) {
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     CompositeBwdOvr ov;
     ov.on = false;
     composite_bwd_row(a, r, wave, lane, ov);
 }
 
+// The upstream gradients of the fused training launches, made on the spot for ray r: the colour term's from the ray's composited
+// colour c (dpt_runner.py:228-229 with mask = 1: l1_grad, as in loss_kernel; also written to g_color), d loss / d gradient_error,
+// and the eikonal term's denominator from the foreground work list's length.
+VDN_DEV CompositeBwdOvr train_upstream(const float (&c)[3], const float* true_rgb, float* g_color, int B, int r, int lane,
+                                       const int32_t* fg_count, float igr_weight, float grad_scale) {
+    CompositeBwdOvr ov;
+    ov.on = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float m = 1.0f;
+        const float diff = c[k] - true_rgb[r * 3 + k];
+        ov.gc[k] = l1_grad(diff * m, m, mask_sum_of_ones(B)) * grad_scale;
+        if (lane == 0) g_color[r * 3 + k] = ov.gc[k];
+    }
+    ov.g_eik = igr_weight;
+    ov.eik_den = (float)(*fg_count) + 1e-5f;
+    return ov;
+}
+
 // renderer.py:262-315 forward, the colour term's gradient (dpt_runner.py:228-229, mask = 1) and the adjoint of the compositor
 // for one ray in ONE launch: the training step's plain configuration (no mask loss, no depth-feature loss, one rank) needs no
 // global quantity between the three but the eikonal term's denominator - the number of inside samples within the relaxed
-// sphere, which is exactly the length of the foreground work list (vdn_foreground_active uses the compositor's own norm
-// expression). The loss SCALARS (logging) are reduced afterwards by the usual kernels, off the critical path. Same device
-// functions as composite_kernel / composite_bwd_kernel and loss_kernel's expressions: bit-identical adjoints.
-__global__ __launch_bounds__(kRW * 64) void composite_train_kernel(CompositeArgs fa, CompositeBwdArgs ba, const float* true_rgb, float* g_color,
-                                                                   const int32_t* fg_count, float igr_weight, float grad_scale) {
-    __shared__ float s_w[kRW][kMaxTB], s_in[kRW][kMaxTB];
-    __shared__ __attribute__((aligned(16))) char s_dump[kRW][1024];       // the code warm-up's LDS-DMA lands here (vdn_common.h); never read
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRW + wave;
-    if (r >= fa.B) return;
+// sphere, which is exactly the length of the foreground work list (vdn_foreground_active tests the compositor's own
+// sample_norm). The loss SCALARS (logging) are reduced afterwards by the usual kernels, off the critical path. Same device
+// functions as composite_kernel / composite_bwd_kernel / loss_kernel: bit-identical adjoints.
+__global__ __launch_bounds__(kRayWaves * 64) void composite_train_kernel(CompositeArgs fa, CompositeBwdArgs ba, const float* true_rgb, float* g_color,
+                                                                         const int32_t* fg_count, float igr_weight, float grad_scale) {
+    __shared__ __attribute__((aligned(16))) char s_dump[kRayWaves][1024];       // the code warm-up's LDS-DMA lands here (vdn_common.h); never read
+    int wave, lane, r;
+    if (!ray_of_wave(fa.B, wave, lane, r)) return;
     // (the launch sits alone on the step's critical path between the forward and the backward kernels, on caches full of their
-    // planes: its 47 KB of code arrive as data while the ray's planes are loaded - vdn_common.h)
+    // planes: its 40 KB of code arrive as data while the ray's planes are loaded - vdn_common.h)
     warm_code_issue(kWarmCodeCompositeTrain, gridDim.x, 2048, s_dump[wave]);
-    const RowOut ro = composite_row(fa, r, lane, CompositeGlobalSrc{fa.sdf, fa.normals, fa.color}, s_w[wave], s_in[wave]);
-    CompositeBwdOvr ov;
-    ov.on = true;
-    const float mask_sum = (float)fa.B + 1e-5f;                       // dpt_runner.py:213 with mask = ones
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float m = 1.0f;
-        const float diff = ro.c[k] - true_rgb[r * 3 + k];
-        const float e = diff * m;
-        const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-        ov.gc[k] = sgn * m / mask_sum * grad_scale;
-        if (lane == 0) g_color[r * 3 + k] = ov.gc[k];
-    }
-    ov.g_eik = igr_weight;
-    ov.eik_den = (float)(*fg_count) + 1e-5f;
-    composite_bwd_row(ba, r, wave, lane, ov);
+    const RowOut ro = composite_row(fa, r, lane, CompositeGlobalSrc{fa.sdf, fa.normals, fa.color});
+    composite_bwd_row(ba, r, wave, lane, train_upstream(ro.c, true_rgb, g_color, fa.B, r, lane, fg_count, igr_weight, grad_scale));
     warm_l2_wait();
 }
 
-// composite_bwd_kernel with the upstream gradients made on the spot, as in composite_train_kernel: the colour term's from the colour
-// the forward left in memory (loss_kernel's expressions, mask = 1), the eikonal denominator from the foreground work list's length.
-// The feature channels' gradient a.g_feat was written by the forward (vdn_composite_fwd_train).
-__global__ __launch_bounds__(kRW * 64) void composite_bwd_train_kernel(CompositeBwdArgs a, const float* color_out, const float* true_rgb,
-                                                                       float* g_color, const int32_t* fg_count, float igr_weight, float grad_scale) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRW + wave;
-    if (r >= a.B) return;
-    CompositeBwdOvr ov;
-    ov.on = true;
-    const float mask_sum = (float)a.B + 1e-5f;                        // dpt_runner.py:213 with mask = ones
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float m = 1.0f;
-        const float diff = color_out[r * 3 + k] - true_rgb[r * 3 + k];
-        const float e = diff * m;
-        const float sgn = e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f);
-        ov.gc[k] = sgn * m / mask_sum * grad_scale;
-        if (lane == 0) g_color[r * 3 + k] = ov.gc[k];
-    }
-    ov.g_eik = igr_weight;
-    ov.eik_den = (float)(*fg_count) + 1e-5f;
-    composite_bwd_row(a, r, wave, lane, ov);
+// composite_bwd_kernel with the upstream gradients made on the spot, as in composite_train_kernel, from the colour the forward
+// left in memory. The feature channels' gradient a.g_feat was written by the forward (vdn_composite_fwd_train).
+__global__ __launch_bounds__(kRayWaves * 64) void composite_bwd_train_kernel(CompositeBwdArgs a, const float* color_out, const float* true_rgb,
+                                                                             float* g_color, const int32_t* fg_count, float igr_weight, float grad_scale) {
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
+    const float c[3] = {color_out[r * 3], color_out[r * 3 + 1], color_out[r * 3 + 2]};
+    composite_bwd_row(a, r, wave, lane, train_upstream(c, true_rgb, g_color, a.B, r, lane, fg_count, igr_weight, grad_scale));
 }
 
-// Adjoint of the ray geometry (include/vdn_render.h: VdnRayAdjointArgs), one wave per ray, sample i = kE * lane + e.
+// Adjoint of the ray geometry (include/vdn_render.h: VdnRayAdjointArgs), one wave per ray, sample i = kEPL * lane + e.
 //   d o = sum_i d pts_i;  d d = sum_i (d pts_i mid_i + d dirs_i) + d dir_cos;  d mid_i = d pts_i . d
 //   mid_i = (z_i + z_{i+1}) / 2 and dists_i = z_{i+1} - z_i for i < n-1;  mid_{n-1} = z_{n-1} + sample_dist / 2, dists_{n-1} const
 //   =>  d z_i = (d mid_i + d mid_{i-1}) / 2 - d dists_i + d dists_{i-1}      (terms with index -1 absent; i = n-1: d mid_i whole)
-__global__ __launch_bounds__(kRW * 64) void ray_adjoint_kernel(RayAdjointArgs a) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * kRW + wave;
-    if (r >= a.B) return;
+__global__ __launch_bounds__(kRayWaves * 64) void ray_adjoint_kernel(RayAdjointArgs a) {
+    int wave, lane, r;
+    if (!ray_of_wave(a.B, wave, lane, r)) return;
     const float d0 = a.rays_d[r * 3], d1 = a.rays_d[r * 3 + 1], d2 = a.rays_d[r * 3 + 2];
     double so[3] = {0.0, 0.0, 0.0}, sd[3] = {0.0, 0.0, 0.0};
     auto pass = [&](const float* dpts, const float* ddirs, const float* ddists, const float* mid, int n, float* dz_a, int n_a,
                     float* dz_b) VDN_INL {
-        float dm[kE], dl[kE];
+        float dm[kEPL], dl[kEPL];
 #pragma unroll
-        for (int e = 0; e < kE; ++e) {
-            const int i = kE * lane + e;
+        for (int e = 0; e < kEPL; ++e) {
+            const int i = kEPL * lane + e;
             dm[e] = 0.0f; dl[e] = 0.0f;
             if (i < n) {
                 const long q = (long)r * n + i;
@@ -447,10 +347,10 @@ __global__ __launch_bounds__(kRW * 64) void ray_adjoint_kernel(RayAdjointArgs a)
             }
         }
         // values of sample i-1: the previous element, or the previous lane's last element
-        const float pm = __shfl_up(dm[kE - 1], 1), pl = __shfl_up(dl[kE - 1], 1);
+        const float pm = __shfl_up(dm[kEPL - 1], 1), pl = __shfl_up(dl[kEPL - 1], 1);
 #pragma unroll
-        for (int e = 0; e < kE; ++e) {
-            const int i = kE * lane + e;
+        for (int e = 0; e < kEPL; ++e) {
+            const int i = kEPL * lane + e;
             if (i >= n) continue;
             const float dm_prev = i == 0 ? 0.0f : (e == 0 ? pm : dm[e - 1]);
             const float dl_prev = i == 0 ? 0.0f : (e == 0 ? pl : dl[e - 1]);
@@ -461,8 +361,8 @@ __global__ __launch_bounds__(kRW * 64) void ray_adjoint_kernel(RayAdjointArgs a)
     };
     const int N = a.N, T = a.T;
 #pragma unroll
-    for (int e = 0; e < kE; ++e) {
-        const int i = kE * lane + e;
+    for (int e = 0; e < kEPL; ++e) {
+        const int i = kEPL * lane + e;
         if (i < N) a.d_z[(long)r * N + i] = 0.0f;
         if (a.d_z_out != nullptr && i >= N && i < T) a.d_z_out[(long)r * (T - N) + (i - N)] = 0.0f;
     }
@@ -470,7 +370,7 @@ __global__ __launch_bounds__(kRW * 64) void ray_adjoint_kernel(RayAdjointArgs a)
     if (a.d_bg_pts != nullptr) pass(a.d_bg_pts, a.d_bg_dirs, a.d_bg_dists, a.bg_mid, T, a.d_z, N, a.d_z_out);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const double o = wsum_d(so[k]), dd = wsum_d(sd[k]);
+        const double o = wave_sum(so[k]), dd = wave_sum(sd[k]);
         if (lane == 0) {
             a.d_rays_o[r * 3 + k] = (float)o;
             a.d_rays_d[r * 3 + k] = (float)dd + a.d_dir_cos[r * 3 + k];
@@ -481,76 +381,61 @@ __global__ __launch_bounds__(kRW * 64) void ray_adjoint_kernel(RayAdjointArgs a)
 __global__ void variance_reduce_kernel(const float* partial, int B, float* out) {
     double s = 0.0;
     for (int i = threadIdx.x; i < B; i += 64) s += (double)partial[i];
-    s = wsum_d(s);
+    s = wave_sum(s);
     if (threadIdx.x == 0) out[0] = (float)s;
 }
 
 }  // namespace vdn
 
-extern "C" int vdn_alpha_composite_bwd(const VdnCompositeBwdArgs* a, void* stream) {
-    using namespace vdn;
-    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxTB) return -1;
-    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance ||
-        !a->alpha || !a->weights || !a->eik) return -2;
-    if (!a->d_sdf || !a->d_normals || !a->d_color || !a->d_var_partial) return -3;
-    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists || !a->d_bg_density || !a->d_bg_rgb)) return -4;
-    if (a->d_feat && (!a->feat || a->feat_ch <= 0 || a->feat_ch > 128)) return -5;
-    if ((a->d_dists != nullptr) != (a->d_dir_cos != nullptr) || (a->d_bg_dists && !a->d_dists)) return -6;
+using namespace vdn;
+
+// The adjoint's launches: feat_dot in front and feat_outer behind the per-ray kernel when the feature channels go through
+// feat_scratch, then the variance gradient's reduction. launch_adjoint() launches the per-ray kernel of the entry point.
+template <class LaunchAdjoint>
+static int launch_composite_bwd(const VdnCompositeBwdArgs* a, void* stream, LaunchAdjoint launch_adjoint) {
     const bool ext_feat = a->d_feat && a->g_feat && a->feat_scratch;
     const int row_blocks = (int)(((long)a->B * a->T + 3) / 4);
     if (ext_feat) hipLaunchKernelGGL(feat_dot_kernel, dim3(row_blocks), dim3(256), 0, (hipStream_t)stream, *a);
-    hipLaunchKernelGGL(composite_bwd_kernel, dim3((a->B + kRW - 1) / kRW), dim3(kRW * 64), 0, (hipStream_t)stream, *a);
+    launch_adjoint();
     if (ext_feat) hipLaunchKernelGGL(feat_outer_kernel, dim3(row_blocks), dim3(256), 0, (hipStream_t)stream, *a);
     if (a->d_variance != nullptr)
         hipLaunchKernelGGL(variance_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->d_var_partial, a->B, a->d_variance);
     return (int)hipGetLastError();
+}
+
+extern "C" int vdn_alpha_composite_bwd(const VdnCompositeBwdArgs* a, void* stream) {
+    if (const int err = composite_bwd_check(a, true)) return err;
+    if ((a->d_dists != nullptr) != (a->d_dir_cos != nullptr) || (a->d_bg_dists && !a->d_dists)) return -6;
+    return launch_composite_bwd(a, stream, [&] { launch_rays(composite_bwd_kernel, a->B, stream, *a); });
 }
 
 extern "C" int vdn_composite_train(const VdnCompositeArgs* f, const VdnCompositeBwdArgs* b, const float* true_rgb, float* g_color,
                                    const int32_t* fg_count, float igr_weight, float grad_scale, void* stream) {
-    using namespace vdn;
-    if (!f || !b || !true_rgb || !g_color || !fg_count) return -1;
-    if (f->B <= 0 || f->N <= 0 || f->T < f->N || f->T > kMaxTB || b->B != f->B || b->N != f->N || b->T != f->T) return -1;
-    if (!f->rays_o || !f->rays_d || !f->sdf || !f->normals || !f->dists || !f->mid_z || !f->color || !f->variance) return -2;
-    if (!f->weights || !f->alpha_out || !f->cdf || !f->inside_sphere || !f->color_out || !f->weight_sum || !f->weight_max || !f->eik_partial) return -3;
-    if (f->T > f->N && (!f->bg_density || !f->bg_rgb || !f->bg_dists || !b->d_bg_density || !b->d_bg_rgb)) return -4;
+    if (!f || !b || !true_rgb || !g_color || !fg_count || b->B != f->B || b->N != f->N || b->T != f->T) return -1;
+    if (const int err = composite_fwd_check(f, true, false, b->d_bg_density && b->d_bg_rgb)) return err;
     // the plain configuration only: no feature channels, no extra upstream gradients, no ray adjoints
     if (f->feat_out || b->d_feat || b->g_feat || b->g_weights || b->g_cdf || b->d_dists || b->d_dir_cos) return -10;
     if (b->alpha != f->alpha_out || b->weights != f->weights || !b->d_sdf || !b->d_normals || !b->d_color || !b->d_var_partial) return -3;
-    hipLaunchKernelGGL(composite_train_kernel, dim3((f->B + kRW - 1) / kRW), dim3(kRW * 64), 0, (hipStream_t)stream, *f, *b, true_rgb,
-                       g_color, fg_count, igr_weight, grad_scale);
-    if (b->d_variance != nullptr)
-        hipLaunchKernelGGL(variance_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, b->d_var_partial, b->B, b->d_variance);
-    return (int)hipGetLastError();
+    return launch_composite_bwd(b, stream, [&] {       // (no feature channels: the per-ray launch and the variance reduction)
+        launch_rays(composite_train_kernel, f->B, stream, *f, *b, true_rgb, g_color, fg_count, igr_weight, grad_scale);
+    });
 }
 
 extern "C" int vdn_composite_bwd_train(const VdnCompositeBwdArgs* a, const float* color_out, const float* true_rgb, float* g_color,
                                        const int32_t* fg_count, float igr_weight, float grad_scale, void* stream) {
-    using namespace vdn;
-    if (!a || !color_out || !true_rgb || !g_color || !fg_count || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxTB) return -1;
-    if (!a->rays_o || !a->rays_d || !a->sdf || !a->normals || !a->dists || !a->mid_z || !a->color || !a->variance ||
-        !a->alpha || !a->weights) return -2;
-    if (!a->d_sdf || !a->d_normals || !a->d_color || !a->d_var_partial) return -3;
-    if (a->T > a->N && (!a->bg_density || !a->bg_rgb || !a->bg_dists || !a->d_bg_density || !a->d_bg_rgb)) return -4;
-    if (a->d_feat && (!a->feat || a->feat_ch <= 0 || a->feat_ch > 128)) return -5;
+    if (!color_out || !true_rgb || !g_color || !fg_count) return -1;
+    if (const int err = composite_bwd_check(a, false)) return err;
     // the Trainer's configuration only: no extra upstream gradients, no ray adjoints
     if (a->g_weights || a->g_cdf || a->d_dists || a->d_dir_cos) return -10;
-    const bool ext_feat = a->d_feat && a->g_feat && a->feat_scratch;
-    const int row_blocks = (int)(((long)a->B * a->T + 3) / 4);
-    if (ext_feat) hipLaunchKernelGGL(feat_dot_kernel, dim3(row_blocks), dim3(256), 0, (hipStream_t)stream, *a);
-    hipLaunchKernelGGL(composite_bwd_train_kernel, dim3((a->B + kRW - 1) / kRW), dim3(kRW * 64), 0, (hipStream_t)stream, *a, color_out, true_rgb,
-                       g_color, fg_count, igr_weight, grad_scale);
-    if (ext_feat) hipLaunchKernelGGL(feat_outer_kernel, dim3(row_blocks), dim3(256), 0, (hipStream_t)stream, *a);
-    if (a->d_variance != nullptr)
-        hipLaunchKernelGGL(variance_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->d_var_partial, a->B, a->d_variance);
-    return (int)hipGetLastError();
+    return launch_composite_bwd(a, stream, [&] {
+        launch_rays(composite_bwd_train_kernel, a->B, stream, *a, color_out, true_rgb, g_color, fg_count, igr_weight, grad_scale);
+    });
 }
 
 extern "C" int vdn_ray_adjoint(const VdnRayAdjointArgs* a, void* stream) {
-    using namespace vdn;
-    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxTB) return -1;
+    if (!a || a->B <= 0 || a->N <= 0 || a->T < a->N || a->T > kMaxT) return -1;
     if (!a->rays_d || !a->mid_z || !a->d_pts || !a->d_dirs || !a->d_dists || !a->d_dir_cos || !a->d_rays_o || !a->d_rays_d || !a->d_z) return -2;
     if (a->T > a->N && a->d_bg_pts && (!a->bg_mid || !a->d_bg_dirs || !a->d_bg_dists || !a->d_z_out)) return -3;
-    hipLaunchKernelGGL(ray_adjoint_kernel, dim3((a->B + kRW - 1) / kRW), dim3(kRW * 64), 0, (hipStream_t)stream, *a);
+    launch_rays(ray_adjoint_kernel, a->B, stream, *a);
     return (int)hipGetLastError();
 }

@@ -184,7 +184,7 @@ constexpr int kWarmCodeNerfBwd = 78 * 1024;           // symbol: nerf_bwd_kernel
 constexpr int kWarmCodeRenderFwd = 28 * 1024;         // symbol: rendernet_fwd_kernelINS_4BF16E
 constexpr int kWarmCodeRenderBwd = 36 * 1024;         // symbol: rendernet_bwd_kernelINS_4BF16E
 constexpr int kWarmCodeSdfBwdSplit = 20 * 1024;       // symbol: sdf_bwd_split_kernel
-constexpr int kWarmCodeCompositeTrain = 40 * 1024;    // symbol: composite_train_kernel
+constexpr int kWarmCodeCompositeTrain = 37 * 1024;    // symbol: composite_train_kernel
 
 // Hardware transcendental forms (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp each): what the MLP
 // epilogues use - the ocml expf/log1pf expansions cost more VALU time than the layer's MFMAs.
