@@ -93,6 +93,12 @@ typedef struct {
     void* H;                  /* [8,P,256] H[l] = softplus output of layer l (= input of layer l+1) */
     void* V;                  /* [8,P,256] V[l] = sweep value v_l = u_{l+1} * softplus'(a_l) */
     void* PE;                 /* [P,64] positional encoding of the point (39 valid) */
+    /* bf16 entry points: every bf16 plane is stored round-to-nearest-even (v_cvt_pk_bf16_f32).
+     * Accuracy contract of their encodings (here, in the normals, in the heads' and the background network's view / point
+     * encodings): sine and cosine are the hardware instructions on the float32 argument in revolutions
+     * (vdn-nerf_amd/csrc/vdn_common.h: sincos_pe), each within 2^-18 + 2^-23 |arg| of the exact function of the exact argument
+     * (absolute) - far below the bf16 rounding the encoded value then receives. The f32 entry points use the library sincosf.
+     * tests/test_gpu_mlp_planes.py holds the planes to it. */
     /* optional work list (vdn_foreground_active; same contract as VdnNerfArgs.active_idx): per-point inputs / outputs
      * are addressed by the dense point id, training saves and deltas by the compact row */
     const int32_t* active_idx;
@@ -133,6 +139,11 @@ typedef struct {
     const float* pts;          /* [P,3] explicit points (standalone RenderingNetwork.forward) or NULL */
     const float* dirs;         /* [P,3] explicit view dirs or NULL (then rays_d[r]) */
     float* out;                /* [P,d_out] */
+    /* bf16 entry point: `out` leaves the last MFMA layer directly - a float32 accumulation of exact bf16 x bf16 products in k-steps
+     * of 16 inputs, the accumulator rounded once per k-step: within (number of k-steps) * 2^-24 * sum |w x| of the exact sum over
+     * the saved bf16 input plane, through |f'| of the output activation (tests/test_gpu_mlp_planes.py). That the matrix
+     * instruction rounds its accumulator once per k-step is this library's ASSUMPTION about v_mfma_f32_32x32x16_bf16 - the
+     * instruction set manual does not state its internal rounding -; the bound is what the tests hold the kernels to. */
     void* save_h;              /* [4,P,256] post-ReLU hidden activations (training) or NULL */
     void* save_small;          /* [P,64] the non-feature inputs [points, PE(view), normals] (33 valid) or NULL */
     int32_t n_per_ray;
@@ -163,6 +174,8 @@ typedef struct {
     const float* pts4;         /* [P,4] explicit input_pts (standalone NeRF.forward) or NULL */
     const float* dirs;         /* [P,3] explicit input_views or NULL (then rays_d[r]) */
     float* density;            /* [P] raw alpha_linear output (before softplus) */
+    /* bf16 entry point: density, rgb and feat leave their MFMA layer directly and carry the accumulation contract stated at
+     * VdnRenderNetArgs.out. */
     float* rgb;                /* [P,3] */
     float* feat;               /* [P,96] dpt_linear output, or NULL when gen_depth_feats is off */
     /* training-mode saves, optional: */

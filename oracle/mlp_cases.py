@@ -1,0 +1,178 @@
+"""Constructed inputs of the bf16 plane tests (oracle/mlp_ops.py, tests/test_gpu_mlp_planes.py), deterministic from the
+case name: the SDF network first, the heads and the background network at the end of the file. tests/test_mlp_ops_model_cpu.py
+proves their coverage without a GPU.
+
+Row counts: 1 (one row), 33 (one row past a 32-row pad block), 129 (one row past a 128-row workgroup), 300 (two full workgroups
+and a partial one whose last block is partial); one work list: 77 of 200 rows, not ascending, so that saves in compact rows
+against outputs in dense rows shows. Nothing larger: these are the smallest shapes that reach every row path.
+Points: uniform in [-1.1, 1.1]^3; one case on the lattice {-1, 0, 1}^3 (exact zeros and +-1). SDFNetwork scale 1 and 1.5.
+Weights: "init" = synth.make_all_states(3, wdepth=True, variance=0.3), where every hidden layer has 22 - 30 % of its units on the knee
+of softplus (0.02 < sigma < 0.98). "hot" = the same state with weight_g of the hidden SDF layers scaled by HOT_FACTORS, chosen per
+layer on the CPU (float64 model, 300 points) so that every layer reaches the kernel's range switches (DESIGN.md 3a, round 3:
+g = t from t >= 25, w = +inf from t = 128): at least 4 % of each layer's units in each of t >= 128, t <= -128, 25 <= t < 128 and
+|t| < 5, with max H < 2^10 (one factor for all layers does not do it: activations compound and the knee empties). "other" (seed
+4) is the state of the wiring check."""
+import numpy as np
+
+from vdn_train import synth
+
+SEED, OTHER_SEED = 3, 4
+HOT_FACTORS = (4.0, 1.0, 1.0, 1.0, 1.4, 1.0, 1.0, 1.4)
+
+# name: (P, scale, points, n_active, weight state)
+SDF_CASES = {
+    "uniform-P1-s1": (1, 1.0, "uniform", None, "init"),
+    "uniform-P33-s1.5": (33, 1.5, "uniform", None, "init"),
+    "lattice-P33-s1": (33, 1.0, "lattice", None, "init"),
+    "uniform-P129-s1": (129, 1.0, "uniform", None, "init"),
+    "uniform-P300-s1.5": (300, 1.5, "uniform", None, "init"),
+    "worklist-P200-n77-s1": (200, 1.0, "uniform", 77, "init"),
+    "hot-P129-s1": (129, 1.0, "uniform", None, "hot"),
+    "hot-P300-s1.5": (300, 1.5, "uniform", None, "hot"),
+}
+
+
+def states(state="init"):
+    st = synth.make_all_states(OTHER_SEED if state == "other" else SEED, wdepth=True, variance=0.3)
+    if state == "hot":
+        sd = st["sdf_network_fine"]
+        for l, f in enumerate(HOT_FACTORS):
+            sd["lin%d.weight_g" % l] = sd["lin%d.weight_g" % l] * np.float32(f)
+    return st
+
+
+def sdf_case(name):
+    P, scale, kind, n_active, state = SDF_CASES[name]
+    if kind == "uniform":
+        pts = (2.2 * synth.uniform(SEED, "mlp/%s/pts" % name, (P, 3)) - 1.1).astype(np.float32)
+    else:
+        pts = (np.floor(3.0 * synth.uniform(SEED, "mlp/%s/pts" % name, (P, 3))) - 1.0).astype(np.float32)
+        pts[0] = 0.0                                   # the origin itself: every sine exactly zero
+        pts[1], pts[2] = 1.0, -1.0
+    c = {"name": name, "P": P, "scale": scale, "pts": pts, "active_idx": None, "n_active": None, "state": state}
+    if n_active is not None:
+        order = np.argsort(synth.uniform(SEED, "mlp/%s/order" % name, (P,)))      # a permutation: not ascending, not contiguous
+        idx = np.full(P, -1, np.int32)
+        idx[:n_active] = order[:n_active]
+        c["active_idx"], c["n_active"] = idx, n_active
+    return c
+
+
+def rows_of(c):
+    """The points behind the rows of the saved planes: the listed ones in list order, or all of them."""
+    return c["pts"] if c["active_idx"] is None else c["pts"][c["active_idx"][:c["n_active"]]]
+
+
+# ---- the heads ---------------------------------------------------------------------------------------------------------------
+# name: (network, P). Inputs: points uniform in [-1.1, 1.1]^3, unit view directions, normals ~ N(0, 1), a feature plane of
+# bf16 values ~ N(0, 0.3) (what the SDF forward leaves there). Row 0 looks along +x from the origin with a zero normal and a zero
+# feature vector: every sine exactly zero. State "init" with unit 7 of layers 0 and 2 silenced (weight_g = bias = 0): a
+# pre-activation that is exactly zero, so that relu(0) = 0 and its mask bit are pinned (background network: unit 7 of pts_linears.2).
+# "color352": the d_feature = 352 colour network (13 k-tiles in its first layer, the 96 appended channels behind the small inputs).
+HEAD_CASES = {"color-P33": ("color_network", 33), "color-P129": ("color_network", 129), "vdn-P33": ("depth_network", 33),
+              "vdn-P300": ("depth_network", 300), "color352-P129": ("color_network", 129)}
+SILENT_UNIT = 7
+STATE_KEY = {"color_network": "color_network_fine", "depth_network": "depth_network_fine"}
+
+
+def head_states(state="heads"):
+    """"heads": the init state with the silenced units; "heads-other": seed 4 likewise (the wiring check); "heads352": with the
+    d_feature = 352 colour network; "nodpt": without the VDN head and the background network's dpt head."""
+    if state == "heads352":
+        st = synth.make_all_states(SEED, wdepth=True, variance=0.3, depth_before_color=True)
+    elif state == "nodpt":
+        st = synth.make_all_states(SEED, wdepth=False, variance=0.3)
+    else:
+        st = states("other" if state == "heads-other" else "init")
+    st["nerf"]["pts_linears.2.weight"][SILENT_UNIT] = 0.0
+    st["nerf"]["pts_linears.2.bias"][SILENT_UNIT] = 0.0
+    for key in STATE_KEY.values():
+        if st[key] is None:
+            continue
+        for l in (0, 2):
+            st[key]["lin%d.weight_g" % l][SILENT_UNIT] = 0.0
+            st[key]["lin%d.bias" % l][SILENT_UNIT] = 0.0
+    return st
+
+
+def head_case(name):
+    net, P = HEAD_CASES[name]
+    u = lambda tag, shape: synth.uniform(SEED, "mlp/%s/%s" % (name, tag), shape)
+    n = lambda tag, shape: synth.normal(SEED, "mlp/%s/%s" % (name, tag), shape)
+    pts = (2.2 * u("pts", (P, 3)) - 1.1).astype(np.float32)
+    dirs = n("dirs", (P, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
+    normals = n("normals", (P, 3)).astype(np.float32)
+    feat = (0.3 * n("feat", (P, 256))).astype(np.float32)
+    pts[0], dirs[0], normals[0], feat[0] = 0.0, (1.0, 0.0, 0.0), 0.0, 0.0
+    wide = name.startswith("color352")
+    return {"name": name, "net": net, "P": P, "pts": pts, "dirs": dirs, "normals": normals, "feat": feat,
+            "d_out": 3 if net == "color_network" else 96, "squeeze": True, "state": "heads352" if wide else "heads",
+            "d_feature": 352 if wide else 256, "extra": (0.3 * n("extra", (P, 96))).astype(np.float32) if wide else None}
+
+
+def head_upstream(c):
+    """g_out [P,d_out] ~ N(0, 1) of a head case (the backward's upstream gradient); row 0 zero."""
+    g = synth.normal(SEED, "mlp/%s/g_out" % c["name"], (c["P"], c["d_out"])).astype(np.float32)
+    g[0] = 0.0
+    return g
+
+
+# ---- the background network ---------------------------------------------------------------------------------------------------
+# name: (P, n_active). Inverted-sphere points [x / r, 1 / r] with r in [1, 4] (renderer.py:112-115), unit view directions; row 0
+# sits on the +x axis at r = 1 and looks along +x (exact zeros and ones).
+NERF_CASES = {"nerf-P1": (1, None), "nerf-P33": (33, None), "nerf-P129": (129, None), "nerf-P300": (300, None),
+              "nerf-worklist-P200-n77": (200, 77), "nerf-nodpt-P129": (129, None)}
+
+
+def nerf_case(name):
+    P, n_active = NERF_CASES[name]
+    u = lambda tag, shape: synth.uniform(SEED, "mlp/%s/%s" % (name, tag), shape)
+    n = lambda tag, shape: synth.normal(SEED, "mlp/%s/%s" % (name, tag), shape)
+    d = n("x", (P, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    r = 1.0 + 3.0 * u("r", (P, 1))
+    pts4 = np.concatenate([d, 1.0 / r], -1).astype(np.float32)
+    dirs = n("dirs", (P, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
+    pts4[0], dirs[0] = (1.0, 0.0, 0.0, 1.0), (1.0, 0.0, 0.0)
+    c = {"name": name, "P": P, "pts4": pts4, "dirs": dirs, "active_idx": None, "n_active": None,
+         "state": "nodpt" if "nodpt" in name else "heads"}
+    if n_active is not None:
+        order = np.argsort(u("order", (P,)))
+        idx = np.full(P, -1, np.int32)
+        idx[:n_active] = order[:n_active]
+        c["active_idx"], c["n_active"] = idx, n_active
+    return c
+
+
+def nerf_rows_of(c):
+    sel = slice(None) if c["active_idx"] is None else c["active_idx"][:c["n_active"]]
+    return c["pts4"][sel], c["dirs"][sel]
+
+
+def nerf_upstream(c):
+    """(g_density [P], g_rgb [P,3], g_feat [P,96] or None) ~ N(0, 1) of a background case; row 0 zero (but in the one-row case)."""
+    n = lambda tag, shape: synth.normal(SEED, "mlp/%s/%s" % (c["name"], tag), shape).astype(np.float32)
+    g = [n("g_density", (c["P"],)), n("g_rgb", (c["P"], 3)), None if c["state"] == "nodpt" else n("g_feat", (c["P"], 96))]
+    for a in g:
+        if a is not None and c["P"] > 1:
+            a[0] = 0.0
+    return g
+
+
+# ---- the SDF backward ---------------------------------------------------------------------------------------------------------
+# Upstream gradients of an SDF case: random, and each chain alone (g_feat = 0 with g_sdf = 0 leaves only the sweep's adjoint and its
+# second-order term; g_normals = 0 leaves only the forward's adjoint: ub and EX exactly zero).
+SDF_UPSTREAM = ("random", "g_feat=0", "g_normals=0")
+
+
+def sdf_upstream(c, kind="random"):
+    """(g_sdf [P], g_feat [P,256] bf16 values, g_normals [P,3]) ~ N(0, 1), dense point order."""
+    n = lambda tag, shape: synth.normal(SEED, "mlp/%s/%s" % (c["name"], tag), shape).astype(np.float32)
+    g_sdf, g_feat, g_n = n("g_sdf", (c["P"],)), n("g_feat", (c["P"], 256)), n("g_normals", (c["P"], 3))
+    if kind == "g_feat=0":
+        g_feat[:], g_sdf[:] = 0.0, 0.0
+    elif kind == "g_normals=0":
+        g_n[:] = 0.0
+    return g_sdf, g_feat, g_n

@@ -1,7 +1,11 @@
 """bf16-MFMA throughput path (precision='bf16') against the fp32 oracle. bf16 operands carry 8 significant bits, so
 this path is NOT held to 1e-4: the bounds below are ~3x the errors measured on MI355X (tests/probes/bf16_probe.py:
 sdf abs err max 5.5e-3 / mean 1e-3, colour PSNR 70 dB at inv_s 20 and 57 dB at inv_s 665, gradient cosine >= 0.9995).
-The fp32 path (tests/test_gpu_parity.py, test_gpu_grads.py) is the one that carries the 1e-4 parity claim."""
+The fp32 path (tests/test_gpu_parity.py, test_gpu_grads.py) is the one that carries the 1e-4 parity claim.
+These bounds are END TO END, across eight chained bf16 layers. The per-layer claim - every plane the bf16 forward and backward launches of the SDF
+network, the heads and the background network write is a bf16 rounding of one float64 layer applied to the plane before (or, in a
+backward chain, after) it, to a few float32 roundings - is tests/test_gpu_mlp_planes.py's (model and plane contract:
+oracle/mlp_ops.py)."""
 import numpy as np
 import pytest
 import torch

@@ -35,6 +35,16 @@ def from_pt32(buf, P, ld):
     return x[:P].float()
 
 
+def decode_chunk_bf16(chunk, kt):
+    """One fmt-1 weight chunk (include/vdn_render.h: VdnChunkDesc; uint8 tensor of >= kt * 2048 + 128 bytes) ->
+    (W [32, 32 kt] float32, bias [32] float32). The chunk is [kt * 2 k-steps][64 lanes][8 bf16], lane (i, h) = i + 32 h holding
+    output row i, element j of k-step s the input k = 16 s + 8 (j >> 2) + 4 h + (j & 3); behind it 32 float32 biases."""
+    raw = chunk.reshape(-1)[:kt * 2048 + 128].cpu().contiguous()
+    w = raw[:kt * 2048].clone().view(torch.bfloat16).view(2 * kt, 2, 32, 2, 4)           # [s, h, i, j >> 2, j & 3]
+    W = w.permute(2, 0, 3, 1, 4).reshape(32, 32 * kt).float()                               # [i, s, j >> 2, h, j & 3]
+    return W, raw[kt * 2048:].clone().view(torch.float32)
+
+
 def col_offset_elems(col0, precision):
     """Element offset of column col0 (a multiple of 32) inside a plane."""
     if precision == "fp32":
