@@ -339,9 +339,14 @@ int vdn_shade_fused_f32(const VdnSdfArgs* sdf_host, const VdnRenderNetArgs* colo
  * registers, by vdn_rendernet_fwd_bf16 of the colour network (fields.py:148-176, mode 'idr', d_out = 3) with ITS saves: col_h
  * [4, rows, 256] hidden activations, col_small [rows, 64] the 33 small inputs, col_out [P,3] the colour - the planes
  * VdnRenderNetArgs.save_h / save_small / out name, in the same layouts (compact rows of sdf_host's work list; col_out by dense
- * point id). color_blob: the colour network's "c2" chunk stream (vdn_hip/images.py). The colour differs from the two launches'
- * by <= 4e-6 (the normal's z component enters the first colour layer in f32 instead of bf16). Declines (-10, nothing launched)
- * ray-gradient saves (U_pe) and the tail split (tail_max_rows). */
+ * point id). color_blob: the colour network's "c2" chunk stream (vdn_hip/images.py). One difference from the two launches: the
+ * normal's z component enters the first colour layer as an f32 term fmaf(w, nz, acc) on the f32 normal instead of as a bf16
+ * operand, so col_h and col_out are not the two launches' bits (col_small is). The contract is stated against the network, not
+ * against those launches: col_small = [o + d z (unscaled), PE4(d) of the row's own ray, the f32 normals this launch writes], every
+ * col_h[l] is a bf16 rounding of its layer applied to the saved plane before it, col_out the sigmoid layer on col_h[3] in f32 -
+ * tests/test_gpu_fused_head_planes.py holds each plane to a float64 model of that layer within max(1, 3 x float32 floor) rounding
+ * units (measured: no bf16 plane off the nearest two bf16 values of the model, col_out within 0.17 units). Declines (-10, nothing
+ * launched) ray-gradient saves (U_pe) and the tail split (tail_max_rows). */
 int vdn_sdf_color_train_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, void* col_h, void* col_small,
                              float* col_out, void* stream);
 int vdn_shade_fused_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, const VdnCompositeArgs* comp_host,

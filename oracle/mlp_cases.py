@@ -1,6 +1,6 @@
 """Constructed inputs of the bf16 plane tests (oracle/mlp_ops.py, tests/test_gpu_mlp_planes.py), deterministic from the
-case name: the SDF network first, the heads and the background network at the end of the file. tests/test_mlp_ops_model_cpu.py
-proves their coverage without a GPU.
+case name: the SDF network first, then the heads, the colour head inside the fused SDF launches (tests/test_gpu_fused_head_planes.py)
+and the background network. tests/test_mlp_ops_model_cpu.py proves their coverage without a GPU.
 
 Row counts: 1 (one row), 33 (one row past a 32-row pad block), 129 (one row past a 128-row workgroup), 300 (two full workgroups
 and a partial one whose last block is partial); one work list: 77 of 200 rows, not ascending, so that saves in compact rows
@@ -116,6 +116,120 @@ def head_upstream(c):
     g = synth.normal(SEED, "mlp/%s/g_out" % c["name"], (c["P"], c["d_out"])).astype(np.float32)
     g[0] = 0.0
     return g
+
+
+# ---- the colour head inside the fused SDF launches (csrc/k_sdf_fwd2.h MODE 3 / 2 / 4) -------------------------------------------
+# MODE 3 (vdn_sdf_color_train_bf16), name: (rays, samples per ray, SDFNetwork scale, n_active, weight state). Ray form only (the
+# entry point rejects `pts`), the smallest shapes that reach every row path: 1 row; 33 rows with ray boundaries at lanes 11 and 22
+# of a wave and one row past a pad block; 129 rows, one past a workgroup, the ray changing every 3 lanes; 300 rows at scale 1.5; a
+# work list of 77 of 200 rows, not ascending; 129 rows on the "hot" SDF state (large features into the head, max H < 2^10).
+# rays_o uniform in [-0.6, 0.6]^3, unit rays_d, every component of neighbouring rays at least DIR_GAP apart (a bf16 step at 1 is
+# 2^-7: the direction of the wrong ray shows in every column), z uniform in [0.05, 1]. Ray 0 starts at the origin and looks along
+# +x (the sines of its zero components are exactly zero). From 3 rows on the last depth is exactly 0 and the middle one negative.
+# Weight states: fused_states below; the colour network always with unit 7 of layers 0 and 2 silenced (head_states), so that its
+# row of the first layer's tail column is zero as well and h0[:, 7] is pinned to exactly 0.
+FUSED_CASES = {
+    "rays-1x1-s1": (1, 1, 1.0, None, "heads"),
+    "rays-3x11-s1": (3, 11, 1.0, None, "heads"),
+    "rays-43x3-s1": (43, 3, 1.0, None, "heads"),
+    "rays-12x25-s1.5": (12, 25, 1.5, None, "heads"),
+    "worklist-8x25-n77-s1": (8, 25, 1.0, 77, "heads"),
+    "hot-43x3-s1": (43, 3, 1.0, None, "heads-hot"),
+}
+DIR_GAP = 0.05
+
+
+def fused_states(state="heads"):
+    """"heads" / "heads-other": head_states; "heads-hot": "heads" with the hot SDF network (HOT_FACTORS); "heads-flat": "heads"
+    with lin8.weight_g[0] = 0 - row 0 of W_8 is zero, the sdf is the constant b_8[0] and its gradient exactly zero everywhere."""
+    st = head_states("heads-other" if state == "heads-other" else "heads")
+    sd = st["sdf_network_fine"]
+    if state == "heads-hot":
+        for l, f in enumerate(HOT_FACTORS):
+            sd["lin%d.weight_g" % l] = sd["lin%d.weight_g" % l] * np.float32(f)
+    elif state == "heads-flat":
+        sd["lin8.weight_g"][0] = 0.0
+    return st
+
+
+def _unit_dirs(tag, n, first=None):
+    """n unit directions, deterministic (the first one given, or drawn); each differs from the one before it by at least DIR_GAP
+    in every component."""
+    out = [] if first is None else [np.asarray(first, np.float32)]
+    for r in range(len(out), n):
+        for k in range(64):
+            d = synth.normal(SEED, "mlp/%s/%d/%d" % (tag, r, k), (3,))
+            d = (d / np.linalg.norm(d)).astype(np.float32)
+            if not out or np.abs(d - out[-1]).min() >= DIR_GAP:
+                break
+        else:
+            raise AssertionError("no direction found")
+        out.append(d)
+    return np.stack(out)
+
+
+def fused_case(name):
+    B, n, scale, n_active, state = FUSED_CASES[name]
+    u = lambda tag, shape: synth.uniform(SEED, "mlp/%s/%s" % (name, tag), shape)
+    rays_o = (1.2 * u("rays_o", (B, 3)) - 0.6).astype(np.float32)
+    rays_d = _unit_dirs(name + "/rays_d", B, first=(1.0, 0.0, 0.0))
+    rays_o[0] = 0.0
+    z = (0.05 + 0.95 * u("z", (B, n))).astype(np.float32)
+    if z.size >= 3:
+        z.reshape(-1)[-1], z.reshape(-1)[z.size // 2] = 0.0, -0.25
+    c = {"name": name, "B": B, "n_per_ray": n, "P": B * n, "scale": scale, "rays_o": rays_o, "rays_d": rays_d, "z": z,
+         "active_idx": None, "n_active": None, "state": state, "squeeze": True}
+    if n_active is not None:
+        order = np.argsort(u("order", (B * n,)))
+        idx = np.full(B * n, -1, np.int32)
+        idx[:n_active] = order[:n_active]
+        c["active_idx"], c["n_active"] = idx, n_active
+    return c
+
+
+def fused_rows_of(c):
+    """The dense point ids (ray * n_per_ray + sample) behind the rows of the saved planes: the listed ones in list order, or all."""
+    return np.arange(c["P"]) if c["active_idx"] is None else c["active_idx"][:c["n_active"]].astype(np.int64)
+
+
+def fused_points_of(c):
+    """The float32 points o + d z of every dense point id, as the reference forms them (renderer.py:233): for the CPU stand-in of
+    the SDF side."""
+    p = c["rays_o"][:, None, :] + c["rays_d"][:, None, :] * c["z"][:, :, None]
+    return p.reshape(-1, 3).astype(np.float32)
+
+
+# MODE 2 (vdn_shade_fused_bf16), name: (rays, T). One workgroup is one ray of 128 samples; T = 160 brings the background inputs
+# and a background colour. Depths sorted in [0, 1.6] from origins within 0.7 of the centre: samples on both sides of the unit sphere.
+SHADE_CASES = {"shade-B1-T128": (1, 128), "shade-B3-T160": (3, 160)}
+
+
+def shade_case(name):
+    B, T = SHADE_CASES[name]
+    N = 128
+    u = lambda tag, shape: synth.uniform(SEED, "mlp/%s/%s" % (name, tag), shape).astype(np.float32)
+    z = np.sort(1.6 * u("z", (B, N)), axis=1).astype(np.float32)
+    dists = np.concatenate([np.diff(z, axis=1), np.full((B, 1), 0.0125, np.float32)], 1).astype(np.float32)
+    c = {"name": name, "B": B, "n_per_ray": N, "N": N, "T": T, "P": B * N, "scale": 1.0, "rays_o": (0.8 * u("rays_o", (B, 3)) - 0.4),
+         "rays_d": _unit_dirs(name + "/rays_d", B), "z": z, "dists": dists, "variance": 0.3, "cos_anneal": 0.5,
+         "active_idx": None, "n_active": None, "state": "heads", "squeeze": True,
+         "bg_density": None, "bg_rgb": None, "bg_dists": None, "background_rgb": None}
+    if T > N:
+        c.update(bg_density=4.0 * u("bg_density", (B * T,)), bg_rgb=u("bg_rgb", (B * T, 3)), bg_dists=0.02 + 0.05 * u("bg_dists", (B, T)),
+                 background_rgb=np.ones(3, np.float32))
+    return c
+
+
+# MODE 4 (vdn_shade_points_bf16), name: (P, weight state). Points uniform in [-1.1, 1.1]^3, the row counts of the SDF cases; once
+# on the state whose sdf is constant: the gradient is exactly zero and the view direction must be zero, never NaN.
+POINT_CASES = {"points-P1": (1, "heads"), "points-P33": (33, "heads"), "points-P129": (129, "heads"), "points-P300": (300, "heads"),
+               "flat-P33": (33, "heads-flat")}
+
+
+def point_case(name):
+    P, state = POINT_CASES[name]
+    pts = (2.2 * synth.uniform(SEED, "mlp/%s/pts" % name, (P, 3)) - 1.1).astype(np.float32)
+    return {"name": name, "P": P, "scale": 1.0, "pts": pts, "active_idx": None, "n_active": None, "state": state, "squeeze": True}
 
 
 # ---- the background network ---------------------------------------------------------------------------------------------------

@@ -34,6 +34,8 @@ Where an operand is not bit for bit a plane the test can read - the plane contra
 | softplus' in the sweep   | formed from the activation itself, the model's from the saved (rounded) H[l] | |u| ln 2 2^-H 2^-9 H | include/vdn_render.h VdnSdfArgs.H |
 | normals                  | hardware sine / cosine in J_PE                                  | scale sum_k 2^k (2^-18 + 2^-23 |arg|) (|u_sin| + |u_cos|) | include/vdn_render.h, VdnSdfArgs.PE |
 | f32 outputs of an MFMA layer (heads' out; background density, rgb, feat) | the accumulator is rounded once per k-step of 16 inputs: 2 kt roundings, each up to 2^-24 of the running sum, where the unit counts one | (2 kt - 1) 2^-24 sum |w x| (times |f'|) | include/vdn_render.h, VdnRenderNetArgs.out and VdnNerfArgs.density |
+| h0 of the colour head inside the fused SDF launches (col_h[0]) | the 33rd small input, the normal's z, enters behind the MFMA accumulation as one f32 fmaf(tail, nz, acc) on the F32 normal (not on its bf16 copy in col_small) with the f32 weight column of the chunks' tails: one more rounding of the whole sum than the unit counts | 2^-24 (sum |w x| + |b| + |tail nz|) | include/vdn_render.h, vdn_sdf_color_train_bf16; vdn_hip/images.py rendering_streams ("c2") |
+| col_small, columns 0..2  | the point is formed in the launch, o + d z in f32 (fused or not), unscaled | none; unit 2^-24 (|d z| + |p|) | include/vdn_render.h, vdn_sdf_color_train_bf16 |
 | 1 - s_l in ex_l          | formed from the rounded s_l = 1 - 2^-H (ex_l = 100 vbar_l v_l (1 - s_l)): an absolute error of one rounding below 1, whatever the size of 1 - s_l | in the unit of EX[l]: 2^-24 ln 2 |vbar_l V[l]| | DESIGN.md section 4; include/vdn_render.h VdnSdfRbarArgs.s_from_h |
 | ex_l in the split launch | it stays in its wave                                            | none: the launch gives UB and AB bit for bit as rbar then fbar, so EX is read from the two-launch run | include/vdn_render.h, vdn_sdf_bwd_split_bf16 |
 | adjoints of the encoded inputs (d_dirs of the heads, d_pts4 / d_dirs of the background network, d_pts of fbar) | no plane holds them: the output is modelled in one piece from the last saved delta / ab blocks | what the accumulated adjoints may carry (2 kt roundings each, at three times the floor) through |J| <= 2^k, and the hardware trig | include/vdn_render.h VdnRenderNetBwdArgs.d_dirs, VdnNerfInputGradArgs, VdnSdfFbarArgs.d_pts |
@@ -42,6 +44,9 @@ Where an operand is not bit for bit a plane the test can read - the plane contra
 The heads' forward (colour head, VDN head: small_inputs, dense_relu, dense_out) and the background network's (plain_encoding,
 nerf_plane_models) are in network units, and every operand there IS a plane the test reads: their only extra terms are the
 hardware sine of the encodings and the accumulation term of the f32 outputs.
+The colour head that runs INSIDE the fused SDF launches (vdn_sdf_color_train_bf16, vdn_shade_fused_bf16, vdn_shade_points_bf16:
+ray_rows, fused_small_inputs, fused_layer0, fused_head_plane_models) is the same network in another execution, with the two rows
+of the table that name it.
 The heads' backward (vdn_rendernet_bwd_bf16: head_delta_out, relu_chain_step) follows them.
 So does the background network's backward (vdn_nerf_mlp_bwd_bf16: nerf_bwd_plane_models).
 and its input adjoints (vdn_nerf_mlp_bwd_input_bf16: nerf_input_adjoint_models), and the SDF backward (vdn_sdf_bwd_rbar_bf16 /
@@ -446,6 +451,88 @@ def simulate_head_forward(ops, pts, dirs, normals, feat_plane, squeeze, d_out, r
         x = planes["h%d" % l]
     planes["out"] = dense_out(x, ops[4]["W"], ops[4]["b"], squeeze, d_out, torch.float32)["y"]
     return planes
+
+
+# ---- the colour head inside the fused SDF launches (csrc/k_sdf_fwd2.h MODE 2 / 3 / 4; the 'c2' stream) --------------------------
+# The same network as above in another execution: the feature vector stays in registers (the bits of the feature plane), the point
+# and the view direction are formed per row from the ray (MODE 4: from the normal), the first layer contracts [feat (256) | small
+# columns 0..31] on the matrix pipe and takes the 33rd small input, the normal's z, as an f32 rank-1 fmaf with the weight column
+# that rides in the chunks' tails. MODE 3 saves col_small / col_h[0..3] / col_out: the planes modelled here.
+
+def ray_rows(rays_o, rays_d, z, row_points, dtype=torch.float64):
+    """Per row: p = o + d z of the row's own ray and sample (UNSCALED: renderer.py:233; the SDF network's scale is not applied), that
+    ray's d, and |d z| for the unit. row_points [rows]: dense point ids r * n_per_ray + s, n_per_ray = z.shape[1]."""
+    ids = np.asarray(row_points, np.int64)
+    r, s = ids // np.shape(z)[1], ids % np.shape(z)[1]
+    o, d = _t(np.asarray(rays_o)[r], dtype), _t(np.asarray(rays_d)[r], dtype)
+    dz = d * _t(np.asarray(z)[r, s], dtype)[:, None]
+    return {"pts": (o + dz).double().numpy(), "dirs": d.double().numpy(), "dz": dz.abs().double().numpy()}
+
+
+def fused_small_inputs(pts, dirs, normals_f32, dz=None, dtype=torch.float64):
+    """The [rows, 33] small plane of the fused head: small_inputs (the trig unit and the hardware-trig extra term of PE4(d)) with
+    the point's own unit - one f32 multiply-add o + d z, fused or not: 2^-24 (|d z| + |p|); dz None: the point is an input."""
+    m = small_inputs(pts, dirs, normals_f32, dtype)
+    if dz is not None:
+        m["unit"][:, :3] = U24 * (np.asarray(dz, np.float64) + np.abs(m["y"][:, :3]))
+    return m
+
+
+def fused_layer0(feat_plane, small_plane, nz_f32, W, b, tail, dtype=torch.float64):
+    """h0 = relu(W [feat (256) | small columns 0..31] + tail nz + b): the matrix part on the two bf16 planes, the rank-1 term on
+    the F32 normal's z with the f32 tail column. mag includes |tail nz|."""
+    x = np.concatenate([np.asarray(feat_plane, np.float64), np.asarray(small_plane, np.float64)[:, :32]], -1)
+    X, Wt, bt = _t(x, dtype), _t(W, dtype), _t(b, dtype)
+    rank1 = _t(nz_f32, dtype)[:, None] * _t(tail, dtype)[None, :]
+    t = (X @ Wt.T + bt) + rank1
+    mag = X.abs().double() @ Wt.abs().double().T + bt.abs().double() + rank1.abs().double()
+    return {"y": torch.relu(t).double().numpy(), "t": t.double().numpy(), "mag": mag.numpy()}
+
+
+def fused_head_plane_models(ops_c2, rays_o, rays_d, z, row_points, normals_f32, feat_plane, planes, squeeze, scale):
+    """{plane: dict(y64, y32, unit, extra, stored)} of the colour head inside one vdn_sdf_color_train_bf16 launch: small from the
+    rays and the launch's own f32 normals (rows in list order), h0 from the feature plane and the small plane it saved, h1..h3 and
+    out from the plane before. ops_c2: layers 0..4 of 'c2'. `scale` (the SDF network's) does not enter: the point is unscaled and
+    the normals the launch wrote already carry it; it is an argument so that a caller cannot forget that it must not."""
+    del scale
+    nrm = np.asarray(normals_f32, np.float32).astype(np.float64)
+    out = {}
+    rows = {dt: ray_rows(rays_o, rays_d, z, row_points, dt) for dt in (torch.float64, torch.float32)}
+    s64, s32 = (fused_small_inputs(rows[dt]["pts"], rows[dt]["dirs"], nrm, rows[dt]["dz"], dt) for dt in (torch.float64, torch.float32))
+    out["small"] = dict(y64=s64["y"], y32=s32["y"], unit=s64["unit"], extra=s64["extra"], stored="bf16")
+    m64, m32 = (fused_layer0(feat_plane, planes["small"], nrm[:, 2], ops_c2[0]["W"], ops_c2[0]["b"], ops_c2[0]["tail"], dt)
+                for dt in (torch.float64, torch.float32))
+    # (the table at the top: the fmaf behind the accumulation is one more rounding of the whole sum)
+    out["h0"] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=U24 * m64["mag"], stored="bf16")
+    x = planes["h0"]
+    for l in (1, 2, 3):
+        m64, m32 = (dense_relu(x, ops_c2[l]["W"], ops_c2[l]["b"], dt) for dt in (torch.float64, torch.float32))
+        out["h%d" % l] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored="bf16")
+        x = planes["h%d" % l]
+    o64, o32 = (dense_out(x, ops_c2[4]["W"], ops_c2[4]["b"], squeeze, 3, dt) for dt in (torch.float64, torch.float32))
+    out["out"] = dict(y64=o64["y"], y32=o32["y"], unit=o64["unit"], extra=o64["extra"], stored="f32")
+    return out
+
+
+def simulate_fused_head_forward(ops_c2, pts, dirs, normals_f32, feat_plane, squeeze, rnd=bf16_rne, dtype=torch.float32, nz=None):
+    """The CPU stand-in of the fused head on per-row points and directions (ray_rows, or MODE 4's own), chained through its own
+    planes, each rounded by `rnd`. dtype = float32: the comparator's test; dtype = float64: the end-to-end reference of
+    vdn_shade_points_bf16 (whose planes nobody saves). nz: what enters the rank-1 term instead of normals[:, 2] (planted errors)."""
+    nrm = np.asarray(normals_f32, np.float32).astype(np.float64)
+    planes = {"small": rnd(fused_small_inputs(pts, dirs, nrm, None, dtype)["y"])}
+    planes["h0"] = rnd(fused_layer0(feat_plane, planes["small"], nrm[:, 2] if nz is None else nz, ops_c2[0]["W"], ops_c2[0]["b"],
+                                    ops_c2[0]["tail"], dtype)["y"])
+    for l in (1, 2, 3):
+        planes["h%d" % l] = rnd(dense_relu(planes["h%d" % (l - 1)], ops_c2[l]["W"], ops_c2[l]["b"], dtype)["y"])
+    planes["out"] = dense_out(planes["h3"], ops_c2[4]["W"], ops_c2[4]["b"], squeeze, 3, dtype)["y"]
+    return planes
+
+
+def view_down_the_normal(normals_f32):
+    """MODE 4's view direction in float64 from the f32 normals the launch wrote: -g / max(|g|, 1e-12) (include/vdn_render.h,
+    vdn_shade_points_bf16: a zero gradient gives a zero direction)."""
+    g = np.asarray(normals_f32, np.float32).astype(np.float64)
+    return -g / np.maximum(np.linalg.norm(g, axis=1, keepdims=True), 1e-12)
 
 
 # ---- the background network's forward (vdn_nerf_mlp_fwd_bf16): NeRF, fields.py:324-353 ----------------------------------------

@@ -262,11 +262,13 @@ def _hold(c, res, rows):
 
 @pytest.mark.parametrize("net,state", [("sdf_network", "init"), ("sdf_network", "hot"), ("color_network", "init"),
                                        ("depth_network", "init"), ("nerf", "init"), ("color_network", "heads"), ("nerf", "heads"),
-                                       ("color_network", "heads352"), ("nerf", "nodpt")])
+                                       ("color_network", "heads352"), ("nerf", "nodpt"), ("color_network", "heads-other")])
 def test_blob_holds_the_operand_weights(net, state):
     """vdn_build_images, fmt 1: every chunk of every stream decoded by the documented layout (vdn_hip/layout.py
     decode_chunk_bf16) equals operand_weights - bf16_rne(float32(scale) W_eff[nmap, kmap]), zeros at -1 map entries, the float32
-    bias block, the tail constants - exactly; the rest of the bias block's KiB is zero."""
+    bias block, the tail constants - exactly; the rest of the bias block's KiB is zero. The colour network's states "heads" and
+    "heads-other" are those of tests/test_gpu_fused_head_planes.py: their "c2" stream (the fused SDF launches' colour head) carries
+    source column 32 of lin0 in every chunk's tail, which has to be among the decoded streams."""
     from vdn_hip import images, layout
     img = getattr(_renderer(state), net)._images()
     torch.cuda.synchronize()
@@ -296,6 +298,8 @@ def test_blob_holds_the_operand_weights(net, state):
                 off += stride
                 n_chunks += 1
     assert n_chunks > 20
+    if net == "color_network" and state != "heads352":
+        assert "c2" in img.blobs and all(L.tail is not None and L.tail[2] == 256 for L in img.streams["c2"])
 
 
 # ---- the SDF forward --------------------------------------------------------------------------------------------------------

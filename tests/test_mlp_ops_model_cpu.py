@@ -421,6 +421,187 @@ def test_head_comparator_rejects_each_planted_error(name, plant):
             assert j["ok"], (name, plant, k, j)
 
 
+# ---- the colour head inside the fused SDF launches ------------------------------------------------------------------------------
+
+FUSED_NAMES = list(mlp_cases.FUSED_CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def _c2_host(state="heads"):
+    from vdn_hip import images
+    st = images.rendering_streams(d_feature=256, mode="idr", d_in=9, d_out=3, d_hidden=256, n_layers=4, multires_view=4)
+    sd = mlp_cases.fused_states(state)["color_network_fine"]
+    return mlp_ops.HostImages.of_sdf_state(sd, st, np.float32, n_layers=5)
+
+
+@functools.lru_cache(maxsize=None)
+def _c2_ops(state="heads"):
+    return [mlp_ops.operand_weights(_c2_host(state), "c2", l) for l in range(5)]
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_setup(name):
+    """The case with the CPU stand-in of its SDF side (the float32 chain of simulate_sdf_forward on the case's SDF state): the
+    feature plane, the same features unrounded, the f32 normals, per row of the saved planes."""
+    c = mlp_cases.fused_case(name)
+    host = mlp_ops.HostImages.of_sdf_state(mlp_cases.fused_states(c["state"])["sdf_network_fine"], _streams())
+    ops, sweep = mlp_ops.sdf_ops(host), mlp_ops.sdf_sweep_ops(host)
+    rows = mlp_cases.fused_rows_of(c)
+    sp = mlp_ops.simulate_sdf_forward(ops, mlp_cases.fused_points_of(c)[rows], c["scale"], ops_sweep=sweep)
+    raw = mlp_ops.sdf_last(sp["H7"], ops[8]["W"], ops[8]["b"], ops[8]["tail"], c["scale"], torch.float32)["feat"]
+    rr = mlp_ops.ray_rows(c["rays_o"], c["rays_d"], c["z"], rows, torch.float32)
+    return {"c": c, "rows": rows, "feat": sp["feat"], "feat_f32": raw, "normals": sp["normals"].astype(np.float32),
+            "pts": rr["pts"], "dirs": rr["dirs"], "H_max": max(float(sp["H%d" % l].max()) for l in range(8))}
+
+
+def _fused_sim(s, ops=None, rnd=mlp_ops.bf16_rne, **kw):
+    a = dict(pts=s["pts"], dirs=s["dirs"], feat=s["feat"], nz=None)
+    a.update(kw)
+    return mlp_ops.simulate_fused_head_forward(ops or _c2_ops(), a["pts"], a["dirs"], s["normals"], a["feat"], True, rnd, nz=a["nz"])
+
+
+def _fused_judged(s, planes):
+    c = s["c"]
+    models = mlp_ops.fused_head_plane_models(_c2_ops(), c["rays_o"], c["rays_d"], c["z"], s["rows"], s["normals"], s["feat"], planes,
+                                             c["squeeze"], c["scale"])
+    return mlp_ops.judge_planes(models, planes), models
+
+
+def test_fused_cases_reach_every_row_path():
+    cs = {n: mlp_cases.fused_case(n) for n in FUSED_NAMES}
+    assert {c["P"] for c in cs.values() if c["active_idx"] is None} == {1, 33, 129, 300}
+    assert {c["scale"] for c in cs.values()} == {1.0, 1.5} and cs["rays-12x25-s1.5"]["P"] == 300
+    assert cs["rays-3x11-s1"]["n_per_ray"] == 11 and cs["rays-43x3-s1"]["n_per_ray"] == 3      # ray boundaries inside a wave
+    w = cs["worklist-8x25-n77-s1"]
+    idx = w["active_idx"][:77]
+    assert w["P"] == 200 and len(set(idx.tolist())) == 77 and (np.diff(idx) < 0).any() and (w["active_idx"][77:] == -1).all()
+    for n, c in cs.items():
+        assert (c["rays_o"][0] == 0).all() and (c["rays_d"][0] == (1.0, 0.0, 0.0)).all(), n
+        assert np.abs(np.linalg.norm(c["rays_d"], axis=1) - 1).max() < 1e-6
+        if c["B"] > 1:          # far more than a bf16 step (2^-7 at 1) in every component of neighbouring rays
+            assert np.abs(np.diff(c["rays_d"], axis=0)).min() >= mlp_cases.DIR_GAP > 4 * 2.0 ** -7, n
+        if c["P"] >= 3:
+            assert (c["z"] == 0).sum() == 1 and (c["z"] < 0).sum() == 1, n
+    init, hot = _fused_setup("rays-43x3-s1"), _fused_setup("hot-43x3-s1")
+    assert hot["H_max"] < 2.0 ** 10 and np.abs(hot["feat"]).max() > 4 * np.abs(init["feat"]).max()      # large features into the head
+    for state in ("heads", "heads-other"):                   # the silenced unit's row of the tail column is zero as well
+        o = _c2_ops(state)[0]
+        u = mlp_cases.SILENT_UNIT
+        assert o["W"].shape == (256, 288) and o["kt"] == 9 and o["tail"].shape == (256,)
+        assert not o["W"][u].any() and o["b"][u] == 0 and o["tail"][u] == 0 and np.count_nonzero(o["tail"]) == 255
+        assert np.array_equal(o["tail"], _c2_host(state).weff["lin0"][:, 32].astype(np.float64))
+    flat = mlp_cases.fused_states("heads-flat")["sdf_network_fine"]
+    assert flat["lin8.weight_g"][0] == 0 and np.count_nonzero(flat["lin8.weight_g"]) == flat["lin8.weight_g"].size - 1
+
+
+@pytest.mark.parametrize("name", FUSED_NAMES)
+def test_fused_head_comparator_accepts_both_roundings_and_the_cases_cover(name):
+    """No false alarm: the float32 stand-in passes every plane of every case, rounded either way. Coverage: the silenced unit gives
+    exact zeros that admit nothing else; every hidden layer has relu inputs of both signs; on the init states no sigmoid output is
+    saturated (all within [0.02, 0.98]), so that the output's unit measures the kernel."""
+    s = _fused_setup(name)
+    for rnd in (mlp_ops.bf16_rne, mlp_ops.bf16_trunc):
+        planes = _fused_sim(s, rnd=rnd)
+        res, models = _fused_judged(s, planes)
+        assert set(res) == {"small", "h0", "h1", "h2", "h3", "out"}
+        for k, j in res.items():
+            assert j["ok"], (name, rnd.__name__, k, j)
+    for k, j in res.items():
+        print("%-22s %-6s floor %.3f units  bound %.2f" % (name, k, j["floor"], j["bound"]))
+    u = mlp_cases.SILENT_UNIT
+    for k in ("h0", "h2"):
+        assert (models[k]["y64"][:, u] == 0).all() and (models[k]["unit"][:, u] == 0).all() and (planes[k][:, u] == 0).all()
+        assert np.all(np.broadcast_to(models[k]["extra"], models[k]["y64"].shape)[:, u] == 0)
+        planes[k][0, u] = 2.0 ** -126
+        assert not _fused_judged(s, planes)[0][k]["ok"]
+        planes[k][0, u] = 0.0
+    if s["c"]["P"] > 1:
+        o = _c2_ops()
+        t = [mlp_ops.fused_layer0(s["feat"], planes["small"], s["normals"][:, 2], o[0]["W"], o[0]["b"], o[0]["tail"])["t"]]
+        t += [mlp_ops.dense_relu(planes["h%d" % (l - 1)], o[l]["W"], o[l]["b"])["t"] for l in (1, 2, 3)]
+        assert all((a > 0).any() and (a < 0).any() for a in t)
+    if s["c"]["state"] == "heads":
+        assert planes["out"].min() >= 0.02 and planes["out"].max() <= 0.98, (planes["out"].min(), planes["out"].max())
+    if name != "rays-1x1-s1":                               # ray 0: the sines of its zero components
+        assert (models["small"]["y64"][s["rows"] < s["c"]["n_per_ray"]][:, [7, 8, 13, 14, 19, 20, 25, 26]] == 0).all()
+
+
+def _fd_nz_bf16(s):
+    return _fused_sim(s, nz=mlp_ops.bf16_rne(s["normals"][:, 2]))
+
+
+def _fd_tail_column_31(s):
+    ops = _copy(_c2_ops())
+    ops[0]["tail"] = _c2_host().weff["lin0"][:, 31].astype(np.float64)
+    return _fused_sim(s, ops=ops)
+
+
+def _fd_small_30_31(s):
+    planes = _fused_sim(s)
+    # (the launch forms the tile once: the saved plane and the first layer's operand are swapped alike)
+    sw = s["normals"].copy()
+    sw[:, [0, 1]] = sw[:, [1, 0]]
+    wrong = mlp_ops.simulate_fused_head_forward(_c2_ops(), s["pts"], s["dirs"], sw, s["feat"], True, nz=s["normals"][:, 2])
+    assert np.array_equal(wrong["small"][:, :30], planes["small"][:, :30])
+    return wrong
+
+
+def _fd_next_rays_direction(s):
+    c = s["c"]
+    r = np.minimum((s["rows"] + 1) // c["n_per_ray"], c["B"] - 1)
+    return _fused_sim(s, dirs=c["rays_d"][r].astype(np.float64))
+
+
+def _fd_scaled_point(s):
+    return _fused_sim(s, pts=s["pts"] * s["c"]["scale"]) if s["c"]["scale"] != 1.0 else None
+
+
+def _fd_feature_unrounded(s):
+    return _fused_sim(s, feat=s["feat_f32"])
+
+
+def _fd_out_rows(s):
+    ops = _copy(_c2_ops())
+    ops[4]["W"][[0, 1]], ops[4]["b"][[0, 1]] = ops[4]["W"][[1, 0]], ops[4]["b"][[1, 0]]
+    return _fused_sim(s, ops=ops)
+
+
+def _fd_small_32_unwritten(s):
+    planes = _fused_sim(s)
+    planes["small"][:, 32] = np.nan                          # (what the NaN pre-fill of the GPU test leaves there)
+    return planes
+
+
+# planted defect -> (the plane that has to catch it, the stand-in with the defect; None where the case cannot show it)
+FUSED_DEFECTS = {"nz-rounded-to-bf16": ("h0", _fd_nz_bf16), "tail-from-column-31": ("h0", _fd_tail_column_31),
+                 "small-columns-30-31-swapped": ("small", _fd_small_30_31), "direction-of-the-next-ray": ("small", _fd_next_rays_direction),
+                 "point-times-scale": ("small", _fd_scaled_point), "feature-operand-unrounded": ("h0", _fd_feature_unrounded),
+                 "output-rows-permuted": ("out", _fd_out_rows), "small-column-32-unwritten": ("small", _fd_small_32_unwritten)}
+
+
+@pytest.mark.parametrize("plant", list(FUSED_DEFECTS))
+def test_fused_head_comparator_rejects_each_planted_defect(plant):
+    """Each defect the fused head could have without the end-to-end tests noticing, planted into the float32 stand-in, is rejected on
+    at least one committed case by the plane it is in (and wherever it is rejected, no plane BEFORE that one complains)."""
+    where, make = FUSED_DEFECTS[plant]
+    order = ["small", "h0", "h1", "h2", "h3", "out"]
+    caught = []
+    for name in FUSED_NAMES:
+        s = _fused_setup(name)
+        planes = make(s)
+        if planes is None:
+            continue
+        res, _ = _fused_judged(s, planes)
+        for k in order[:order.index(where)]:
+            assert res[k]["ok"], (plant, name, k, res[k])
+        if not res[where]["ok"]:
+            caught.append(name)
+        print("%-30s %-22s plane %-5s %s  error %.3g units (bound %.2f), %d of %d elements outside" % (
+            plant, name, where, "REJECTED" if not res[where]["ok"] else "passes", res[where]["err"], res[where]["bound"],
+            res[where]["n_bad"], res[where]["n"]))
+    assert caught, "%s: plane %s rejects it on no case" % (plant, where)
+
+
 # ---- the background network's forward -------------------------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)
