@@ -1221,6 +1221,75 @@ typedef struct {
 int vdn_cluster_quadrics(const VdnClusterQuadricArgs* args_host, void* stream);
 int vdn_cluster_place(const VdnClusterQuadricArgs* args_host, void* stream);
 
+/* ---- textured meshes: a per-face atlas baked on the device (csrc/mesh_texture.hip; vdn_hip/mesh.py: texel_points, project_step,
+ * gather_atlas, sample_texture, bake_texture) -----------------------------------------------------------------------
+ * The atlas is S x S texels, uint8 RGB, row 0 at the top, cut into C x C square cells of n x n texels, C = S / n (integer), n >= 4;
+ * the strip right of and below the cells (S % n columns and rows) is unused. Face f owns half h = f & 1 of cell c = f >> 1, whose
+ * origin is the texel ((c % C) n, (c / C) n). With m = n - 3 and local texel (i, j) = (column, row) inside the cell:
+ *   lower half (h = 0): owns i + j <= n - 2, T = n (n - 1) / 2 texels. Corners 0, 1, 2 of the face sit at the texel centres (0, 0),
+ *     (m, 0), (0, m), i.e. at the continuous coordinates (0.5, 0.5), (m + 0.5, 0.5), (0.5, m + 0.5). A texel with i + j <= m has the
+ *     barycentrics b1 = i / m, b2 = j / m, b0 = (1 - b1) - b2; a gutter texel, i + j = n - 2, takes the nearest point of the
+ *     hypotenuse: b1 = clamp((i - 0.5) / m, 0, 1), b2 = 1 - b1, b0 = 0.
+ *   upper half (h = 1): the lower half turned by 180 degrees - local (i, j) is read as (n - 1 - i, n - 1 - j) - so it owns
+ *     i + j >= n and its corners sit at (n - 0.5, n - 0.5), (n - 0.5 - m, n - 0.5), (n - 0.5, n - 0.5 - m).
+ *   the diagonal i + j = n - 1 belongs to nobody and repeats the texel (i, j - 1), or (i - 1, 0) where j = 0 (both are gutter texels
+ *     of the lower half); every other unowned texel - the upper half of a last, half-filled cell, empty cells, the strip - is 0.
+ * Texel points are numbered face-major, q = f T + r, r running over j = 0 .. n - 2 (outer), i = 0 .. n - 2 - j (inner) in the
+ * half's own (turned) frame: r = j (2 n - 1 - j) / 2 + i. All of it is integer arithmetic, restated in tests/test_mesh_texture_cpu.py.
+ *   vdn_tex_points:  one thread per texel point q: points[q] = fp32((b0 v0 + b1 v1) + b2 v2) in double from the double vertices (every
+ *                    product and sum rounded on its own: the file is built without contraction), face[q] = f. A corner index outside
+ *                    [0, V) sets *error = 1 (the caller zeroes it first) and gives the point (0, 0, 0).
+ *   vdn_tex_gather:  one thread per atlas texel, gather form: the texel finds its cell, its half and r (or the diagonal's source, or
+ *                    nothing) and writes its three bytes once, rint(clip(c, 0, 1) * 255) in fp32 of colors[q] read in BGR order and
+ *                    stored as RGB (vdn_hip.mesh.quantize_colors_bgr). n_colors must equal F T.
+ *   vdn_tex_sample:  one thread per query: face[r] in [0, F) and a point. (b1, b2) of the point's projection onto the face's plane
+ *                    solve the 2 x 2 normal equations of e1 = v1 - v0, e2 = v2 - v0 against w = p - v0 in double:
+ *                      det = a11 a22 - a12 a12;  b1 = (a22 r1 - a12 r2) / det;  b2 = (a11 r2 - a12 r1) / det
+ *                    (b1 = b2 = 0 where det is not positive and finite), clamped into the triangle: b1 = max(b1, 0), b2 = max(b2, 0),
+ *                    and where s = b1 + b2 > 1 both are divided by s (NaN compares false: such a coordinate becomes 0). Continuous
+ *                    atlas coordinates: x = ox + 0.5 + m b1, y = oy + 0.5 + m b2 (lower), x = ox + n - 0.5 - m b1, y = oy + n - 0.5 - m b2
+ *                    (upper). Bilinear taps at floor(x - 0.5), floor(y - 0.5) and their successors, indices clamped to [0, S - 1];
+ *                    rgb = fp32(((w00 t00 + w10 t10) + (w01 t01 + w11 t11)) / 255) per channel in double. A face outside [0, F)
+ *                    (-1 = miss) gives the background; a corner index outside [0, V) sets *error = 1 and gives the background.
+ * Inside a face every tap with a non-zero weight is a texel the face owns, so nothing bleeds between faces under
+ * bilinear filtering at the base level; mip levels mix neighbours. Status -10: V, F, F T, R or S S beyond 32-bit indexing. */
+typedef struct {
+    const double* vertices;        /* [V][3]   (points, sample) */
+    const void* triangles;         /* [F][3] int64 or int32 (index_bytes)   (points, sample) */
+    float* points;                 /* [F T][3] out   (points) */
+    int32_t* face;                 /* [F T] out   (points) */
+    int32_t* error;                /* [1]   (points, sample) */
+    const float* colors;           /* [n_colors][3] BGR   (gather) */
+    uint8_t* atlas;                /* [S][S][3] RGB: out (gather), in (sample) */
+    const int64_t* hit_face;       /* [R]   (sample) */
+    const double* hit_points;      /* [R][3]   (sample) */
+    float* rgb;                    /* [R][3] out   (sample) */
+    int64_t V, F, R, n_colors;
+    double bg_r, bg_g, bg_b;       /* the colour of a miss   (sample) */
+    int32_t S, n, index_bytes, _pad;
+} VdnTexArgs;
+int vdn_tex_points(const VdnTexArgs* args_host, void* stream);
+int vdn_tex_gather(const VdnTexArgs* args_host, void* stream);
+int vdn_tex_sample(const VdnTexArgs* args_host, void* stream);
+
+/* vdn_tex_project: one Newton step of N points towards the level set of a field whose value and gradient the caller evaluated at x,
+ * held inside the ball of radius max_offset around x0. One thread per point, in double on the widened fp32 inputs:
+ *   den = max((gx gx + gy gy) + gz gz, 1e-12);  y = x + (-sdf g) / den;  e = y - x0;  r = sqrt((ex ex + ey ey) + ez ez);
+ *   r > max_offset: y = x0 + e (max_offset / r);   out = fp32(y).
+ * Where that rounding carries out past the ball (in double, from the rounded values), every component steps to the next fp32 towards
+ * x0, so |out - x0| <= max_offset holds for the stored floats. A non-finite sdf, g or result leaves the point where it was:
+ * out = x. out may be x itself. */
+typedef struct {
+    const float* x;                /* [N][3] */
+    const float* x0;               /* [N][3] */
+    const float* sdf;              /* [N] */
+    const float* g;                /* [N][3] */
+    float* out;                    /* [N][3] */
+    int64_t N;
+    double max_offset;
+} VdnTexProjectArgs;
+int vdn_tex_project(const VdnTexProjectArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

@@ -18,7 +18,12 @@ or any hit, two-sided Moller-Trumbore in double); visibility_votes counts the ca
 
 Simplification (csrc/mesh_simplify.hip; the front door is vdn_train/mesh_simplify.py): cluster_quadrics groups the vertices by the
 cells of a uniform grid and sums each cluster's quadric in a fixed order, simplify_mesh places one vertex per cluster and emits the
-triangles that survive, count_simplified_faces is the count-only pass a face budget is searched with."""
+triangles that survive, count_simplified_faces is the count-only pass a face budget is searched with.
+
+Textured meshes (csrc/mesh_texture.hip; the front door is vdn_train/mesh_texture.py): texture_layout gives every face a triangular
+patch of a per-face atlas, texel_points / project_points place a surface point under every texel, gather_atlas writes the shaded
+colours into the atlas, bake_texture is the three in a row; sample_texture looks an atlas up at points of the mesh and
+render_textured_view does that where rays hit."""
 import math
 import os
 
@@ -523,6 +528,7 @@ class MeshGrid:
         if F > 0 and V == 0:
             raise ValueError("a triangle refers to a vertex outside [0, 0)")
         self.device, self.V, self.F = dev, V, F
+        self.vertices, self.triangles = v, t                  # (the arrays the grid was built from: render_textured_view samples on them)
         lo, hi, mean_extent = [0.0] * 3, [0.0] * 3, 0.0
         with torch.cuda.device(dev):
             if F > 0:
@@ -985,3 +991,295 @@ def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="qua
                   faces_duplicate=n_surv - int(new_t.shape[0]), status={str(k): int(n) for k, n in enumerate(n_stat)})
     return {"vertices": new_v.to(vertices.dtype), "triangles": new_t, "attributes": out_attrs,
             "vertex_cluster": new_of_cluster[s["vertex_cluster"]], "status": status, "report": report}
+
+
+# ---- textured meshes: a per-face atlas (csrc/mesh_texture.hip) ----------------------------------------------------------
+TEXTURE_MIN_PATCH = 4        # m = n - 3 >= 1: a patch needs its three corner texels apart, a gutter and the diagonal
+TEXTURE_PROJECT_ROUNDS = 2   # Newton steps of the texel points towards the level set: an interface default, not a measurement
+
+
+def texture_layout(F, texture_size, patch=None):
+    """The atlas layout of F faces on a texture_size^2 atlas (include/vdn_render.h has the rules) -> dict(F, S, n, C, T, m, points):
+    n the cell edge in texels, C = S // n cells per row, T = n (n - 1) / 2 texels per face, m = n - 3, points = F T. patch=None picks
+    the largest n with ceil(F / 2) <= (S // n)^2. ValueError when even n = 4 does not fit, or a given patch does not. Host integers."""
+    try:
+        F_, S = int(F), int(texture_size)
+    except (TypeError, ValueError):
+        raise ValueError("F and texture_size must be integers, got %r and %r" % (F, texture_size))
+    if F_ != F or F_ < 0 or S != texture_size or S < TEXTURE_MIN_PATCH:
+        raise ValueError("texture_layout needs F >= 0 and texture_size >= %d as integers, got %r and %r" % (TEXTURE_MIN_PATCH, F, texture_size))
+    if S * S >= 1 << 31:
+        raise ValueError("texture_size %d: the atlas does not fit 32-bit indexing" % S)
+    cells = (F_ + 1) // 2
+    if patch is None:
+        k = max(1, math.isqrt(cells))                                              # ceil(sqrt(cells)), at least one cell per row
+        if k * k < cells:
+            k += 1
+        n = S // k                                                                 # the largest n with S // n >= k
+        if n < TEXTURE_MIN_PATCH:
+            raise ValueError("%d faces need %d x %d cells: a %d^2 atlas leaves them fewer than %d texels per edge" % (F_, k, k, S, TEXTURE_MIN_PATCH))
+    else:
+        try:
+            n = int(patch)
+        except (TypeError, ValueError):
+            raise ValueError("patch must be an integer, got %r" % (patch,))
+        if n != patch or n < TEXTURE_MIN_PATCH or n > S:
+            raise ValueError("patch must be an integer in [%d, texture_size], got %r" % (TEXTURE_MIN_PATCH, patch))
+        if cells > (S // n) ** 2:
+            raise ValueError("%d faces do not fit a %d^2 atlas in cells of %d texels (%d cells)" % (F_, S, n, (S // n) ** 2))
+    T = n * (n - 1) // 2
+    if F_ * T >= 1 << 31:
+        raise ValueError("%d faces of %d texels do not fit 32-bit indexing" % (F_, T))
+    return {"F": F_, "S": S, "n": n, "C": S // n, "T": T, "m": n - 3, "points": F_ * T}
+
+
+def texture_uv(layout):
+    """OBJ texture coordinates of every face corner -> float64 [F,3,2] numpy: vt = (x / S, 1 - y / S) of the corner's continuous
+    atlas position (x, y) (row 0 of the atlas is its top, v = 0 of an OBJ its bottom)."""
+    F, S, n, C, m = (layout[k] for k in ("F", "S", "n", "C", "m"))
+    f = np.arange(F, dtype=np.int64)
+    c, h = f >> 1, f & 1
+    ox, oy = ((c % C) * n).astype(np.float64), ((c // C) * n).astype(np.float64)
+    lower = np.array([[0.5, 0.5], [m + 0.5, 0.5], [0.5, m + 0.5]])
+    upper = np.array([[n - 0.5, n - 0.5], [n - 0.5 - m, n - 0.5], [n - 0.5, n - 0.5 - m]])
+    local = np.where((h == 0)[:, None, None], lower[None], upper[None])
+    x, y = ox[:, None] + local[:, :, 0], oy[:, None] + local[:, :, 1]
+    return np.stack([x / S, 1.0 - y / S], axis=-1)
+
+
+def _texture_mesh(name, vertices, triangles):
+    """-> (vertices float64 [V,3], triangles int32 / int64 [F,3]) contiguous on the device"""
+    _check_triangles(name, triangles)
+    _check_vertices(name, vertices, triangles)
+    if vertices.shape[0] >= 1 << 31 or triangles.shape[0] >= 1 << 31:
+        raise ValueError("%s: the sizes do not fit 32-bit indexing" % name)
+    if triangles.shape[0] > 0 and vertices.shape[0] == 0:
+        raise ValueError("a triangle refers to a vertex outside [0, 0)")
+    return vertices.detach().double().contiguous(), triangles.contiguous()
+
+
+def _check_layout(layout, F):
+    if not (isinstance(layout, dict) and all(k in layout for k in ("F", "S", "n", "C", "T", "m", "points"))):
+        raise ValueError("layout must be a record of texture_layout")
+    if layout["F"] != F:
+        raise ValueError("the layout is one of %d faces, the mesh has %d" % (layout["F"], F))
+    if layout != texture_layout(F, layout["S"], layout["n"]):
+        raise ValueError("the layout record is not one texture_layout gives")
+
+
+def _tex_args(layout, v=None, t=None):
+    a = lib.VdnTexArgs()
+    a.S, a.n, a.F = layout["S"], layout["n"], layout["F"]
+    if v is not None:
+        a.vertices, a.triangles, a.V, a.index_bytes = v.data_ptr(), t.data_ptr(), v.shape[0], t.element_size()
+    return a
+
+
+def texel_points(vertices, triangles, layout):
+    """The surface point every owned texel of the atlas shows (vdn_tex_points) -> (points [F T,3] fp32, face [F T] int32), face-major:
+    row f T + r is texel r of face f. vertices [V,3] CUDA float (taken as float64), triangles [F,3] CUDA int64 or int32. The points
+    are (b0 v0 + b1 v1) + b2 v2 in double, rounded once. ValueError on CPU tensors, wrong shapes or a corner index outside [0, V)."""
+    v, t = _texture_mesh("texel_points", vertices, triangles)
+    _check_layout(layout, t.shape[0])
+    dev, P = v.device, layout["points"]
+    points = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(P, dtype=torch.int32, device=dev)
+    if P == 0:
+        return points, face
+    with torch.cuda.device(dev):
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = _tex_args(layout, v, t)
+        a.points, a.face, a.error = points.data_ptr(), face.data_ptr(), err.data_ptr()
+        _call_sized("vdn_tex_points", a, lib.stream_handle())
+        if int(err.item()):                                   # one host read: the error flag
+            raise ValueError("a triangle refers to a vertex outside [0, %d)" % v.shape[0])
+    return points, face
+
+
+def _rows(name, x, n=None, cols=3):
+    """x as a contiguous fp32 tensor: [P,cols], or [P] with cols = 0; n: the row count it must have"""
+    ok = torch.is_tensor(x) and x.is_cuda and x.is_floating_point() and ((x.dim() == 2 and x.shape[1] == cols) if cols else x.dim() == 1)
+    if not (ok and (n is None or x.shape[0] == n)):
+        raise ValueError("%s must be a float CUDA tensor %s%s" % (name, "[P,%d]" % cols if cols else "[P]", "" if n is None else " with P = %d" % n))
+    return x.detach().float().contiguous()
+
+
+def project_step(x, x0, sdf, gradient, max_offset):
+    """One Newton step of the points x towards the zero level of a field with the values `sdf` [P] and gradients `gradient` [P,3] at
+    x, kept within max_offset of x0 (vdn_tex_project; all four fp32 CUDA tensors) -> x' [P,3] fp32:
+    x' = x - sdf g / max(|g|^2, 1e-12), pulled back onto the ball |x' - x0| <= max_offset; a row whose sdf, g or result is not finite
+    stays where it was."""
+    if not (torch.is_tensor(x) and torch.is_tensor(x0) and torch.is_tensor(sdf) and torch.is_tensor(gradient)):
+        raise ValueError("project_step needs CUDA tensors")
+    x = _rows("x", x)
+    P = x.shape[0]
+    x0, g, s = _rows("x0", x0, P), _rows("gradient", gradient, P), _rows("sdf", sdf.reshape(-1) if sdf.dim() == 2 and sdf.shape[1] == 1 else sdf, P, cols=0)
+    if not (x0.device == g.device == s.device == x.device):
+        raise ValueError("x, x0, sdf and gradient must be on one device")
+    try:
+        r = float(max_offset)
+    except (TypeError, ValueError):
+        raise ValueError("max_offset must be a number, got %r" % (max_offset,))
+    if not (r >= 0.0 and r < float("inf")):
+        raise ValueError("max_offset must be finite and not negative, got %r" % (max_offset,))
+    out = torch.empty_like(x)
+    if P > 0:
+        a = lib.VdnTexProjectArgs()
+        a.x, a.x0, a.sdf, a.g, a.out, a.N, a.max_offset = x.data_ptr(), x0.data_ptr(), s.data_ptr(), g.data_ptr(), out.data_ptr(), P, r
+        with torch.cuda.device(x.device):
+            _call_sized("vdn_tex_project", a, lib.stream_handle())
+    return out
+
+
+def project_points(renderer, points, rounds=TEXTURE_PROJECT_ROUNDS, max_offset=0.0, batch=1 << 20):
+    """`rounds` Newton steps of points [P,3] (CUDA, object space) towards the SDF network's zero level set, each row kept within
+    max_offset of where it started -> [P,3] fp32. Between the steps the value and the raw gradient come from shade_points (the
+    existing launch; its colour is not used), at most `batch` points at a time; then project_step. rounds = 0 returns the points."""
+    if int(rounds) != rounds or rounds < 0:
+        raise ValueError("rounds must be a non-negative integer, got %r" % (rounds,))
+    x0 = _rows("points", points)
+    x = x0
+    for _ in range(int(rounds)):
+        if renderer is None:
+            raise ValueError("projection needs the renderer: its SDF network is the level set")
+        sdf, g, _c = shade_points(renderer, x, batch=batch)
+        x = project_step(x, x0, sdf, g, max_offset)
+    return x
+
+
+def gather_atlas(colors, layout):
+    """The atlas of a layout from the colours of its texel points (vdn_tex_gather): colors [F T,3] float CUDA tensor in the
+    networks' BGR order -> uint8 [S,S,3] RGB, row 0 at the top; each byte is quantize_colors_bgr's rint(clip(c, 0, 1) * 255) in
+    fp32. The diagonal of every cell repeats its neighbour in the lower half; whatever no face owns is 0."""
+    if not (isinstance(layout, dict) and "points" in layout):
+        raise ValueError("layout must be a record of texture_layout")
+    _check_layout(layout, layout["F"])
+    if not torch.is_tensor(colors):
+        raise ValueError("gather_atlas needs colours as a float [F T,3] CUDA tensor")
+    c = _rows("colors", colors, layout["points"])
+    S = layout["S"]
+    atlas = torch.empty(S, S, 3, dtype=torch.uint8, device=c.device)
+    a = _tex_args(layout)
+    a.colors, a.n_colors, a.atlas = (c.data_ptr() if c.shape[0] > 0 else None), c.shape[0], atlas.data_ptr()
+    with torch.cuda.device(c.device):
+        _call_sized("vdn_tex_gather", a, lib.stream_handle())
+    return atlas
+
+
+def sample_texture(texture, layout, vertices, triangles, face, points, background=(1.0, 1.0, 1.0)):
+    """Bilinear lookups of an atlas at points of the mesh (vdn_tex_sample): texture uint8 [S,S,3] CUDA, layout its record, face [R]
+    integers (-1 = miss) and points [R,3] (taken as float64) -> fp32 [R,3] RGB in [0, 1]. A point is projected onto its face's plane
+    and clamped into the triangle; a miss gives `background`. vertices are taken as float64."""
+    v, t = _texture_mesh("sample_texture", vertices, triangles)
+    _check_layout(layout, t.shape[0])
+    dev, S = v.device, layout["S"]
+    if not (torch.is_tensor(texture) and texture.device == dev and texture.dtype == torch.uint8 and tuple(texture.shape) == (S, S, 3)):
+        raise ValueError("texture must be a uint8 [%d,%d,3] tensor on the mesh's device" % (S, S))
+    face, points = torch.as_tensor(face), torch.as_tensor(points)
+    if face.dim() != 1 or face.is_floating_point() or face.dtype == torch.bool:
+        raise ValueError("face must be an integer [R] array")
+    R = face.shape[0]
+    if points.dim() != 2 or tuple(points.shape) != (R, 3) or not points.is_floating_point():
+        raise ValueError("points must be a float [%d,3] array, got %s" % (R, tuple(points.shape)))
+    try:
+        bg = [float(x) for x in background]
+        assert len(bg) == 3
+    except (TypeError, ValueError, AssertionError):
+        raise ValueError("background must be three numbers, got %r" % (background,))
+    face = face.detach().to(device=dev, dtype=torch.int64).contiguous()
+    points = points.detach().to(device=dev, dtype=torch.float64).contiguous()
+    rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    if R == 0:
+        return rgb
+    if t.shape[0] == 0:                                       # no face to hit: every query is a miss
+        rgb[:] = torch.tensor(bg, dtype=torch.float64, device=dev).float()
+        return rgb
+    with torch.cuda.device(dev):
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = _tex_args(layout, v, t)
+        a.atlas, a.hit_face, a.hit_points, a.rgb, a.R, a.error = texture.contiguous().data_ptr(), face.data_ptr(), points.data_ptr(), rgb.data_ptr(), R, err.data_ptr()
+        a.bg_r, a.bg_g, a.bg_b = bg
+        _call_sized("vdn_tex_sample", a, lib.stream_handle())
+        if int(err.item()):
+            raise ValueError("a triangle refers to a vertex outside [0, %d)" % v.shape[0])
+    return rgb
+
+
+def mean_edge_length(vertices, triangles):
+    """The mean length of the 3 F triangle sides, in double (one host read); 0.0 for an empty mesh."""
+    if triangles.shape[0] == 0:
+        return 0.0
+    p = vertices.double()[triangles.long()]
+    return float((p - p.roll(-1, dims=1)).norm(dim=2).mean())
+
+
+def bake_texture(renderer, vertices, triangles, texture_size=2048, patch=None, project=TEXTURE_PROJECT_ROUNDS, max_offset=None,
+                 shade=None, batch=1 << 20):
+    """Bake the appearance of a mesh into a per-face atlas -> {"texture": uint8 [S,S,3] RGB, "uv": float64 [F,3,2] (numpy: OBJ vt per
+    face corner), "layout": texture_layout's record, "points": fp32 [F T,3] the shaded points}; texture and points are device tensors.
+    vertices [V,3] float, triangles [F,3] integers, object space, numpy arrays or tensors (moved to the renderer's device, or cuda).
+    The texel points of the layout (texel_points) take `project` Newton steps towards the SDF network's level set, each within
+    max_offset (default: the mesh's mean edge length) of its place on the triangle (project_points; 0 switches it off), are shaded -
+    shade_points(renderer, points, batch): view = -normal, exactly as the vertices of a PLY are shaded - and gathered (gather_atlas).
+    `shade`: a callable (points [P,3] cuda fp32, face [P] int32) -> colour [P,3] float BGR that stands in for the colour network,
+    called with at most `batch` points; renderer may then be None when project is 0. patch / texture_size: texture_layout's; every
+    face gets the same patch, which suits meshes whose faces are of one size. An empty mesh gives an all-zero atlas. Filtering is
+    safe at the base level only: mip levels mix neighbouring patches."""
+    if int(project) != project or project < 0:
+        raise ValueError("project must be a non-negative integer, got %r" % (project,))
+    if int(batch) != batch or batch < 1:
+        raise ValueError("batch must be at least 1")
+    if shade is not None and not callable(shade):
+        raise ValueError("shade must be callable")
+    if renderer is None and (shade is None or project > 0):
+        raise ValueError("bake_texture needs the renderer unless `shade` is given and project is 0")
+    if renderer is not None:
+        dev = lib.first_param(renderer.sdf_network).device
+    else:
+        dev = next((x.device for x in (vertices, triangles) if torch.is_tensor(x) and x.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    to_dev = lambda x: x.to(dev) if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    v, t = to_dev(vertices), to_dev(triangles)
+    if v.dim() != 2 or v.shape[1] != 3 or t.dim() != 2 or t.shape[1] != 3 or not v.is_floating_point() or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError("bake_texture needs float vertices [V,3] and integer triangles [F,3]")
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.long()
+    F = t.shape[0]
+    layout = texture_layout(F, texture_size, patch)
+    if max_offset is not None and not (float(max_offset) >= 0.0 and float(max_offset) < float("inf")):
+        raise ValueError("max_offset must be finite and not negative, got %r" % (max_offset,))
+    with torch.cuda.device(dev), torch.no_grad():
+        if F == 0:
+            return {"texture": torch.zeros(layout["S"], layout["S"], 3, dtype=torch.uint8, device=dev), "uv": texture_uv(layout),
+                    "layout": layout, "points": torch.empty(0, 3, dtype=torch.float32, device=dev)}
+        points, face = texel_points(v, t, layout)
+        if project > 0:
+            r = mean_edge_length(v, t) if max_offset is None else float(max_offset)
+            points = project_points(renderer, points, rounds=project, max_offset=r, batch=batch)
+        if shade is None:
+            colors = shade_points(renderer, points, batch=batch)[2]
+            if colors.shape[1] != 3:
+                raise ValueError("a texture needs a colour network with three outputs, got %d" % colors.shape[1])
+        else:
+            colors = torch.empty(points.shape[0], 3, dtype=torch.float32, device=dev)
+            for s in range(0, points.shape[0], batch):
+                c = shade(points[s:s + batch], face[s:s + batch])
+                if not (torch.is_tensor(c) and tuple(c.shape) == (min(batch, points.shape[0] - s), 3)):
+                    raise ValueError("shade must return one BGR colour per point")
+                colors[s:s + batch] = c
+        texture = gather_atlas(colors, layout)
+    return {"texture": texture, "uv": texture_uv(layout), "layout": layout, "points": points}
+
+
+def render_textured_view(grid, texture, origins, directions, background=(1.0, 1.0, 1.0)):
+    """What a textured mesh looks like along rays: MeshGrid.cast (the closest hit) followed by sample_texture at o + t d -> fp32 [R,3]
+    RGB in [0, 1], `background` where a ray misses. grid: the MeshGrid of the baked mesh; texture: bake_texture's result (its
+    "texture" and "layout"). The preview of a bake, and its end-to-end check."""
+    if not isinstance(grid, MeshGrid):
+        raise ValueError("grid must be a MeshGrid of the baked mesh")
+    if not (isinstance(texture, dict) and "texture" in texture and "layout" in texture):
+        raise ValueError("texture must be the result of bake_texture")
+    o, d = grid._rays(origins, "origins"), grid._rays(directions, "directions")
+    t, face = grid.cast(o, d)
+    hit = face >= 0
+    x = o + torch.where(hit, t, torch.zeros_like(t))[:, None] * d
+    return sample_texture(texture["texture"], texture["layout"], grid.vertices, grid.triangles, face, x, background=background)

@@ -5,7 +5,10 @@ Layout (`binary_little_endian 1.0`):
   element vertex V:  float x y z, [float nx ny nz], [uchar red green blue]
   element face F:    property list uchar int vertex_indices   (always 3 indices: 13 bytes per face)
 Both elements are written from numpy structured arrays; read_ply reads exactly this layout and raises on anything else.
-read_points_ply reads the positions of a scanned cloud, read_dtu_aux the arrays the DTU evaluation keeps beside one."""
+read_points_ply reads the positions of a scanned cloud, read_dtu_aux the arrays the DTU evaluation keeps beside one.
+write_obj / read_obj: a textured mesh as a Wavefront OBJ with its material library and its PNG (vdn_hip.mesh.bake_texture's atlas)."""
+import os
+
 import numpy as np
 
 _POS = ("x", "y", "z")
@@ -170,6 +173,113 @@ def read_ply(path):
                     return {"vertices": col(_POS), "triangles": face["v"].astype(np.int32).reshape(F, 3),
                             "normals": col(_NRM) if has_n else None, "colors": col(_COL) if has_c else None}
     raise ValueError("%s: the header is not one write_ply writes" % path)
+
+
+def _obj_paths(path):
+    stem, ext = os.path.splitext(str(path))
+    if ext.lower() != ".obj":
+        raise ValueError("%s: an OBJ path ends in .obj" % path)
+    return stem + ".obj", stem + ".mtl", stem + ".png"
+
+
+def write_obj(path, vertices, triangles, uv, texture, normals=None):
+    """A textured mesh as the trio <stem>.obj, <stem>.mtl (one material, `map_Kd <stem>.png`) and <stem>.png -> the .obj path.
+    vertices [V,3] float, triangles [F,3] integer, uv [F,3,2] float (one texture coordinate per face corner, v = 0 at the bottom:
+    vdn_hip.mesh.bake_texture's "uv"), texture uint8 [S,S,3] RGB with row 0 at the top, normals [V,3] float or None. Faces are
+    written as `f v/vt` or `f v/vt/vn`, 1-based, face f using the texture coordinates 3 f + 1 .. 3 f + 3. Positions and
+    normals are stored as fp32 and printed with %.9g, the coordinates with %.17g: read_obj returns those arrays bit for bit."""
+    from PIL import Image
+    obj, mtl, png = _obj_paths(path)
+    vertices = np.asarray(vertices).reshape(-1, 3)
+    triangles = np.asarray(triangles).reshape(-1, 3)
+    uv = np.asarray(uv, dtype=np.float64)
+    texture = np.asarray(texture)
+    V, F = vertices.shape[0], triangles.shape[0]
+    if not np.issubdtype(triangles.dtype, np.integer) and F > 0:
+        raise ValueError("triangles must be integers, got %s" % triangles.dtype)
+    if F > 0 and (triangles.min() < 0 or triangles.max() >= V):
+        raise ValueError("triangle indices must lie in [0, V)")
+    if uv.shape != (F, 3, 2):
+        raise ValueError("uv must be [F,3,2] = %s, got %s" % ((F, 3, 2), uv.shape))
+    if texture.ndim != 3 or texture.shape[2] != 3 or texture.dtype != np.uint8 or texture.shape[0] < 1 or texture.shape[1] < 1:
+        raise ValueError("texture must be uint8 [H,W,3], got %s %s" % (texture.dtype, texture.shape))
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.shape != (V, 3):
+            raise ValueError("normals must be [V,3] = %s, got %s" % ((V, 3), normals.shape))
+    name = os.path.basename(png)
+    lines = ["mtllib %s" % os.path.basename(mtl)]
+    lines += ["v %.9g %.9g %.9g" % tuple(p) for p in vertices.astype(np.float32).tolist()]
+    if normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(p) for p in normals.astype(np.float32).tolist()]
+    lines += ["vt %.17g %.17g" % tuple(p) for p in uv.reshape(-1, 2).tolist()]
+    lines.append("usemtl material_0")
+    tri = (triangles.astype(np.int64) + 1).tolist()
+    if normals is None:
+        lines += ["f %d/%d %d/%d %d/%d" % (a, 3 * f + 1, b, 3 * f + 2, c, 3 * f + 3) for f, (a, b, c) in enumerate(tri)]
+    else:
+        lines += ["f %d/%d/%d %d/%d/%d %d/%d/%d" % (a, 3 * f + 1, a, b, 3 * f + 2, b, c, 3 * f + 3, c) for f, (a, b, c) in enumerate(tri)]
+    with open(obj, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    with open(mtl, "w") as f:
+        f.write("newmtl material_0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s\n" % name)
+    Image.fromarray(np.ascontiguousarray(texture)).save(png)
+    return obj
+
+
+def read_obj(path):
+    """-> dict(vertices [V,3] float32, triangles [F,3] int32, uv [T,2] float64 (the file's vt lines), uv_index [F,3] int32,
+    normals [V,3] float32 | None, normal_index [F,3] int32 | None, mtllib, texture_path (the map_Kd of the material library, beside
+    the file; None without one)) of a file of write_obj: triangles only, `f v/vt` or `f v/vt/vn`, indices 0-based on return.
+    ValueError on anything else."""
+    path = str(path)
+    v, vn, vt, fv, ft, fn, mtllib = [], [], [], [], [], [], None
+    with open(path) as f:
+        for ln in f:
+            tok = ln.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            try:
+                if tok[0] == "v" and len(tok) == 4:
+                    v.append([float(x) for x in tok[1:]])
+                elif tok[0] == "vn" and len(tok) == 4:
+                    vn.append([float(x) for x in tok[1:]])
+                elif tok[0] == "vt" and len(tok) == 3:
+                    vt.append([float(x) for x in tok[1:]])
+                elif tok[0] == "f" and len(tok) == 4:
+                    parts = [[int(x) - 1 for x in c.split("/")] for c in tok[1:]]
+                    if len({len(p) for p in parts}) != 1 or len(parts[0]) not in (2, 3):
+                        raise ValueError
+                    fv.append([p[0] for p in parts])
+                    ft.append([p[1] for p in parts])
+                    if len(parts[0]) == 3:
+                        fn.append([p[2] for p in parts])
+                elif tok[0] == "mtllib" and len(tok) == 2:
+                    mtllib = tok[1]
+                elif tok[0] in ("usemtl", "o", "g", "s"):
+                    continue
+                else:
+                    raise ValueError
+            except ValueError:
+                raise ValueError("%s: not a line write_obj writes: %r" % (path, ln.rstrip("\n")))
+    if fn and len(fn) != len(fv):
+        raise ValueError("%s: some faces carry normals and some do not" % path)
+    arr = lambda x, dt, w: np.asarray(x, dtype=dt).reshape(-1, w)
+    tri, uvi = arr(fv, np.int32, 3), arr(ft, np.int32, 3)
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(v) or uvi.min() < 0 or uvi.max() >= len(vt)):
+        raise ValueError("%s: a face refers to a vertex or a texture coordinate the file does not hold" % path)
+    texture_path = None
+    if mtllib is not None:
+        mtl = os.path.join(os.path.dirname(path), mtllib)
+        if os.path.exists(mtl):
+            with open(mtl) as f:
+                for ln in f:
+                    tok = ln.split()
+                    if len(tok) == 2 and tok[0] == "map_Kd":
+                        texture_path = os.path.join(os.path.dirname(path), tok[1])
+    return {"vertices": arr(v, np.float32, 3), "triangles": tri, "uv": arr(vt, np.float64, 2), "uv_index": uvi,
+            "normals": arr(vn, np.float32, 3) if vn else None, "normal_index": arr(fn, np.int32, 3) if fn else None,
+            "mtllib": mtllib, "texture_path": texture_path}
 
 
 def read_dtu_aux(path):

@@ -150,7 +150,7 @@ def val_img(renderer, scene, rays_gen, idx, resolution_level=1, batch_size=512, 
 
 
 def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, threshold=0.0, world_space=False, scale_mat=None,
-                  vertex_colors=True, vertex_normals=True, clean=None, sparse=None, simplify=None):
+                  vertex_colors=True, vertex_normals=True, clean=None, sparse=None, simplify=None, texture=None):
     """Runner.validate_mesh (dpt_runner.py:699-713) without trimesh: the iso-surface of the SDF network inside the box, written
     to `out_path` as a binary PLY (vdn_train/meshio.py) -> (out_path, V, F). `world_space` maps the vertices by
     v * scale_mat[0,0] + scale_mat[:3,3] (708; a uniform scale and a translation: unit normals are unchanged). Beyond the
@@ -162,8 +162,14 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     `simplify` (a dict of vdn_train.mesh_simplify.simplify_mesh's keyword arguments - cell_size or target_faces, in object-space
     units - or None: the file as it always was) thins the mesh after `clean` and before the world_space map. The vertices are then
     shaded AFTER the simplification, at their new positions (renderer.shade_vertices): normals and colours come from the networks,
-    not from averages, and the fine surface is never shaded at all - one shading pass, over the vertices that reach the file."""
+    not from averages, and the fine surface is never shaded at all - one shading pass, over the vertices that reach the file.
+    `texture` (a dict of vdn_hip.mesh.bake_texture's keyword arguments - texture_size, patch, project, ... - or None: nothing beyond
+    the PLY) bakes a per-face atlas of the mesh that reaches the file, after `clean` and `simplify`, in object space, and writes
+    <stem>.obj, <stem>.mtl and <stem>.png beside the PLY (vdn_train.meshio.write_obj), the vertices mapped as the PLY's are. The PLY
+    and the return value are what they are without it."""
     from vdn_train import meshio
+    if texture is not None and not isinstance(texture, dict):
+        raise ValueError("texture must be a dict of bake_texture's keyword arguments, got %r" % (texture,))
     normals = colors = None
     if simplify is not None:
         from vdn_train import mesh_simplify
@@ -195,6 +201,10 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
         vertices, triangles, attrs = res["vertices"], res["triangles"], list(res["attributes"])
         normals = attrs.pop(0) if normals is not None else None
         colors = attrs.pop(0) if colors is not None else None
+    baked = None
+    if texture is not None:
+        from vdn_train import mesh_texture
+        baked = mesh_texture.bake_texture(renderer, np.asarray(vertices), np.asarray(triangles), **texture)
     if world_space:
         if scale_mat is None:
             raise ValueError("world_space=True needs the scene's scale_mat (SceneData.scale_mats_np[0])")
@@ -204,15 +214,17 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     meshio.write_ply(out_path, vertices, triangles, normals=normals, colors=colors)
+    if baked is not None:
+        meshio.write_obj(os.path.splitext(out_path)[0] + ".obj", vertices, triangles, baked["uv"], baked["texture"], normals=normals)
     return out_path, int(vertices.shape[0]), int(triangles.shape[0])
 
 
-def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simplify=None, **kw):
+def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simplify=None, texture=None, **kw):
     """validate_mesh for a vdn_train.dataset.SceneData: its object bounding box and scale_mats_np[0], the runner's file name
     meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711). A `clean` dict with a true "use_masks" entry gets
     the scene's object-space cameras and its masks (cleaning happens in object space); a true "use_cameras" entry gets the cameras
     and the image size without the masks - what a "visibility" entry needs (either of the two satisfies it). `simplify` is
-    validate_mesh's, in object-space units."""
+    validate_mesh's, in object-space units, and so is `texture`: meshes/<iter_step>.obj, .mtl and .png beside the PLY."""
     if clean is not None:
         clean = dict(clean)
         use_masks, use_cameras = clean.pop("use_masks", False), clean.pop("use_cameras", False)
@@ -223,4 +235,4 @@ def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simpl
     bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
     bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
     return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
-                         scale_mat=scene.scale_mats_np[0], clean=clean, simplify=simplify, **kw)
+                         scale_mat=scene.scale_mats_np[0], clean=clean, simplify=simplify, texture=texture, **kw)
