@@ -99,6 +99,20 @@ typedef struct {
      * (vdn-nerf_amd/csrc/vdn_common.h: sincos_pe), each within 2^-18 + 2^-23 |arg| of the exact function of the exact argument
      * (absolute) - far below the bf16 rounding the encoded value then receives. The f32 entry points use the library sincosf.
      * tests/test_gpu_mlp_planes.py holds the planes to it. */
+    /* f32 entry points (here, the heads, the background network and their backward chains; tests/test_gpu_mlp_planes_f32.py holds
+     * every plane to it): every plane is row-major f32 [P, ld] in the network's own units (work list: compact rows). Encodings use
+     * the library sincosf on the float32 argument 2^k x (x = scale * p rounded once), each value within 1 ulp (2^-23 |y|).
+     * An MFMA layer (v_mfma_f32_32x32x2_f32) accumulates in ONE k-ordered chain: the bias first, then for g ascending and
+     * j = 0..3 the two products k = 8g+j and k = 8g+4+j of one instruction. How that instruction rounds its two products internally
+     * the instruction set manual does not state; this library's ASSUMPTION is a chain of fused multiply-adds, k = 8g+j before
+     * k = 8g+4+j, one rounding per product and no wider accumulator - the tests take their float32 floor from that chain
+     * (oracle/mlp_ops.py: mfma_chain_f32) and three times the floor absorbs the other readings.
+     * H[l] = softplus(100 a_l) / 100 and S[l] = sigmoid(100 a_l), a_l = W_l H[l-1] + b_l, both from one exponential:
+     * t = 100 log2(e) a, e = 2^-|t|, u = 1 + e, H = log2(u) ln 2 / 100 + max(a, 0), r = 1 / u, S = a >= 0 ? r : e r (v_exp_f32,
+     * v_log_f32, v_rcp_f32: 1 ulp each). A pre-activation of exactly 0 gives S = 1/2 and H = float32(ln 2 / 100) exactly. The
+     * hardware exponential may flush a result below 2^-126 to zero: an S below 2^-125 is held to 2^-126 absolute.
+     * Layer 3 has 217 outputs: columns 217..223 of H[3] / S[3] / V[3] hold softplus(0), 1/2 and 0 (zero weights, zero bias) and
+     * columns 224..255 are never written; neither is promised. */
     /* optional work list (vdn_foreground_active; same contract as VdnNerfArgs.active_idx): per-point inputs / outputs
      * are addressed by the dense point id, training saves and deltas by the compact row */
     const int32_t* active_idx;
@@ -487,7 +501,9 @@ typedef struct {
     void* UB;                 /* out, see above */
     void* EX;                 /* out */
     int32_t s_from_h;          /* 1: S points at the H planes; softplus' = 1 - exp(-100 h) is evaluated in the kernel.
-                               * 2: H and V are in units of 1/(100 log2 e) (bf16 forward): softplus' = 1 - 2^-H */
+                               * 2: H and V are in units of 1/(100 log2 e) (bf16 forward): softplus' = 1 - 2^-H
+                               * 0 and 1 are held by tests/test_gpu_mlp_planes_f32.py (no caller passes 1 today), 2 by
+                               * tests/test_gpu_mlp_planes.py; acc_pts = 1 of VdnSdfFbarArgs by both. */
     /* optional work list (vdn_foreground_active; same contract as VdnNerfArgs.active_idx): per-point inputs / outputs
      * are addressed by the dense point id, training saves and deltas by the compact row */
     const int32_t* active_idx;

@@ -11,7 +11,8 @@ of softplus (0.02 < sigma < 0.98). "hot" = the same state with weight_g of the h
 layer on the CPU (float64 model, 300 points) so that every layer reaches the kernel's range switches (DESIGN.md 3a, round 3:
 g = t from t >= 25, w = +inf from t = 128): at least 4 % of each layer's units in each of t >= 128, t <= -128, 25 <= t < 128 and
 |t| < 5, with max H < 2^10 (one factor for all layers does not do it: activations compound and the knee empties). "other" (seed
-4) is the state of the wiring check."""
+4) is the state of the wiring check. The fp32 plane tests (tests/test_gpu_mlp_planes_f32.py) run the same cases and add only
+SDF_F32_CASES (a pre-activation that is exactly 0) and sdf_d_pts_prefill (what d_pts holds before an acc_pts = 1 launch)."""
 import numpy as np
 
 from vdn_train import synth
@@ -32,8 +33,19 @@ SDF_CASES = {
 }
 
 
+# The fp32 plane tests (tests/test_gpu_mlp_planes_f32.py) run SDF_CASES as they are and this one more: state "silent" = "init" with
+# unit 7 of lin2 silenced (weight_g = bias = 0), so that its pre-activation is exactly 0: H = ln 2 / 100 and S = 1/2 exactly - the
+# boundary of the fp32 kernel's a >= 0 ? r : e r.
+SDF_F32_CASES = {"silent-P33-s1": (33, 1.0, "uniform", None, "silent")}
+SDF_SILENT = (2, 7)                                    # (layer, unit)
+
+
 def states(state="init"):
     st = synth.make_all_states(OTHER_SEED if state == "other" else SEED, wdepth=True, variance=0.3)
+    if state == "silent":
+        sd = st["sdf_network_fine"]
+        sd["lin%d.weight_g" % SDF_SILENT[0]][SDF_SILENT[1]] = 0.0
+        sd["lin%d.bias" % SDF_SILENT[0]][SDF_SILENT[1]] = 0.0
     if state == "hot":
         sd = st["sdf_network_fine"]
         for l, f in enumerate(HOT_FACTORS):
@@ -42,7 +54,7 @@ def states(state="init"):
 
 
 def sdf_case(name):
-    P, scale, kind, n_active, state = SDF_CASES[name]
+    P, scale, kind, n_active, state = SDF_CASES[name] if name in SDF_CASES else SDF_F32_CASES[name]
     if kind == "uniform":
         pts = (2.2 * synth.uniform(SEED, "mlp/%s/pts" % name, (P, 3)) - 1.1).astype(np.float32)
     else:
@@ -279,6 +291,11 @@ def nerf_upstream(c):
 # Upstream gradients of an SDF case: random, and each chain alone (g_feat = 0 with g_sdf = 0 leaves only the sweep's adjoint and its
 # second-order term; g_normals = 0 leaves only the forward's adjoint: ub and EX exactly zero).
 SDF_UPSTREAM = ("random", "g_feat=0", "g_normals=0")
+
+
+def sdf_d_pts_prefill(c):
+    """What d_pts [P,3] holds before a vdn_sdf_bwd_fbar_* launch with acc_pts = 1: ~ N(0, 1), finite, dense point order."""
+    return synth.normal(SEED, "mlp/%s/d_pts_before" % c["name"], (c["P"], 3)).astype(np.float32)
 
 
 def sdf_upstream(c, kind="random"):

@@ -40,6 +40,9 @@ Where an operand is not bit for bit a plane the test can read - the plane contra
 | ex_l in the split launch | it stays in its wave                                            | none: the launch gives UB and AB bit for bit as rbar then fbar, so EX is read from the two-launch run | include/vdn_render.h, vdn_sdf_bwd_split_bf16 |
 | adjoints of the encoded inputs (d_dirs of the heads, d_pts4 / d_dirs of the background network, d_pts of fbar) | no plane holds them: the output is modelled in one piece from the last saved delta / ab blocks | what the accumulated adjoints may carry (2 kt roundings each, at three times the floor) through |J| <= 2^k, and the hardware trig | include/vdn_render.h VdnRenderNetBwdArgs.d_dirs, VdnNerfInputGradArgs, VdnSdfFbarArgs.d_pts |
 | H[3], V[3]               | 217 outputs: columns 217..255 of the plane are not promised     | not read                            | include/vdn_render.h, VdnSdfArgs.H; images.py sdf_streams (nmap of lin3) |
+| fp32 entry points: the normals, ub_0, d_pts, d_dirs, d_pts4 (a sine or cosine behind a sum) | the library sincosf, 1 ulp of a value <= 1, on a float32 argument that is one rounding of scale p (LIB_TRIG) | sum_k 2^k (2^-23 + 2^-24 |arg|) (|u_sin| + |u_cos|), times the factors in front of the sum | include/vdn_render.h, VdnSdfArgs (f32 entry points) |
+| fp32 entry point: S[l]   | the hardware exponential may flush a result below 2^-126 to zero | 2^-126 where S < 2^-125             | include/vdn_render.h, VdnSdfArgs (f32 entry points) |
+| fp32 entry points: every MFMA layer | nothing: the operands are the f32 planes themselves; the float32 floor is the k-ordered chain mfma_chain_f32 | none (the assumption on the instruction's two products is absorbed by the factor 3) | include/vdn_render.h, VdnSdfArgs (f32 entry points) |
 
 The heads' forward (colour head, VDN head: small_inputs, dense_relu, dense_out) and the background network's (plain_encoding,
 nerf_plane_models) are in network units, and every operand there IS a plane the test reads: their only extra terms are the
@@ -52,6 +55,9 @@ So does the background network's backward (vdn_nerf_mlp_bwd_bf16: nerf_bwd_plane
 and its input adjoints (vdn_nerf_mlp_bwd_input_bf16: nerf_input_adjoint_models), and the SDF backward (vdn_sdf_bwd_rbar_bf16 /
 vdn_sdf_bwd_fbar_bf16: pe_jacobian, sdf_rbar_step, sdf_fbar_step, sdf_d_pts_model - the closed forms of DESIGN.md section 4, which
 tests/test_mlp_ops_model_cpu.py holds against torch autograd of the oracle, a double backward).
+The fp32 launches (vdn_*_f32; tests/test_gpu_mlp_planes_f32.py, tests/test_mlp_f32_model_cpu.py) are held by the same models in their
+fp32 forms - operand_weights(fmt=0), f32=True / chain=True, s_mode 0 / 1, sdf_plane_models_f32, sdf_bwd_models_f32 at the end of
+this file -: network units, row-major f32 planes, stored="f32", the last three rows of the table.
 """
 import math
 
@@ -61,8 +67,11 @@ import torch
 C = 100.0 * math.log2(math.e)
 U24, U23 = 2.0 ** -24, 2.0 ** -23
 LN2 = math.log(2.0)
+F32_QUANTUM = 2.0 ** -149               # the spacing of the float32 subnormals
 D0, N_RES = 39, 25                      # encoded inputs; residue slots behind them
 TRIG_ABS, TRIG_ARG = 2.0 ** -18, 2.0 ** -23
+HW_TRIG = (TRIG_ABS, TRIG_ARG)          # hardware sine / cosine (bf16 entry points): absolute error, and per unit of |arg|
+LIB_TRIG = (U23, U24)                   # library sincosf (f32 entry points): 1 ulp of a value <= 1; the float32 argument is one rounding of scale p
 
 
 # ---- bf16 as a set of float64 values ----------------------------------------------------------------------------------------
@@ -132,11 +141,12 @@ class HostImages:
         return cls(weff, bias, streams)
 
 
-def operand_weights(img, stream, layer, rounded=True):
+def operand_weights(img, stream, layer, rounded=True, fmt=1):
     """Layer `layer` of `stream` as its chunks hold it (include/vdn_render.h VdnChunkDesc, csrc/prep.hip):
     W [n_pad, k_pad] = bf16_rne(float32(scale) * W_eff[nmap, kmap]) (0 where a map entry is -1), b [n_pad] =
     float32(bias_scale * bias[nmap]), tail = the float32 constants that ride behind the bias block (or None); float64 arrays.
-    rounded=False: the same image without any rounding (img holding float64 weights): the exact network, for the chain test."""
+    rounded=False: the same image without any rounding (img holding float64 weights): the exact network, for the chain test.
+    fmt=0: the image as an fp32 chunk holds it - W = float32(float32(scale) * W_eff[nmap, kmap]), no bf16 rounding."""
     if not isinstance(img, HostImages):
         img = HostImages.of(img)
     L = img.streams[stream][layer]
@@ -161,7 +171,7 @@ def operand_weights(img, stream, layer, rounded=True):
     if L.tail is not None:
         first, stride = (L.tail[3], L.tail[4]) if len(L.tail) > 3 else (0, 1)
         tail = img.weff[L.tail[0]].astype(ft).reshape(-1)[first::stride][:L.tail[2]].astype(np.float64)
-    return {"W": bf16_rne(W) if rounded else W.astype(np.float64), "b": np.concatenate(bs).astype(np.float64), "tail": tail,
+    return {"W": bf16_rne(W) if rounded and fmt == 1 else W.astype(np.float64), "b": np.concatenate(bs).astype(np.float64), "tail": tail,
             "kt": L.kt, "n_chunks": len(L.chunks)}
 
 
@@ -171,7 +181,7 @@ def _t(a, dtype):
     return torch.as_tensor(np.asarray(a, np.float64)).to(dtype)
 
 
-def posenc_scaled(pts, scale, dtype=torch.float64):
+def posenc_scaled(pts, scale, dtype=torch.float64, unit_c=C):
     """x = C PE(scale p) [P,39] (embedder order: p, then sin, cos per octave), with `arg` (the argument of each column) and
     `deriv` (|d column / d arg|), float64 numpy, for posenc_units."""
     p = _t(pts, dtype) * torch.tensor(float(scale), dtype=dtype)
@@ -182,7 +192,7 @@ def posenc_scaled(pts, scale, dtype=torch.float64):
         args += [a, a]
         der += [torch.cos(a).abs(), torch.sin(a).abs()]
     f = lambda ts: torch.cat(ts, -1).double().numpy()
-    x = (torch.cat(cols, -1) * torch.tensor(C, dtype=dtype)).double().numpy()
+    x = (torch.cat(cols, -1) * torch.tensor(unit_c, dtype=dtype)).double().numpy()      # (unit_c = 1: the f32 entry point, network units)
     return {"y": x, "arg": f(args), "deriv": f(der)}
 
 
@@ -310,21 +320,21 @@ def sweep_units(m, u, mag):
     return unit, extra
 
 
-def pe_jacobian_T(pts, scale, U, dtype=torch.float64, n_freqs=6):
+def pe_jacobian_T(pts, scale, U, dtype=torch.float64, n_freqs=6, trig=HW_TRIG):
     """n = scale J_PE(scale p)^T U [P,3] (fields.py:97-108 through the encoding), with mag = scale sum |terms| and the extra
     term of the hardware sine / cosine."""
     p = _t(pts, dtype) * torch.tensor(float(scale), dtype=dtype)
     Ut = _t(U, dtype)
-    n, mag, trig = Ut[:, :3].clone(), Ut[:, :3].abs().double(), torch.zeros(len(p), 3, dtype=torch.float64)
+    n, mag, terr = Ut[:, :3].clone(), Ut[:, :3].abs().double(), torch.zeros(len(p), 3, dtype=torch.float64)
     for k in range(n_freqs):
         f = float(2 ** k)
         us, uc = Ut[:, 3 + 6 * k:6 + 6 * k], Ut[:, 6 + 6 * k:9 + 6 * k]
         a = p * f
         n = n + f * (torch.cos(a) * us - torch.sin(a) * uc)
         mag = mag + f * ((torch.cos(a) * us).abs() + (torch.sin(a) * uc).abs()).double()
-        trig = trig + f * (TRIG_ABS + TRIG_ARG * a.abs().double()) * (us.abs() + uc.abs()).double()
+        terr = terr + f * (trig[0] + trig[1] * a.abs().double()) * (us.abs() + uc.abs()).double()
     sc = float(scale)
-    return {"y": (n * torch.tensor(sc, dtype=dtype)).double().numpy(), "mag": mag.numpy() * sc, "extra": trig.numpy() * sc}
+    return {"y": (n * torch.tensor(sc, dtype=dtype)).double().numpy(), "mag": mag.numpy() * sc, "extra": terr.numpy() * sc}
 
 
 def sdf_sweep_models(ops_sweep, w8row, pts, scale, planes):
@@ -368,7 +378,7 @@ def _padded(a, n):
     return np.concatenate([a, np.zeros((len(a), n - a.shape[1]))], -1)
 
 
-def small_inputs(pts, dirs, normals, dtype=torch.float64):
+def small_inputs(pts, dirs, normals, dtype=torch.float64, hw_trig=True):
     """-> y [P,33] and its unit / extra term: the points and the normals are copied (no arithmetic: a bf16 rounding of the f32
     input itself), the encoded view direction is one sine or cosine of the exact product 2^k d (the hardware ones: the header's
     contract at VdnSdfArgs.PE)."""
@@ -384,13 +394,46 @@ def small_inputs(pts, dirs, normals, dtype=torch.float64):
     trig[:, 6:30] = 1.0
     arg = np.zeros_like(y)
     arg[:, 6:30] = torch.cat(args[2:], -1).abs().double().numpy()
-    return {"y": y, "unit": U23 * np.abs(y) * trig, "extra": (TRIG_ABS + TRIG_ARG * arg) * trig}
+    return {"y": y, "unit": U23 * np.abs(y) * trig, "extra": (TRIG_ABS + TRIG_ARG * arg) * trig * float(hw_trig)}
 
 
-def dense_relu(x, W, b, dtype=torch.float64):
+def mfma_k_order(k_pad):
+    """The k order of an fp32 MFMA layer (csrc/mlp_engine.h, F32::mma): for g ascending and j = 0..3 the two products k = 8 g + j and
+    k = 8 g + 4 + j of one v_mfma_f32_32x32x2_f32."""
+    g, j, h = np.arange(k_pad // 8)[:, None, None], np.arange(4)[None, :, None], np.arange(2)[None, None, :]
+    return (8 * g + j + 4 * h).reshape(-1)
+
+
+def mfma_chain_f32(x, W, b=None):
+    """The float32 floor of an fp32 MFMA layer, as oracle/dw_ops.py fma_chain_f32 is of the GEMMs: x [P,K] and W [N,K] (float32
+    values), acc = bias, then acc = float32(acc + w_k x_k) for k in mfma_k_order - one rounding per product, the two products of one
+    instruction one after the other (include/vdn_render.h states this reading as the library's assumption) -> [P,N] as float64."""
+    xT = np.ascontiguousarray(np.asarray(x, np.float32).astype(np.float64).T)       # [K, P]: the product of two float32 is exact in float64
+    WT = np.ascontiguousarray(np.asarray(W, np.float32).astype(np.float64).T)       # [K, N]
+    acc32 = np.zeros((xT.shape[1], WT.shape[1]), np.float32)
+    if b is not None:
+        acc32[:] = np.asarray(b, np.float32)[None, :]
+    acc64, tmp = acc32.astype(np.float64), np.empty(acc32.shape, np.float64)
+    for k in mfma_k_order(WT.shape[0]):
+        if WT[k].any():                                  # (a zero column adds nothing to any accumulator)
+            np.multiply(xT[k][:, None], WT[k][None, :], out=tmp)
+            tmp += acc64
+            acc32[...] = tmp                             # the one rounding of this product's accumulation
+            acc64[...] = acc32
+    return acc64
+
+
+def _mm(X, Wt, bt, dtype, chain):
+    """X W^T (+ b) in `dtype`; chain: the float32 evaluation is the k-ordered chain of an fp32 MFMA layer."""
+    if chain and dtype == torch.float32:
+        return _t(mfma_chain_f32(X.double().numpy(), Wt.double().numpy(), None if bt is None else bt.double().numpy()), dtype)
+    return X @ Wt.T if bt is None else X @ Wt.T + bt
+
+
+def dense_relu(x, W, b, dtype=torch.float64, chain=False):
     """relu(W x + b) from the saved input plane(s) x [P, k_pad] -> y, mag = sum |w x| + |b|."""
     X, Wt, bt = _t(x, dtype), _t(W, dtype), _t(b, dtype)
-    t = X @ Wt.T + bt
+    t = _mm(X, Wt, bt, dtype, chain)
     return {"y": torch.relu(t).double().numpy(), "t": t.double().numpy(),
             "mag": (X.abs().double() @ Wt.abs().double().T + bt.abs().double()).numpy()}
 
@@ -401,16 +444,17 @@ def accum_extra(mag, kt):
     return (2 * kt - 1) * U24 * mag
 
 
-def dense_out(x, W, b, squeeze, d_out, dtype=torch.float64):
+def dense_out(x, W, b, squeeze, d_out, dtype=torch.float64, chain=False):
     """The output layer: sigmoid (squeeze_out, fields.py:170-171) or relu of W x + b, columns 0..d_out-1, with its unit:
     the accumulation through |f'| = s (1 - s), and the exponential and the reciprocal of the sigmoid (2^-23 |y| each)."""
-    m = dense_relu(x, W, b, dtype)
-    kt = np.shape(W)[1] // 32
+    m = dense_relu(x, W, b, dtype, chain)
+    # (chain: an fp32 MFMA layer, whose floor is its own chain - no extra term)
+    extra = (lambda mag: 0.0 * mag) if chain else (lambda mag: accum_extra(mag, np.shape(W)[1] // 32))
     if not squeeze:
-        return {"y": m["y"][:, :d_out], "unit": U24 * m["mag"][:, :d_out], "extra": accum_extra(m["mag"][:, :d_out], kt)}
+        return {"y": m["y"][:, :d_out], "unit": U24 * m["mag"][:, :d_out], "extra": extra(m["mag"][:, :d_out])}
     s = torch.sigmoid(_t(m["t"], torch.float64) if dtype == torch.float64 else _t(m["t"], dtype)).double().numpy()[:, :d_out]
     slope = m["mag"][:, :d_out] * s * (1.0 - s)
-    return {"y": s, "unit": U24 * slope + 2.0 * U23 * s, "extra": accum_extra(slope, kt)}
+    return {"y": s, "unit": U24 * slope + 2.0 * U23 * s, "extra": extra(slope)}
 
 
 def head_layer0_input(feat_plane, small, extra=None):
@@ -420,36 +464,39 @@ def head_layer0_input(feat_plane, small, extra=None):
     return np.concatenate(x, -1)
 
 
-def head_plane_models(ops, pts, dirs, normals, feat_plane, planes, squeeze, d_out, extra=None):
+def head_plane_models(ops, pts, dirs, normals, feat_plane, planes, squeeze, d_out, extra=None, f32=False):
     """{plane: dict(y64, y32, unit, extra, stored)} of one vdn_rendernet_fwd_bf16 launch: small from the inputs, h0 from the
     feature plane it was given and the small plane it saved, h1..h3 and out from the plane before. ops: layers 0..4 of 'fwd'.
     extra [P,96] (d_feature = 352): the f32 input whose bf16 copy is the plane save_extra, read by layer 0 behind small."""
+    # f32: vdn_rendernet_fwd_f32 - row-major f32 planes (copies are exact), the library sincosf, every float32 evaluation of a layer
+    # the k-ordered chain of mfma_chain_f32, on the fmt-0 operand weights
     out = {}
+    st = "f32" if f32 else "bf16"
     if extra is not None:
         e = np.asarray(extra, np.float64)
-        out["extra"] = dict(y64=e, y32=e, unit=np.zeros_like(e), extra=0.0, stored="bf16")
-    s64, s32 = (small_inputs(pts, dirs, normals, dt) for dt in (torch.float64, torch.float32))
-    out["small"] = dict(y64=s64["y"], y32=s32["y"], unit=s64["unit"], extra=s64["extra"], stored="bf16")
+        out["extra"] = dict(y64=e, y32=e, unit=np.zeros_like(e), extra=0.0, stored=st)
+    s64, s32 = (small_inputs(pts, dirs, normals, dt, hw_trig=not f32) for dt in (torch.float64, torch.float32))
+    out["small"] = dict(y64=s64["y"], y32=s32["y"], unit=s64["unit"], extra=s64["extra"], stored=st)
     x = head_layer0_input(feat_plane, planes["small"], planes["extra"] if extra is not None else None)
     for l in range(4):
-        m64, m32 = (dense_relu(x, ops[l]["W"], ops[l]["b"], dt) for dt in (torch.float64, torch.float32))
-        out["h%d" % l] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored="bf16")
+        m64, m32 = (dense_relu(x, ops[l]["W"], ops[l]["b"], dt, f32) for dt in (torch.float64, torch.float32))
+        out["h%d" % l] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored=st)
         x = planes["h%d" % l]
-    o64, o32 = (dense_out(x, ops[4]["W"], ops[4]["b"], squeeze, d_out, dt) for dt in (torch.float64, torch.float32))
+    o64, o32 = (dense_out(x, ops[4]["W"], ops[4]["b"], squeeze, d_out, dt, f32) for dt in (torch.float64, torch.float32))
     out["out"] = dict(y64=o64["y"], y32=o32["y"], unit=o64["unit"], extra=o64["extra"], stored="f32")
     return out
 
 
-def simulate_head_forward(ops, pts, dirs, normals, feat_plane, squeeze, d_out, rnd=bf16_rne, extra=None):
+def simulate_head_forward(ops, pts, dirs, normals, feat_plane, squeeze, d_out, rnd=bf16_rne, extra=None, chain=False):
     """The CPU stand-in of the launch (float32 chain through its own bf16 planes), for the comparator's own test."""
     planes = {"small": rnd(small_inputs(pts, dirs, normals, torch.float32)["y"])}
     if extra is not None:
         planes["extra"] = rnd(extra)
     x = head_layer0_input(feat_plane, planes["small"], planes.get("extra"))
     for l in range(4):
-        planes["h%d" % l] = rnd(dense_relu(x, ops[l]["W"], ops[l]["b"], torch.float32)["y"])
+        planes["h%d" % l] = rnd(dense_relu(x, ops[l]["W"], ops[l]["b"], torch.float32, chain)["y"])
         x = planes["h%d" % l]
-    planes["out"] = dense_out(x, ops[4]["W"], ops[4]["b"], squeeze, d_out, torch.float32)["y"]
+    planes["out"] = dense_out(x, ops[4]["W"], ops[4]["b"], squeeze, d_out, torch.float32, chain)["y"]
     return planes
 
 
@@ -540,7 +587,7 @@ def view_down_the_normal(normals_f32):
 # 4); feature = W_f h_7 + b_f (a bf16 plane, no activation), density = w_a . h_7 + b_a; hv = relu(W_v [feature | vpe] + b_v);
 # rgb = W_r hv + b_r, feat = W_d hv + b_d (f32, no activation). save_mask / save_mask_v = (save_h > 0) / (save_hv > 0), exactly.
 
-def plain_encoding(x, n_freqs, dtype=torch.float64):
+def plain_encoding(x, n_freqs, dtype=torch.float64, hw_trig=True):
     """[x, sin(2^0 x), cos(2^0 x), ...] with its unit and extra term: x is copied (a bf16 rounding of the f32 input itself), each
     other column is one hardware sine or cosine of the exact product 2^k x (the header's contract at VdnSdfArgs.PE)."""
     xt = _t(x, dtype)
@@ -554,7 +601,7 @@ def plain_encoding(x, n_freqs, dtype=torch.float64):
     trig, arg = np.zeros_like(y), np.zeros_like(y)
     trig[:, d:] = 1.0
     arg[:, d:] = torch.cat(args, -1).abs().double().numpy()
-    return {"y": y, "unit": U23 * np.abs(y) * trig, "extra": (TRIG_ABS + TRIG_ARG * arg) * trig}
+    return {"y": y, "unit": U23 * np.abs(y) * trig, "extra": (TRIG_ABS + TRIG_ARG * arg) * trig * float(hw_trig)}
 
 
 def nerf_inputs_of(planes):
@@ -569,34 +616,37 @@ def nerf_inputs_of(planes):
     return x
 
 
-def _linear(x, W, b, dtype):
+def _linear(x, W, b, dtype, chain=False):
     X, Wt, bt = _t(x, dtype), _t(W, dtype), _t(b, dtype)
-    return (X @ Wt.T + bt).double().numpy(), (X.abs().double() @ Wt.abs().double().T + bt.abs().double()).numpy()
+    return _mm(X, Wt, bt, dtype, chain).double().numpy(), (X.abs().double() @ Wt.abs().double().T + bt.abs().double()).numpy()
 
 
-def nerf_plane_models(ops, pts4, dirs, planes):
+def nerf_plane_models(ops, pts4, dirs, planes, f32=False):
     """{plane: dict(y64, y32, unit, extra, stored)} of one launch, each from the saved planes before it. ops: layers 0..10 of
     'fwd' (8 = feature_linear + alpha_linear, 9 = views_linears.0, 10 = rgb_linear + dpt_linear)."""
+    # f32: vdn_nerf_mlp_fwd_f32, as head_plane_models
     out = {}
+    st = "f32" if f32 else "bf16"
     for name, src, nf in (("pe", pts4, 10), ("vpe", dirs, 4)):
-        e64, e32 = plain_encoding(src, nf, torch.float64), plain_encoding(src, nf, torch.float32)
-        out[name] = dict(y64=e64["y"], y32=e32["y"], unit=e64["unit"], extra=e64["extra"], stored="bf16")
+        e64, e32 = plain_encoding(src, nf, torch.float64, not f32), plain_encoding(src, nf, torch.float32, not f32)
+        out[name] = dict(y64=e64["y"], y32=e32["y"], unit=e64["unit"], extra=e64["extra"], stored=st)
     x = nerf_inputs_of(planes)
     for i, name in [(i, "h%d" % i) for i in range(8)] + [(9, "hv")]:
-        m64, m32 = (dense_relu(x[i], ops[i]["W"], ops[i]["b"], dt) for dt in (torch.float64, torch.float32))
-        out[name] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored="bf16")
-    (y64, mag), (y32, _) = (_linear(x[8], ops[8]["W"], ops[8]["b"], dt) for dt in (torch.float64, torch.float32))
-    out["feature"] = dict(y64=y64[:, :256], y32=y32[:, :256], unit=U24 * mag[:, :256], extra=0.0, stored="bf16")
-    out["density"] = dict(y64=y64[:, 256], y32=y32[:, 256], unit=U24 * mag[:, 256], extra=accum_extra(mag[:, 256], ops[8]["kt"]), stored="f32")
-    (y64, mag), (y32, _) = (_linear(x[10], ops[10]["W"], ops[10]["b"], dt) for dt in (torch.float64, torch.float32))
-    ex = accum_extra(mag, ops[10]["kt"])
+        m64, m32 = (dense_relu(x[i], ops[i]["W"], ops[i]["b"], dt, f32) for dt in (torch.float64, torch.float32))
+        out[name] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored=st)
+    (y64, mag), (y32, _) = (_linear(x[8], ops[8]["W"], ops[8]["b"], dt, f32) for dt in (torch.float64, torch.float32))
+    out["feature"] = dict(y64=y64[:, :256], y32=y32[:, :256], unit=U24 * mag[:, :256], extra=0.0, stored=st)
+    out["density"] = dict(y64=y64[:, 256], y32=y32[:, 256], unit=U24 * mag[:, 256],
+                          extra=0.0 if f32 else accum_extra(mag[:, 256], ops[8]["kt"]), stored="f32")
+    (y64, mag), (y32, _) = (_linear(x[10], ops[10]["W"], ops[10]["b"], dt, f32) for dt in (torch.float64, torch.float32))
+    ex = np.zeros_like(mag) if f32 else accum_extra(mag, ops[10]["kt"])
     out["rgb"] = dict(y64=y64[:, :3], y32=y32[:, :3], unit=U24 * mag[:, :3], extra=ex[:, :3], stored="f32")
     if y64.shape[1] > 32:                                # (with the dpt head: three more chunks)
         out["feat"] = dict(y64=y64[:, 32:128], y32=y32[:, 32:128], unit=U24 * mag[:, 32:128], extra=ex[:, 32:128], stored="f32")
     return out
 
 
-def simulate_nerf_forward(ops, pts4, dirs, rnd=bf16_rne, dtype=torch.float32):
+def simulate_nerf_forward(ops, pts4, dirs, rnd=bf16_rne, dtype=torch.float32, chain=False):
     """The CPU stand-in of the launch (float32 chain through its own bf16 planes), for the comparator's own test. With
     dtype = float64 and rnd = identity it is the exact chain (the chain tests)."""
     f32 = dtype
@@ -604,12 +654,12 @@ def simulate_nerf_forward(ops, pts4, dirs, rnd=bf16_rne, dtype=torch.float32):
     for i in range(8):
         x = nerf_inputs_of({**{"h%d" % j: np.zeros((len(pts4), 256)) for j in range(8)}, "feature": np.zeros((len(pts4), 256)),
                             "hv": None, **planes})[i]
-        planes["h%d" % i] = rnd(dense_relu(x, ops[i]["W"], ops[i]["b"], f32)["y"])
-    y, _ = _linear(planes["h7"], ops[8]["W"], ops[8]["b"], f32)
+        planes["h%d" % i] = rnd(dense_relu(x, ops[i]["W"], ops[i]["b"], f32, chain)["y"])
+    y, _ = _linear(planes["h7"], ops[8]["W"], ops[8]["b"], f32, chain)
     planes["feature"], planes["density"] = rnd(y[:, :256]), y[:, 256]
     x9 = np.concatenate([planes["feature"], _padded(planes["vpe"], 32)], -1)
-    planes["hv"] = rnd(dense_relu(x9, ops[9]["W"], ops[9]["b"], f32)["y"])
-    y, _ = _linear(planes["hv"], ops[10]["W"], ops[10]["b"], f32)
+    planes["hv"] = rnd(dense_relu(x9, ops[9]["W"], ops[9]["b"], f32, chain)["y"])
+    y, _ = _linear(planes["hv"], ops[10]["W"], ops[10]["b"], f32, chain)
     planes["rgb"] = y[:, :3]
     if y.shape[1] > 32:
         planes["feat"] = y[:, 32:128]
@@ -621,12 +671,12 @@ def simulate_nerf_forward(ops, pts4, dirs, rnd=bf16_rne, dtype=torch.float32):
 # delta_h[l] = (W_{l+1}^T delta_h[l+1]) . [h_l > 0]; W_0^T delta_h[0] in the first layer's padded input order = [d_feat (256) |
 # d_pts (3), d PE4(view) (27), d_normals (3) | (d_extra (96))]. 'bwd' stream: W_4^T, W_3^T, W_2^T, W_1^T, W_0^T.
 
-def relu_chain_step(delta_next, Wt, mask, dtype=torch.float64):
+def relu_chain_step(delta_next, Wt, mask, dtype=torch.float64, chain=False):
     """(W^T delta_next) . mask from the saved delta plane -> y, mag (zero where the mask is: nothing but an exact 0 passes there)."""
     d, W = _t(delta_next, dtype), _t(Wt, dtype)
     d = d[:, :W.shape[1]] if d.shape[1] >= W.shape[1] else torch.cat([d, torch.zeros(len(d), W.shape[1] - d.shape[1], dtype=dtype)], -1)
     m = _t(np.asarray(mask, np.float64), dtype)
-    return {"y": ((d @ W.T) * m).double().numpy(), "mag": ((d.abs().double() @ W.abs().double().T) * m.double()).numpy()}
+    return {"y": (_mm(d, W, None, dtype, chain) * m).double().numpy(), "mag": ((d.abs().double() @ W.abs().double().T) * m.double()).numpy()}
 
 
 def head_delta_out(g_out, out, squeeze, dtype=torch.float64):
@@ -639,23 +689,24 @@ def head_delta_out(g_out, out, squeeze, dtype=torch.float64):
     return {"y": y.double().numpy(), "unit": U24 * (g.abs() * (o + 2.0 * o * (1.0 - o))).double().numpy()}
 
 
-def head_bwd_plane_models(ops_bwd, g_out, out, h_planes, planes, squeeze, d_out, with_pts=True, d_extra_before=None):
+def head_bwd_plane_models(ops_bwd, g_out, out, h_planes, planes, squeeze, d_out, with_pts=True, d_extra_before=None, f32=False):
     """{plane: dict(y64, y32, unit, extra, stored)} of one vdn_rendernet_bwd_bf16 launch: delta_out from g_out and the forward's
     out, every delta_h from the delta plane after it and the forward's saved h (its mask), d_feat / d_normals / d_pts from the
     saved delta_h[0] (f32 outputs of an MFMA layer: the accumulation term). h_planes: the forward's save_h [4][P,256]."""
     res = {}
+    st = "f32" if f32 else "bf16"                        # (f32: vdn_rendernet_bwd_f32, as head_plane_models)
     d64, d32 = (head_delta_out(g_out, out, squeeze, dt) for dt in (torch.float64, torch.float32))
-    res["delta_out"] = dict(y64=d64["y"], y32=d32["y"], unit=d64["unit"], extra=0.0, stored="bf16")
+    res["delta_out"] = dict(y64=d64["y"], y32=d32["y"], unit=d64["unit"], extra=0.0, stored=st)
     nxt = planes["delta_out"]
     for l in (3, 2, 1, 0):
         mask = h_planes[l] > 0
-        m64, m32 = (relu_chain_step(nxt, ops_bwd[3 - l]["W"], mask, dt) for dt in (torch.float64, torch.float32))
-        res["delta_h%d" % l] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored="bf16")
+        m64, m32 = (relu_chain_step(nxt, ops_bwd[3 - l]["W"], mask, dt, f32) for dt in (torch.float64, torch.float32))
+        res["delta_h%d" % l] = dict(y64=m64["y"], y32=m32["y"], unit=U24 * m64["mag"], extra=0.0, stored=st)
         nxt = planes["delta_h%d" % l]
     ones = np.ones((len(nxt), ops_bwd[4]["W"].shape[0]))
-    m64, m32 = (relu_chain_step(nxt, ops_bwd[4]["W"], ones, dt) for dt in (torch.float64, torch.float32))
-    ex = accum_extra(m64["mag"], ops_bwd[4]["kt"])
-    res["d_feat"] = dict(y64=m64["y"][:, :256], y32=m32["y"][:, :256], unit=U24 * m64["mag"][:, :256], extra=0.0, stored="bf16")
+    m64, m32 = (relu_chain_step(nxt, ops_bwd[4]["W"], ones, dt, f32) for dt in (torch.float64, torch.float32))
+    ex = np.zeros_like(m64["mag"]) if f32 else accum_extra(m64["mag"], ops_bwd[4]["kt"])
+    res["d_feat"] = dict(y64=m64["y"][:, :256], y32=m32["y"][:, :256], unit=U24 * m64["mag"][:, :256], extra=0.0, stored=st)
     for name, lo in (("d_normals", 286),) + ((("d_pts", 256),) if with_pts else ()):
         res[name] = dict(y64=m64["y"][:, lo:lo + 3], y32=m32["y"][:, lo:lo + 3], unit=U24 * m64["mag"][:, lo:lo + 3],
                          extra=ex[:, lo:lo + 3], stored="f32")
@@ -666,29 +717,30 @@ def head_bwd_plane_models(ops_bwd, g_out, out, h_planes, planes, squeeze, d_out,
     return res
 
 
-def head_d_dirs_model(ops_bwd, delta_h0, dirs):
+def head_d_dirs_model(ops_bwd, delta_h0, dirs, f32=False):
     """d_dirs = J_PE4(view)^T (W_0^T delta_h[0])[259:286] [P,3]: the 27 adjoints of the encoded view are no plane, so this output
     is modelled from delta_h[0] in one piece. Unit: the Jacobian's sum; extra: the hardware sine / cosine and what the 27
     accumulated adjoints may carry (2 kt roundings each, at three times the floor), through |J| <= 2^k."""
     ones = np.ones((len(delta_h0), ops_bwd[4]["W"].shape[0]))
     r = {}
     for dt in (torch.float64, torch.float32):
-        m = relu_chain_step(delta_h0, ops_bwd[4]["W"], ones, dt)
-        r[dt] = (pe_jacobian_T(dirs, 1.0, m["y"][:, 259:286], dt, n_freqs=4), m["mag"][:, 259:286])
+        m = relu_chain_step(delta_h0, ops_bwd[4]["W"], ones, dt, f32)
+        r[dt] = (pe_jacobian_T(dirs, 1.0, m["y"][:, 259:286], dt, n_freqs=4, trig=(U23, 0.0) if f32 else HW_TRIG), m["mag"][:, 259:286])
     j64, mag = r[torch.float64]
     w = np.concatenate([np.ones(3)] + [np.full(6, 2.0 ** k) for k in range(4)])
-    carried = (3.0 * 2 * ops_bwd[4]["kt"] * U24 * mag * w).reshape(len(mag), 9, 3).sum(1)
+    # (f32: the library sincosf of the exact product 2^k d, and the adjoints' float32 floor is their own chain: nothing carried)
+    carried = (3.0 * 2 * ops_bwd[4]["kt"] * U24 * mag * w).reshape(len(mag), 9, 3).sum(1) * (0.0 if f32 else 1.0)
     return dict(y64=j64["y"], y32=r[torch.float32][0]["y"], unit=U24 * 3.0 * j64["mag"], extra=j64["extra"] + carried, stored="f32")
 
 
-def simulate_head_backward(ops_bwd, g_out, out, h_planes, squeeze, rnd=bf16_rne):
+def simulate_head_backward(ops_bwd, g_out, out, h_planes, squeeze, rnd=bf16_rne, chain=False):
     """The CPU stand-in of the launch (float32 chain through its own bf16 planes)."""
     planes = {"delta_out": rnd(head_delta_out(g_out, out, squeeze, torch.float32)["y"])}
     nxt = planes["delta_out"]
     for l in (3, 2, 1, 0):
-        planes["delta_h%d" % l] = rnd(relu_chain_step(nxt, ops_bwd[3 - l]["W"], h_planes[l] > 0, torch.float32)["y"])
+        planes["delta_h%d" % l] = rnd(relu_chain_step(nxt, ops_bwd[3 - l]["W"], h_planes[l] > 0, torch.float32, chain)["y"])
         nxt = planes["delta_h%d" % l]
-    u = relu_chain_step(nxt, ops_bwd[4]["W"], np.ones((len(nxt), ops_bwd[4]["W"].shape[0])), torch.float32)["y"]
+    u = relu_chain_step(nxt, ops_bwd[4]["W"], np.ones((len(nxt), ops_bwd[4]["W"].shape[0])), torch.float32, chain)["y"]
     planes["d_feat"], planes["d_pts"], planes["d_normals"] = rnd(u[:, :256]), u[:, 256:259], u[:, 286:289]
     return planes
 
@@ -699,39 +751,39 @@ def simulate_head_backward(ops_bwd, g_out, out, h_planes, squeeze, rnd=bf16_rne)
 # delta_head) . [h_7 > 0]; delta_h[l] = (W_{l+1}^T delta_h[l+1]) . [h_l > 0], layer 5's transposed image in its padded input
 # order [pe (96) | h_4 (256)].
 
-def nerf_bwd_plane_models(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, planes):
+def nerf_bwd_plane_models(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, planes, f32=False):
     """{plane: dict(y64, y32, unit, extra, stored)} of one launch, each from the saved delta plane after it and the forward's saved
     activations (their masks). ob: layers 0..9 of 'bwd'. g_feat None: without the dpt head (delta_o is [P,32])."""
     res = {}
+    st = "f32" if f32 else "bf16"                        # (f32: vdn_nerf_mlp_bwd_f32, as head_plane_models)
     g_o = np.zeros((len(g_rgb), 128 if g_feat is not None else 32))
     g_o[:, :3] = g_rgb
     if g_feat is not None:
         g_o[:, 32:] = g_feat
-    res["delta_o"] = dict(y64=g_o, y32=g_o, unit=np.zeros_like(g_o), extra=0.0, stored="bf16")
-    steps = [("delta_v", "delta_o", 0, hv_plane > 0)]
+    res["delta_o"] = dict(y64=g_o, y32=g_o, unit=np.zeros_like(g_o), extra=0.0, stored=st)
     both = {}
     for dt in (torch.float64, torch.float32):
-        m = relu_chain_step(planes["delta_o"], ob[0]["W"], hv_plane > 0, dt)
-        u = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(g_rgb), ob[1]["W"].shape[0])), dt)
+        m = relu_chain_step(planes["delta_o"], ob[0]["W"], hv_plane > 0, dt, f32)
+        u = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(g_rgb), ob[1]["W"].shape[0])), dt, f32)
         both[dt] = (m, u)
     m64, u64 = both[torch.float64]
-    res["delta_v"] = dict(y64=m64["y"], y32=both[torch.float32][0]["y"], unit=U24 * m64["mag"], extra=0.0, stored="bf16")
+    res["delta_v"] = dict(y64=m64["y"], y32=both[torch.float32][0]["y"], unit=U24 * m64["mag"], extra=0.0, stored=st)
     gd = np.asarray(g_density, np.float64)[:, None]
     res["delta_head"] = dict(y64=np.concatenate([u64["y"][:, :256], gd], -1), y32=np.concatenate([both[torch.float32][1]["y"][:, :256], gd], -1),
-                             unit=np.concatenate([U24 * u64["mag"][:, :256], np.zeros_like(gd)], -1), extra=0.0, stored="bf16")
+                             unit=np.concatenate([U24 * u64["mag"][:, :256], np.zeros_like(gd)], -1), extra=0.0, stored=st)
     nxt = planes["delta_head"]
     for l, li in ((7, 2), (6, 3), (5, 4), (4, 5), (3, 6), (2, 7), (1, 8), (0, 9)):
         mask = h_planes[l] > 0
         if l == 4:                                        # W_5^T's rows: [pe (96) | h_4 (256)]
             mask = np.concatenate([np.zeros((len(mask), 96), bool), mask], -1)
-        a64, a32 = (relu_chain_step(nxt, ob[li]["W"], mask, dt) for dt in (torch.float64, torch.float32))
+        a64, a32 = (relu_chain_step(nxt, ob[li]["W"], mask, dt, f32) for dt in (torch.float64, torch.float32))
         sel = slice(96, 352) if l == 4 else slice(None)
-        res["delta_h%d" % l] = dict(y64=a64["y"][:, sel], y32=a32["y"][:, sel], unit=U24 * a64["mag"][:, sel], extra=0.0, stored="bf16")
+        res["delta_h%d" % l] = dict(y64=a64["y"][:, sel], y32=a32["y"][:, sel], unit=U24 * a64["mag"][:, sel], extra=0.0, stored=st)
         nxt = planes["delta_h%d" % l]
     return res
 
 
-def simulate_nerf_backward(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, rnd=bf16_rne, dtype=torch.float32):
+def simulate_nerf_backward(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, rnd=bf16_rne, dtype=torch.float32, chain=False):
     """The CPU stand-in of the launch (float32 chain through its own bf16 planes; float64 with rnd = identity: the exact chain)."""
     f32 = dtype
     g_o = np.zeros((len(g_rgb), 128 if g_feat is not None else 32))
@@ -739,15 +791,15 @@ def simulate_nerf_backward(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, rnd
     if g_feat is not None:
         g_o[:, 32:] = g_feat
     planes = {"delta_o": rnd(g_o)}
-    planes["delta_v"] = rnd(relu_chain_step(planes["delta_o"], ob[0]["W"], hv_plane > 0, f32)["y"])
-    u = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(g_rgb), ob[1]["W"].shape[0])), f32)["y"]
+    planes["delta_v"] = rnd(relu_chain_step(planes["delta_o"], ob[0]["W"], hv_plane > 0, f32, chain)["y"])
+    u = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(g_rgb), ob[1]["W"].shape[0])), f32, chain)["y"]
     planes["delta_head"] = rnd(np.concatenate([u[:, :256], np.asarray(g_density, np.float64)[:, None]], -1))
     nxt = planes["delta_head"]
     for l, li in ((7, 2), (6, 3), (5, 4), (4, 5), (3, 6), (2, 7), (1, 8), (0, 9)):
         mask = h_planes[l] > 0
         if l == 4:
             mask = np.concatenate([np.zeros((len(mask), 96), bool), mask], -1)
-        y = relu_chain_step(nxt, ob[li]["W"], mask, f32)["y"]
+        y = relu_chain_step(nxt, ob[li]["W"], mask, f32, chain)["y"]
         planes["delta_h%d" % l] = rnd(y[:, 96:352] if l == 4 else y)
         nxt = planes["delta_h%d" % l]
     return planes
@@ -760,7 +812,7 @@ def simulate_nerf_backward(ob, g_density, g_rgb, g_feat, h_planes, hv_plane, rnd
 # ab_{l-1} = (W_l^T ab_l) . s_{l-1} + ex_{l-1}. UB, EX and AB are in the network's own units; s_l = 1 - 2^-H[l] from the saved
 # plane in both the kernel and the model (s_from_h = 2): no extra term.
 
-def pe_jacobian(pts, scale, g_n, dtype=torch.float64):
+def pe_jacobian(pts, scale, g_n, dtype=torch.float64, trig=HW_TRIG):
     """ub_0 = scale J_PE(scale p) g_n [P,39], with mag (= |ub_0|: one product chain each) and the hardware-trig extra term."""
     p = _t(pts, dtype) * torch.tensor(float(scale), dtype=dtype)
     g = _t(g_n, dtype) * torch.tensor(float(scale), dtype=dtype)
@@ -769,7 +821,7 @@ def pe_jacobian(pts, scale, g_n, dtype=torch.float64):
         f = float(2 ** k)
         a = p * f
         cols += [f * torch.cos(a) * g, -f * torch.sin(a) * g]
-        e = f * (TRIG_ABS + TRIG_ARG * a.abs().double()) * g.abs().double()
+        e = f * (trig[0] + trig[1] * a.abs().double()) * g.abs().double()
         ex += [e, e]
     y = torch.cat(cols, -1).double().numpy()
     return {"y": y, "unit": U24 * 4.0 * np.abs(y), "extra": torch.cat(ex, -1).numpy()}
@@ -785,42 +837,59 @@ def rbar_operand(l, ub_l):
     return ub_l
 
 
-def sdf_rbar_step(l, ub_l, W, H_l, V_l, dtype=torch.float64, ex_factor=LN2, aten_threshold=False):
-    """ub_{l+1} (its columns made by layer l) and ex_l from the saved ub_l, H[l] and V[l]. -> dicts with y / unit."""
+def one_minus_sigma(S_l, dtype, s_mode, aten_threshold=False):
+    """(softplus', E = 1 - softplus', dE) of a loaded plane value, as VdnSdfRbarArgs.s_from_h reads it, and what the exponential and (s_mode 1) the
+    rounded product 100 log2(e) h may move it by: s_mode 2: the plane holds H = 100 log2(e) h, E = 2^-H; 1: the plane holds h in the
+    network's units, E = 2^-(100 log2(e) h) = exp(-100 h); 0: the plane holds softplus' itself (the fp32 forward's S), E = 1 - S
+    as the kernel forms it (exact above 1/2)."""
+    H = _t(S_l, dtype)
+    if s_mode == 0:
+        return H, 1.0 - H, np.zeros(H.shape)
+    t = H if s_mode == 2 else H * torch.tensor(C, dtype=dtype)
+    E = torch.exp2(-t)
+    if aten_threshold:                                   # (the reference's softplus: see sdf_sweep)
+        E = torch.where(t > math.log2(1.0 + math.exp(20.0)), torch.zeros_like(E), E)
+    Ed, td = E.double().numpy(), t.double().numpy()
+    return 1.0 - E, E, U23 * Ed + (2.0 * U24 * LN2 * td * Ed if s_mode == 1 else 0.0)
+
+
+def sdf_rbar_step(l, ub_l, W, H_l, V_l, dtype=torch.float64, ex_factor=LN2, aten_threshold=False, s_mode=2, chain=False):
+    """ub_{l+1} (its columns made by layer l) and ex_l from the saved ub_l, H[l] and V[l]. -> dicts with y / unit. The fp32 launch:
+    ex_factor = 100 (V in the network's units), s_mode 0 or 1 (one_minus_sigma), chain (mfma_chain_f32)."""
     X, Wt = _t(rbar_operand(l, ub_l), dtype), _t(W, dtype)
     n = 256 - D0 if l == 3 else 256
-    vbar = (X @ Wt.T)[:, :n]
+    vbar = _mm(X, Wt, None, dtype, chain)[:, :n]
     mag = (X.abs().double() @ Wt.abs().double().T)[:, :n].numpy()
-    H, V = _t(H_l, dtype)[:, :n], _t(V_l, dtype)[:, :n]
-    E = torch.exp2(-H)
-    if aten_threshold:                                   # (the reference's softplus: see sdf_sweep)
-        E = torch.where(H > math.log2(1.0 + math.exp(20.0)), torch.zeros_like(E), E)
-    sig = 1.0 - E
+    V = _t(V_l, dtype)[:, :n]
+    sig, E, dE = one_minus_sigma(np.asarray(H_l, np.float64)[:, :n], dtype, s_mode, aten_threshold)
     ub = vbar * sig
     # the documented order (DESIGN.md section 4: ex_l = 100 vbar_l v_l (1 - s_l), s_l = 1 - 2^-H): 1 - s_l is formed from the ROUNDED
     # s_l, so it carries an absolute error of one rounding of a number just below 1 (2^-24), whatever its own size
-    ex = vbar * V * (1.0 - sig) * torch.tensor(ex_factor, dtype=dtype)
+    k = torch.tensor(ex_factor, dtype=dtype)
+    # (network units, s_mode 0 / 1: the factor first, as DESIGN.md section 4 writes it - on the "hot" state vbar_l v_l alone passes
+    # through the float32 subnormals, and a floor taken behind that would be the model's own loss, not a rounding)
+    ex = vbar * V * (1.0 - sig) * k if s_mode == 2 else k * vbar * V * (1.0 - sig)
     s, Ed, Vd = sig.double().numpy(), E.double().numpy(), V.abs().double().numpy()
     vb = np.abs(vbar.double().numpy())
-    return {"ub": ub.double().numpy(), "ub_unit": U24 * (mag * s + 2.0 * np.abs(ub.double().numpy())) + U23 * mag * Ed,
-            "ex": ex.double().numpy(), "ex_unit": U24 * LN2 * Vd * (Ed * mag + vb) + (3.0 * U24 + U23) * np.abs(ex.double().numpy())}
+    # (dE = 2^-23 E in the scaled units of the bf16 launch: there the two dE terms are 2^-23 mag E and 2^-23 |ex|)
+    return {"ub": ub.double().numpy(), "ub_unit": U24 * (mag * s + 2.0 * np.abs(ub.double().numpy())) + mag * dE,
+            "ex": ex.double().numpy(), "ex_unit": U24 * ex_factor * Vd * (Ed * mag + vb) + 3.0 * U24 * np.abs(ex.double().numpy()) +
+            ex_factor * vb * Vd * dE}
 
 
-def sdf_fbar_step(l, ab_l, Wt, H_prev, EX_prev, dtype=torch.float64, aten_threshold=False):
+def sdf_fbar_step(l, ab_l, Wt, H_prev, EX_prev, dtype=torch.float64, aten_threshold=False, s_mode=2, chain=False):
     """ab_{l-1} = (W_l^T ab_l) . s_{l-1} + ex_{l-1} from the saved ab_l, H[l-1] and EX[l-1]."""
     A, W = _t(ab_l, dtype), _t(Wt, dtype)
     A = A[:, :W.shape[1]] if A.shape[1] >= W.shape[1] else torch.cat([A, torch.zeros(len(A), W.shape[1] - A.shape[1], dtype=dtype)], -1)
     A = torch.where((W.abs().sum(0) > 0)[None, :], A, torch.zeros_like(A))      # (columns no weight reads: the image's padding)
     n = 256 - D0 if l == 4 else 256
-    t = (A @ W.T)[:, :n]
+    t = _mm(A, W, None, dtype, chain)[:, :n]
     mag = (A.abs().double() @ W.abs().double().T)[:, :n].numpy()
-    H, EX = _t(H_prev, dtype)[:, :n], _t(EX_prev, dtype)[:, :n]
-    E = torch.exp2(-H)
-    if aten_threshold:
-        E = torch.where(H > math.log2(1.0 + math.exp(20.0)), torch.zeros_like(E), E)
-    y = (t * (1.0 - E) + EX).double().numpy()
-    s, Ed = (1.0 - E).double().numpy(), E.double().numpy()
-    return {"y": y, "unit": U24 * (mag * s + 2.0 * np.abs(t.double().numpy()) * s + np.abs(y)) + U23 * mag * Ed}
+    EX = _t(EX_prev, dtype)[:, :n]
+    sig, E, dE = one_minus_sigma(np.asarray(H_prev, np.float64)[:, :n], dtype, s_mode, aten_threshold)
+    y = (t * sig + EX).double().numpy()
+    s = sig.double().numpy()
+    return {"y": y, "unit": U24 * (mag * s + 2.0 * np.abs(t.double().numpy()) * s + np.abs(y)) + mag * dE}
 
 
 UB_COLS = (64, 256, 256, 256, 288, 256, 256, 256, 256)
@@ -859,7 +928,7 @@ def sdf_fbar_ops(img, rounded=True):
 def simulate_sdf_backward(ops, ops_fbar, pts, scale, g_sdf, g_feat, g_n, H, V, rnd=bf16_rne, dtype=torch.float32, **kw):
     """The CPU stand-in of rbar + fbar (float32 chain through its own bf16 blocks; float64 with rnd = identity: the exact chain).
     -> ub (9 blocks), EX (8 planes), ab (9 blocks, by layer). kw: ex_factor / aten_threshold of sdf_rbar_step."""
-    fk = {k: v for k, v in kw.items() if k == "aten_threshold"}
+    fk = {k: v for k, v in kw.items() if k in ("aten_threshold", "s_mode", "chain")}
     ub = [rnd(_padded(pe_jacobian(pts, scale, g_n, dtype)["y"], 64))]
     EX = []
     for l in range(8):
@@ -877,20 +946,20 @@ def simulate_sdf_backward(ops, ops_fbar, pts, scale, g_sdf, g_feat, g_n, H, V, r
     return ub, EX, ab
 
 
-def encoding_jacobian_T(x, U, n_freqs, dtype=torch.float64):
+def encoding_jacobian_T(x, U, n_freqs, dtype=torch.float64, trig=HW_TRIG):
     """J^T U of the plain encoding [x, sin(2^0 x), cos(2^0 x), ...] of a d-vector: -> y [P,d], mag (sum of |terms|), the
     hardware-trig extra term, and `carry` = sum_j |J_j| e_j for a given per-column error e of U (see nerf_input_adjoint_models)."""
     xt, Ut = _t(x, dtype), _t(U, dtype)
     d = xt.shape[1]
-    y, mag, trig = Ut[:, :d].clone(), Ut[:, :d].abs().double(), torch.zeros(len(xt), d, dtype=torch.float64)
+    y, mag, terr = Ut[:, :d].clone(), Ut[:, :d].abs().double(), torch.zeros(len(xt), d, dtype=torch.float64)
     for k in range(n_freqs):
         f = float(2 ** k)
         us, uc = Ut[:, d * (1 + 2 * k):d * (2 + 2 * k)], Ut[:, d * (2 + 2 * k):d * (3 + 2 * k)]
         a = xt * f
         y = y + f * (torch.cos(a) * us - torch.sin(a) * uc)
         mag = mag + f * ((torch.cos(a) * us).abs() + (torch.sin(a) * uc).abs()).double()
-        trig = trig + f * (TRIG_ABS + TRIG_ARG * a.abs().double()) * (us.abs() + uc.abs()).double()
-    return {"y": y.double().numpy(), "mag": mag.numpy(), "extra": trig.numpy()}
+        terr = terr + f * (trig[0] + trig[1] * a.abs().double()) * (us.abs() + uc.abs()).double()
+    return {"y": y.double().numpy(), "mag": mag.numpy(), "extra": terr.numpy()}
 
 
 def _carried(err, d, n_freqs):
@@ -899,7 +968,7 @@ def _carried(err, d, n_freqs):
     return (err * w).reshape(len(err), 1 + 2 * n_freqs, d).sum(1)
 
 
-def nerf_input_adjoint_models(ob, pts4, dirs, planes):
+def nerf_input_adjoint_models(ob, pts4, dirs, planes, f32=False):
     """d_pts4 [P,4] and d_dirs [P,3] of vdn_nerf_mlp_bwd_input_bf16 (explicit inputs: the encodings' Jacobians, no map through the
     inverted sphere) from the saved delta_h0, delta_h5 and delta_v: the adjoints of the two encodings (W_0^T delta_h0 + the encoded
     input's rows of W_5^T delta_h5; the view's rows of W_views^T delta_v) are no plane, so each output is modelled in one piece.
@@ -907,31 +976,35 @@ def nerf_input_adjoint_models(ob, pts4, dirs, planes):
     res = {}
     r = {}
     for dt in (torch.float64, torch.float32):
-        a0 = relu_chain_step(planes["delta_h0"], ob[10]["W"], np.ones((len(pts4), 96)), dt)
-        a5 = relu_chain_step(planes["delta_h5"], ob[5]["W"], np.ones((len(pts4), 352)), dt)
-        av = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(pts4), 288)), dt)
+        a0 = relu_chain_step(planes["delta_h0"], ob[10]["W"], np.ones((len(pts4), 96)), dt, f32)
+        a5 = relu_chain_step(planes["delta_h5"], ob[5]["W"], np.ones((len(pts4), 352)), dt, f32)
+        av = relu_chain_step(planes["delta_v"], ob[1]["W"], np.ones((len(pts4), 288)), dt, f32)
         r[dt] = (a0["y"][:, :84] + a5["y"][:, :84], a0["mag"][:, :84] + a5["mag"][:, :84], av["y"][:, 256:283], av["mag"][:, 256:283])
     for name, x, nf, iy, d, kt in (("d_pts4", pts4, 10, 0, 4, ob[10]["kt"] + ob[5]["kt"]), ("d_dirs", dirs, 4, 2, 3, ob[1]["kt"])):
-        j64 = encoding_jacobian_T(x, r[torch.float64][iy], nf, torch.float64)
-        j32 = encoding_jacobian_T(x, r[torch.float32][iy], nf, torch.float32)
-        carry = _carried(3.0 * 2 * kt * U24 * r[torch.float64][iy + 1], d, nf)
+        tr = (U23, 0.0) if f32 else HW_TRIG              # (f32: the library sincosf of the exact product 2^k x; nothing carried)
+        j64 = encoding_jacobian_T(x, r[torch.float64][iy], nf, torch.float64, tr)
+        j32 = encoding_jacobian_T(x, r[torch.float32][iy], nf, torch.float32, tr)
+        carry = _carried(3.0 * 2 * kt * U24 * r[torch.float64][iy + 1], d, nf) * (0.0 if f32 else 1.0)
         res[name] = dict(y64=j64["y"], y32=j32["y"], unit=U24 * 3.0 * j64["mag"], extra=j64["extra"] + carry, stored="f32")
     return res
 
 
-def sdf_d_pts_model(ops_fbar, pts, scale, g_n, U_pe, ab0, ab4):
+def sdf_d_pts_model(ops_fbar, pts, scale, g_n, U_pe, ab0, ab4, f32=False, before=None):
     """d_pts [P,3] of vdn_sdf_bwd_fbar_bf16: scale J_PE^T a_e + the explicit x-dependence of the Jacobian in
     n = scale J_PE(x)^T U_pe, a_e = W_0^T ab_0 + (W_4^T ab_4)[encoded input's rows] the adjoint of the encoded input (no plane: the
     output is modelled in one piece from the saved ab_0, ab_4 and the forward's U_pe):
-        d_pts_d = scale (J^T a_e)_d - scale^2 g_n,d sum_k 4^k (sin(2^k s x_d) U_sin,k,d + cos(2^k s x_d) U_cos,k,d)."""
+        d_pts_d = scale (J^T a_e)_d - scale^2 g_n,d sum_k 4^k (sin(2^k s x_d) U_sin,k,d + cos(2^k s x_d) U_cos,k,d).
+    f32: vdn_sdf_bwd_fbar_f32 - the library sincosf (LIB_TRIG) and the adjoints' float32 floor is their own k-ordered chain, so
+    nothing is carried. before [P,3]: acc_pts = 1, the output is what d_pts held + the adjoint (one more rounding in the unit)."""
     r = {}
+    tr = LIB_TRIG if f32 else HW_TRIG
     for dt in (torch.float64, torch.float32):
-        a0 = relu_chain_step(ab0, ops_fbar[0]["W"], np.ones((len(pts), ops_fbar[0]["W"].shape[0])), dt)
-        a4 = relu_chain_step(np.asarray(ab4)[:, :256], ops_fbar[4]["W"], np.ones((len(pts), 288)), dt)
+        a0 = relu_chain_step(ab0, ops_fbar[0]["W"], np.ones((len(pts), ops_fbar[0]["W"].shape[0])), dt, f32)
+        a4 = relu_chain_step(np.asarray(ab4)[:, :256], ops_fbar[4]["W"], np.ones((len(pts), 288)), dt, f32)
         ae, mag = a0["y"][:, :D0] + a4["y"][:, 224:224 + D0], a0["mag"][:, :D0] + a4["mag"][:, 224:224 + D0]
         sc = torch.tensor(float(scale), dtype=dt)
         x = _t(pts, dt) * sc
-        j = encoding_jacobian_T(x.double().numpy() if dt == torch.float64 else x.numpy(), ae, 6, dt)
+        j = encoding_jacobian_T(x.double().numpy() if dt == torch.float64 else x.numpy(), ae, 6, dt, tr)
         U, g = _t(U_pe, dt), _t(g_n, dt)
         second, smag, strig = torch.zeros_like(x), torch.zeros(x.shape, dtype=torch.float64), torch.zeros(x.shape, dtype=torch.float64)
         for k in range(6):
@@ -939,14 +1012,17 @@ def sdf_d_pts_model(ops_fbar, pts, scale, g_n, U_pe, ab0, ab4):
             us, uc = U[:, 3 + 6 * k:6 + 6 * k], U[:, 6 + 6 * k:9 + 6 * k]
             second = second + f * (torch.sin(a) * us + torch.cos(a) * uc)
             smag = smag + f * ((torch.sin(a) * us).abs() + (torch.cos(a) * uc).abs()).double()
-            strig = strig + f * (TRIG_ABS + TRIG_ARG * a.abs().double()) * (us.abs() + uc.abs()).double()
+            strig = strig + f * (tr[0] + tr[1] * a.abs().double()) * (us.abs() + uc.abs()).double()
         y = _t(j["y"], dt) * sc - sc * sc * g * second
+        if before is not None:
+            y = _t(before, dt) + y
         s1, s2 = float(scale), float(scale) ** 2
         r[dt] = dict(y=y.double().numpy(), mag=s1 * j["mag"] + s2 * (g.abs().double() * smag).numpy(),
                      extra=s1 * j["extra"] + s2 * (g.abs().double() * strig).numpy() +
-                     s1 * _carried(3.0 * 2 * (ops_fbar[0]["kt"] + ops_fbar[4]["kt"]) * U24 * mag, 3, 6))
+                     s1 * _carried(3.0 * 2 * (ops_fbar[0]["kt"] + ops_fbar[4]["kt"]) * U24 * mag, 3, 6) * (0.0 if f32 else 1.0))
     m = r[torch.float64]
-    return dict(y64=m["y"], y32=r[torch.float32]["y"], unit=U24 * 4.0 * m["mag"], extra=m["extra"], stored="f32")
+    unit = U24 * 4.0 * m["mag"] + (0.0 if before is None else U24 * np.abs(m["y"]))
+    return dict(y64=m["y"], y32=r[torch.float32]["y"], unit=unit, extra=m["extra"], stored="f32")
 
 
 # ---- the comparator ---------------------------------------------------------------------------------------------------------
@@ -964,6 +1040,10 @@ def judge(got, y64, y32, unit, extra=0.0, stored="bf16"):
     got, y64, y32 = (np.asarray(a, np.float64) for a in (got, y64, y32))
     unit = np.broadcast_to(np.asarray(unit, np.float64), y64.shape)
     extra = np.broadcast_to(np.asarray(extra, np.float64), y64.shape)
+    if stored == "f32":
+        # below 2^-126 a float32 is spaced 2^-149 whatever its size: a result there, or a product formed from one, carries up to half
+        # that spacing per rounding, which no multiple of 2^-24 |y| covers (two roundings; an exact zero still admits nothing)
+        unit = np.where(unit > 0.0, unit + F32_QUANTUM, 0.0)
     floor = _ratio(np.maximum(np.abs(y32 - y64) - extra, 0.0), unit)        # (beyond the extra term, as `err` below)
     bound = max(1.0, 3.0 * floor)
     e = bound * unit + extra
@@ -1069,4 +1149,198 @@ def judge_planes(models, planes):
         got = np.asarray(planes[k], np.float64)
         got = got[:, :m["y64"].shape[1]] if got.ndim == 2 else got
         res[k] = judge(got, m["y64"], m["y32"], m["unit"], m["extra"], m["stored"])
+    return res
+
+
+# ---- the fp32 SDF launches (vdn_sdf_mlp_fwd_f32 mode 1; vdn_sdf_bwd_rbar_f32 / vdn_sdf_bwd_fbar_f32 through sdf_bwd_models_f32) -------
+# Network units, row-major f32 planes, the fmt-0 operand weights of sdf_streams(scaled=False): PE [P,64] = the encoding of scale p
+# (39 valid); a_l = W_l H[l-1] + b_l (layer 4 on [H[3] (217) | PE], 1 / sqrt 2 in the image); H[l] = softplus(100 a_l) / 100 and
+# S[l] = sigmoid(100 a_l), both from the saved H[l-1]; feat = rows 0..255 of the last image on the saved H[7], sdf = row 256 / scale;
+# V[7] = w8row / scale . S[7], V[l] = (W_{l+1}^T V[l+1]) . S[l] from the saved V[l+1] and S[l]; U_pe = u_4[PE part] + u_0;
+# normals = scale J_PE^T U_pe from the saved U_pe. No factor C, no residue slots, no 8-bit softplus', no bf16 rounding: every plane is
+# the f32 value itself, so a plane's only allowance is max(1, 3 floor) units, floor = the float32 model in the kernel's documented
+# order (mfma_chain_f32; softplus100_pair in float32), plus the library sincosf's term where a sine enters behind a sum (LIB_TRIG).
+
+def f32_rne(a):
+    """Nearest float32 as float64: the 'rounding' of a plane of the fp32 launches' stand-ins."""
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+def softplus100_pair(a, dtype=torch.float64, aten_threshold=False):
+    """(softplus(100 a) / 100, sigmoid(100 a)). float64: the stable closed forms (aten_threshold: the reference's softplus, which
+    returns a itself and derivative 1 where 100 a > 20 - the chain tests against the oracle). float32: the evaluation
+    include/vdn_render.h documents for the fp32 entry point - t = 100 log2(e) a, e = 2^-|t|, u = 1 + e, h = log2(u) ln 2 / 100 +
+    max(a, 0), r = 1 / u, s = a >= 0 ? r : e r - as the floor."""
+    a = _t(a, dtype)
+    if dtype == torch.float64:
+        z = 100.0 * a
+        h, s = torch.clamp(a, min=0.0) + torch.log1p(torch.exp(-z.abs())) / 100.0, torch.sigmoid(z)
+        if aten_threshold:
+            h, s = torch.where(z > 20.0, a, h), torch.where(z > 20.0, torch.ones_like(s), s)
+        return h, s
+    t = a * torch.tensor(C, dtype=dtype)
+    e = torch.exp2(-t.abs())
+    u = 1.0 + e
+    r = 1.0 / u
+    return torch.log2(u) * torch.tensor(LN2 / 100.0, dtype=dtype) + torch.clamp(a, min=0.0), torch.where(a >= 0, r, e * r)
+
+
+def sdf_hidden_operand_f32(l, x_plane, pe_plane):
+    """Input of hidden layer l of the unscaled stream in its image's padded k order (pad columns and columns 217.. of H[3] read
+    zero weights: vdn_hip/images.py sdf_streams, kmap of lin4)."""
+    pe = None if pe_plane is None else _padded(np.asarray(pe_plane, np.float64)[:, :D0], 64)
+    if l == 0:
+        return pe
+    if l == 4:
+        return np.concatenate([_padded(np.asarray(x_plane, np.float64)[:, :256 - D0], 224), pe], -1)
+    return np.asarray(x_plane, np.float64)
+
+
+def sdf_hidden_f32(l, x_plane, pe_plane, W, b, dtype=torch.float64, aten_threshold=False):
+    a, mag = _linear(sdf_hidden_operand_f32(l, x_plane, pe_plane), W, b, dtype, chain=True)
+    h, s = softplus100_pair(a, dtype, aten_threshold)
+    return {"h": h.double().numpy(), "s": s.double().numpy(), "a": a, "mag": mag}
+
+
+def hidden_units_f32(m):
+    """(unit of H, unit of S) from the float64 model, one float32 rounding per operation, every transcendental (v_exp_f32,
+    v_log_f32, v_rcp_f32) at 2^-23 |y|. With t = 100 log2(e) |a|, e = 2^-t, L = log2(1 + e), q = e / (1 + e) = min(s, 1 - s):
+    H: a (2^-24 mag, through dh/da = s), the product t (constant and product: 2 2^-24 t, through dh/dt = q ln 2 / 100), the
+       exponential (2^-23 e: 2^-23 q / 100), the sum 1 + e (2^-24 (1 + e): 2^-24 / 100), the logarithm (2^-23 L ln 2 / 100), the
+       constant ln 2 / 100 and the final multiply-add (2^-24 (L ln 2 / 100 + |h|)).
+    S: a (through ds/da = 100 s (1 - s)), t (through ds/dt = ln 2 s (1 - s)), the exponential (2^-23 s (1 - s)), the sum and the
+       reciprocal (2^-24 s, 2^-23 s) and - S's own term - the product e r where a < 0 (2^-24 s; granted on both sides)."""
+    s, h, mag = m["s"], np.abs(m["h"]), m["mag"]
+    t = C * np.abs(m["a"])
+    e = np.exp2(-t)
+    L, q, w = np.log2(1.0 + e), e / (1.0 + e), s * (1.0 - s)
+    unit_h = U24 * (mag * s + h + L * LN2 / 100.0 + 1.0 / 100.0 + 2.0 * t * q * LN2 / 100.0) + U23 * (q / 100.0 + L * LN2 / 100.0)
+    unit_s = U24 * (mag * 100.0 * w + 2.0 * LN2 * t * w + 2.0 * s) + U23 * (w + s)
+    return unit_h, unit_s
+
+
+def _sweep_operand_f32(l, V_l, k_pad):
+    """V[l] as the operand of W_l^T (columns 217.. of V[3] are not outputs of layer 3; their weights are zero)."""
+    v = np.array(np.asarray(V_l, np.float64)[:, :k_pad])
+    if l == 3:
+        v = _padded(v[:, :256 - D0], k_pad)
+    return v
+
+
+def sdf_plane_models_f32(ops, ops_sweep, w8row, pts, scale, planes):
+    """{plane: dict(y64, y32, unit, extra, stored)} of one vdn_sdf_mlp_fwd_f32 mode-1 launch with every save, each plane from the
+    saved planes before it (`planes`: PE [P,39], H0..H7, S0..S7, V0..V7 [P,256], U_pe [P,39] as the launch left them). ops: layers
+    0..8 of 'full', ops_sweep[l]: the image of W_l^T, both from operand_weights(fmt=0); w8row: row 0 of W_8 (float32)."""
+    out = {}
+    dts = (torch.float64, torch.float32)
+    pe64, pe32 = (posenc_scaled(pts, scale, dt, 1.0) for dt in dts)
+    trig = np.ones_like(pe64["y"])
+    trig[:, :3] = 0.0
+    out["PE"] = dict(y64=pe64["y"], y32=pe32["y"], unit=U24 * np.abs(pe64["arg"]) * pe64["deriv"] + U23 * np.abs(pe64["y"]) * trig,
+                     extra=0.0, stored="f32")
+    for l in range(8):
+        n = 256 - D0 if l == 3 else 256
+        m64, m32 = (sdf_hidden_f32(l, planes["H%d" % (l - 1)] if l else None, planes["PE"], ops[l]["W"], ops[l]["b"], dt) for dt in dts)
+        uh, us = hidden_units_f32(m64)
+        out["H%d" % l] = dict(y64=m64["h"][:, :n], y32=m32["h"][:, :n], unit=uh[:, :n], extra=0.0, stored="f32")
+        # (the hardware exponential may flush a result below the smallest normal float32 to zero: include/vdn_render.h, VdnSdfArgs.S)
+        flush = np.where(m64["s"] < 2.0 ** -125, 2.0 ** -126, 0.0)
+        out["S%d" % l] = dict(y64=m64["s"][:, :n], y32=m32["s"][:, :n], unit=us[:, :n], extra=flush[:, :n], stored="f32")
+    sc = float(scale)
+    inv = {torch.float64: 1.0 / sc, torch.float32: float(np.float32(1.0) / np.float32(sc))}
+    (y64, mag), (y32, _) = (_linear(planes["H7"], ops[8]["W"], ops[8]["b"], dt, chain=True) for dt in dts)
+    out["feat"] = dict(y64=y64[:, :256], y32=y32[:, :256], unit=U24 * mag[:, :256], extra=0.0, stored="f32")
+    sdf64, sdf32 = y64[:, 256] * inv[torch.float64], f32_rne(y32[:, 256] * inv[torch.float32])
+    out["sdf"] = dict(y64=sdf64, y32=sdf32, unit=U24 * (mag[:, 256] / sc + 2.0 * np.abs(sdf64)), extra=0.0, stored="f32")
+    # the sweep
+    pe_part = {}
+    for l in range(7, -1, -1):
+        n = 256 - D0 if l == 3 else 256
+        S = np.asarray(planes["S%d" % l], np.float64)[:, :n]
+        r = {}
+        for dt in dts:
+            if l == 7:
+                u = (_t(w8row, dt) * torch.tensor(inv[dt], dtype=dt)).double().numpy()[None, :].repeat(len(S), 0)
+                mag = np.abs(u)                          # (the product w8row / scale: one rounding of its own)
+            else:
+                Wt = ops_sweep[l + 1]["W"]
+                u, mag = _linear(_sweep_operand_f32(l + 1, planes["V%d" % (l + 1)], Wt.shape[1]), Wt, np.zeros(len(Wt)), dt, chain=True)
+                if l == 3:                               # u_4 = [d / d h_3 (217, padded to 224) | d / d PE (39)]
+                    pe_part[dt] = (u[:, 224:224 + D0], mag[:, 224:224 + D0])
+            r[dt] = ((_t(u[:, :n], dt) * _t(S, dt)).double().numpy(), mag[:, :n])
+        y64, mag = r[torch.float64]
+        out["V%d" % l] = dict(y64=y64, y32=r[torch.float32][0], unit=U24 * (mag * S + 2.0 * np.abs(y64)), extra=0.0, stored="f32")
+    r = {}
+    for dt in dts:
+        Wt = ops_sweep[0]["W"]
+        u0, mag0 = _linear(_sweep_operand_f32(0, planes["V0"], Wt.shape[1]), Wt, np.zeros(len(Wt)), dt, chain=True)
+        r[dt] = ((_t(pe_part[dt][0], dt) + _t(u0[:, :D0], dt)).double().numpy(), pe_part[dt][1] + mag0[:, :D0])
+    y64, mag = r[torch.float64]
+    out["U_pe"] = dict(y64=y64, y32=r[torch.float32][0], unit=U24 * (mag + np.abs(y64)), extra=0.0, stored="f32")
+    n64, n32 = (pe_jacobian_T(pts, scale, planes["U_pe"], dt, trig=LIB_TRIG) for dt in dts)
+    out["normals"] = dict(y64=n64["y"], y32=n32["y"], unit=U24 * 4.0 * n64["mag"], extra=n64["extra"], stored="f32")
+    return out
+
+
+def simulate_sdf_forward_f32(ops, ops_sweep, w8row, pts, scale, dtype=torch.float32, rnd=f32_rne, defect=None, aten_threshold=False):
+    """The CPU stand-in of the launch: the chain-ordered float32 model run through its own planes (float64 with rnd = identity: the
+    exact chain, for the oracle tests). defect: a planted error - "s-negated" (S = sigmoid(-100 a)), "upe-without-u4" (the PE part of
+    u_4 left out of U_pe), "hw-trig" (the error the bf16 contract allows the encoding: 2^-18 absolute)."""
+    P = len(pts)
+    pe = posenc_scaled(pts, scale, dtype, 1.0)["y"]
+    if defect == "hw-trig":
+        pe[:, 3:] += TRIG_ABS
+    planes = {"PE": rnd(pe)}
+    for l in range(8):
+        m = sdf_hidden_f32(l, planes["H%d" % (l - 1)] if l else None, planes["PE"], ops[l]["W"], ops[l]["b"], dtype, aten_threshold)
+        n = m["h"].shape[1]
+        planes["H%d" % l], planes["S%d" % l] = np.zeros((P, 256)), np.zeros((P, 256))
+        planes["H%d" % l][:, :n], planes["S%d" % l][:, :n] = rnd(m["h"]), rnd(1.0 - m["s"] if defect == "s-negated" else m["s"])
+    inv = 1.0 / float(scale) if dtype == torch.float64 else float(np.float32(1.0) / np.float32(scale))
+    y, _ = _linear(planes["H7"], ops[8]["W"], ops[8]["b"], dtype, chain=True)
+    planes["feat"], planes["sdf"] = rnd(y[:, :256]), rnd(y[:, 256] * inv)
+    u = (_t(w8row, dtype) * torch.tensor(inv, dtype=dtype)).double().numpy()[None, :].repeat(P, 0)
+    pe4 = None
+    for l in range(7, -1, -1):
+        n = 256 - D0 if l == 3 else 256
+        planes["V%d" % l] = np.zeros((P, 256))
+        planes["V%d" % l][:, :n] = rnd((_t(u[:, :n], dtype) * _t(planes["S%d" % l][:, :n], dtype)).double().numpy())
+        Wt = ops_sweep[l]["W"]
+        u, _ = _linear(_sweep_operand_f32(l, planes["V%d" % l], Wt.shape[1]), Wt, np.zeros(len(Wt)), dtype, chain=True)
+        if l == 4:
+            pe4 = u[:, 224:224 + D0]
+    planes["U_pe"] = rnd(u[:, :D0] if defect == "upe-without-u4" else (_t(pe4, dtype) + _t(u[:, :D0], dtype)).double().numpy())
+    planes["normals"] = rnd(pe_jacobian_T(pts, scale, planes["U_pe"], dtype)["y"])
+    return planes
+
+
+def sdf_ops_f32(img, rounded=True):
+    """(layers 0..8 of the unscaled 'full' stream, the images of W_0^T .. W_7^T by l, those of the 'fbar' stream by l), fmt 0."""
+    return ([operand_weights(img, "full", l, rounded, fmt=0) for l in range(9)],
+            [operand_weights(img, "full", sweep_stream_layer(l), rounded, fmt=0) for l in range(8)],
+            [operand_weights(img, "fbar", 8 - l, rounded, fmt=0) for l in range(9)])
+
+
+def sdf_bwd_models_f32(ops, ops_fbar, pts, scale, g_sdf, g_feat, g_n, S, s_mode, V, ub, EX, ab):
+    """{block: dict(y64, y32, unit, extra, stored)} of vdn_sdf_bwd_rbar_f32 + vdn_sdf_bwd_fbar_f32, each block from the saved block
+    before it, as sdf_bwd_models: network units (ex_l = 100 vbar_l v_l (1 - s_l)), s_mode 0 - S holds the forward's softplus' planes
+    (s_from_h = 0) - or 1 - S holds the H planes and softplus' = 1 - exp(-100 h) is formed from them (s_from_h = 1)."""
+    res = {}
+    dts = (torch.float64, torch.float32)
+    j64, j32 = (pe_jacobian(pts, scale, g_n, dt, LIB_TRIG) for dt in dts)
+    res["ub0"] = dict(y64=j64["y"], y32=j32["y"], unit=j64["unit"], extra=j64["extra"], stored="f32")
+    for l in range(8):
+        m64, m32 = (sdf_rbar_step(l, ub[l], ops[l]["W"], S[l], V[l], dt, ex_factor=100.0, s_mode=s_mode, chain=True) for dt in dts)
+        res["ub%d" % (l + 1)] = dict(y64=m64["ub"], y32=m32["ub"], unit=m64["ub_unit"], extra=0.0, stored="f32")
+        res["EX%d" % l] = dict(y64=m64["ex"], y32=m32["ex"], unit=m64["ex_unit"], extra=0.0, stored="f32")
+    c = np.asarray(ub[0], np.float64)[:, :D0]
+    res["ub4pe"] = dict(y64=c, y32=c, unit=np.zeros_like(c), extra=0.0, stored="f32")
+    gs = np.asarray(g_sdf, np.float64)[:, None]
+    a8 = np.concatenate([np.asarray(g_feat, np.float64), gs / float(scale)], -1)
+    u8 = np.zeros_like(a8)
+    u8[:, 256] = U24 * np.abs(a8[:, 256])                # (one division)
+    res["ab8"] = dict(y64=a8, y32=f32_rne(a8), unit=u8, extra=0.0, stored="f32")
+    for l in range(8, 0, -1):
+        m64, m32 = (sdf_fbar_step(l, ab[l], ops_fbar[l]["W"], S[l - 1], EX[l - 1], dt, s_mode=s_mode, chain=True) for dt in dts)
+        res["ab%d" % (l - 1)] = dict(y64=m64["y"], y32=m32["y"], unit=m64["unit"], extra=0.0, stored="f32")
     return res

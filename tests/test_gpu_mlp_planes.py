@@ -20,7 +20,7 @@ units, beyond a bf16 rounding of the reference and beyond the extra term; "of it
 allowance (units and extra terms) it needs. Every (case, plane) is printed with bound, floor and kernel error (pytest -rA).
 
 Measured on the MI355X (worst over the cases of a launch; "sdf (hot)" = the weight state that reaches t >= 25 and t >= 128 in every
-layer; "sdf bwd" = rbar + fbar over all cases and upstream gradients; "head acc" = the acc_* = 1 forms). The hidden planes need one unit where t is just below -24 (1 + 2^t rounds to 1: the float32 evaluation of the documented
+layer; "sdf bwd" = rbar + fbar over all cases and upstream gradients, "d_pts+acc" = fbar's acc_pts = 1 over a finite pre-fill; "head acc" = the acc_* = 1 forms). The hidden planes need one unit where t is just below -24 (1 + 2^t rounds to 1: the float32 evaluation of the documented
 formula itself); the V planes need almost the whole code step their contract grants (the 8-bit softplus' is a truncated code):
 
 sdf        PE          6 cases  bound <=  2.09  floor <= 0.695  kernel error <= 0.000 units, <= 0.00 of its allowance
@@ -93,6 +93,7 @@ sdf bwd    ab2        12 cases  bound <=  4.36  floor <= 1.453  kernel error <= 
 sdf bwd    ab1        12 cases  bound <=  5.01  floor <= 1.668  kernel error <= 0.035 units, <= 0.01 of its allowance
 sdf bwd    ab0        12 cases  bound <=  4.92  floor <= 1.642  kernel error <= 0.081 units, <= 0.02 of its allowance
 sdf bwd    d_pts      12 cases  bound <=  1.00  floor <= 0.000  kernel error <= 0.000 units, <= 0.16 of its allowance
+sdf bwd    d_pts+acc  12 cases  bound <=  1.00  floor <= 0.000  kernel error <= 0.000 units, <= 0.16 of its allowance
 head       small       5 cases  bound <=  1.00  floor <= 0.000  kernel error <= 0.000 units, <= 0.00 of its allowance
 head       h0          5 cases  bound <=  2.80  floor <= 0.932  kernel error <= 0.000 units, <= 0.00 of its allowance
 head       h1          5 cases  bound <=  2.97  floor <= 0.991  kernel error <= 0.000 units, <= 0.00 of its allowance
@@ -150,7 +151,8 @@ vdn_nerf_mlp_bwd_bf16 on the forward's own planes: delta_o, delta_v, delta_head,
 
 vdn_nerf_mlp_bwd_input_bf16: the same delta planes bit for bit, d_pts4 and d_dirs. vdn_sdf_bwd_rbar_bf16 then vdn_sdf_bwd_fbar_bf16
 on the forward's own planes, for random upstream gradients and for each chain alone (g_feat = g_sdf = 0; g_normals = 0): every UB
-block, EX[l], every AB block, d_pts; vdn_sdf_bwd_split_bf16 gives UB and AB bit for bit and leaves EX alone.
+block, EX[l], every AB block, d_pts (acc_pts = 0, and acc_pts = 1 into a pre-filled d_pts); vdn_sdf_bwd_split_bf16 gives UB and AB bit
+for bit and leaves EX alone.
 """
 import functools
 
@@ -699,9 +701,9 @@ def _blocks(flat, P, cols, n):
 AB_COLS = (288,) + (256,) * 8
 
 
-def _sdf_backward(c, fb, kind, entry):
+def _sdf_backward(c, fb, kind, entry, before=None):
     """rbar + fbar ("two") or vdn_sdf_bwd_split_bf16 ("split") on the forward's own planes -> (ub blocks, EX planes or None, ab
-    blocks by layer)."""
+    blocks by layer). before [P,3]: fbar with acc_pts = 1 on a d_pts that holds it."""
     from vdn_hip import layout, lib
     img = _sdf_images(c["state"])[0]
     P = c["P"]
@@ -723,7 +725,9 @@ def _sdf_backward(c, fb, kind, entry):
         rb.n_active = fa.n_active = b.inp(np.asarray([n]), torch.int32)
     if entry == "two":                                   # (with the ray adjoint, which the one-launch form declines)
         fa.pts, fa.n_per_ray, fa.z_ld, fa.g_normals, fa.U_pe = rb.pts, 1, 1, rb.g_normals, fb["U_pe"].data_ptr()
-        fa.acc_pts, fa.d_pts = 0, b.out("d_pts", P, 3)
+        fa.acc_pts, fa.d_pts = int(before is not None), b.out("d_pts", P, 3)
+        if before is not None:
+            b["d_pts"].copy_(torch.as_tensor(before).to(DEV))
         _call("vdn_sdf_bwd_rbar_bf16", rb, _stream())
         _call("vdn_sdf_bwd_fbar_bf16", fa, _stream())
     else:
@@ -737,7 +741,10 @@ def _sdf_backward(c, fb, kind, entry):
     d_pts = b.np("d_pts")
     listed = np.zeros(P, bool)
     listed[rows] = True
-    assert np.isnan(d_pts[~listed]).all(), "d_pts of an unlisted point was written"
+    if before is None:
+        assert np.isnan(d_pts[~listed]).all(), "d_pts of an unlisted point was written"
+    else:
+        assert np.array_equal(d_pts[~listed], np.asarray(before, np.float64)[~listed]), "d_pts of an unlisted point was written"
     c["_d_pts"] = d_pts[rows]
     return ub, [b.rows("EX", l, P, 256, n) for l in range(8)], ab
 
@@ -752,7 +759,7 @@ def test_sdf_backward_blocks_vs_float64_layer_models(name, kind):
     and EX[l] from the UB block before it (and H[l], V[l]), ab_8 from g_feat / g_sdf, every further AB block from the AB block
     after it (and H, EX), d_pts from ab_0, ab_4 and the forward's U_pe. vdn_sdf_bwd_split_bf16 gives UB and AB bit for bit and leaves
     EX alone. With g_normals = 0, UB and EX are
-    exactly zero."""
+    exactly zero. fbar's acc_pts = 1 adds the ray adjoint into a pre-filled d_pts."""
     c = mlp_cases.sdf_case(name)
     fb, fplanes, n = _sdf_forward(c)
     ub, EX, ab = _sdf_backward(c, fb, kind, "two")
@@ -776,6 +783,14 @@ def test_sdf_backward_blocks_vs_float64_layer_models(name, kind):
     print("\n".join(rows))
     if kind == "g_normals=0":
         assert all((planes[k] == 0).all() for k in planes if k.startswith(("ub", "EX")))
+    # acc_pts = 1: the same launches add the adjoint into what d_pts held (one more rounding), the blocks bit for bit
+    before = mlp_cases.sdf_d_pts_prefill(c)
+    ub3, EX3, ab3 = _sdf_backward(c, fb, kind, "two", before=before)
+    assert all(np.array_equal(x, y, equal_nan=True) for a3, a in ((ub3, ub), (EX3, EX), (ab3, ab)) for x, y in zip(a3, a))
+    acc = mlp_ops.sdf_d_pts_model(ofb, mlp_cases.rows_of(c), c["scale"], g_n[sel], fplanes["U_pe"], ab[0], ab[4], before=before[sel])
+    rows = []
+    _hold(dict(c, name="%s/%s+acc" % (name, kind)), mlp_ops.judge_planes({"d_pts": acc}, {"d_pts": c["_d_pts"]}), rows)
+    print("\n".join(rows))
     ub2, _, ab2 = _sdf_backward(c, fb, kind, "split")
     for l in range(9):
         for tag, x, y in (("ub", ub[l], ub2[l]), ("ab", ab[l], ab2[l])):

@@ -45,6 +45,15 @@ def decode_chunk_bf16(chunk, kt):
     return W, raw[kt * 2048:].clone().view(torch.float32)
 
 
+def decode_chunk_f32(chunk, kt):
+    """One fmt-0 weight chunk (csrc/mlp_engine.h, F32; uint8 tensor of >= kt * 4096 + 128 bytes) -> (W [32, 32 kt] float32,
+    bias [32] float32). The chunk is [kt * 4 groups][64 lanes][4 f32], lane (i, h) = i + 32 h of group g holding
+    W[i][8 g + 4 h .. + 3]; behind it, at byte kt * 4096, 32 float32 biases."""
+    raw = chunk.reshape(-1)[:kt * 4096 + 128].cpu().contiguous()
+    w = raw[:kt * 4096].clone().view(torch.float32).view(4 * kt, 2, 32, 4)                 # [g, h, i, e]
+    return w.permute(2, 0, 1, 3).reshape(32, 32 * kt).contiguous(), raw[kt * 4096:].clone().view(torch.float32)
+
+
 def col_offset_elems(col0, precision):
     """Element offset of column col0 (a multiple of 32) inside a plane."""
     if precision == "fp32":
