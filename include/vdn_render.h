@@ -125,7 +125,12 @@ typedef struct {
      * workgroups (one per CU); when the list ends within tail_max_rows rows behind tail_row0 (a multiple of 128, normally one
      * full round = 32 768), vdn_sdf_mlp_fwd_bf16 leaves the rows from tail_row0 on alone and vdn_sdf_fwd_tail_bf16 - called with
      * the SAME struct - evaluates them with 32-row workgroups (csrc/k_sdf_fwd1_split.h): same planes, same values, bit for bit.
-     * Both decide on the device-side row count, so both launches are always made. tail_max_rows = 0: off. */
+     * Both decide on the device-side row count, so both launches are always made. tail_max_rows = 0: off.
+     * Promised, with saves and without (tests/test_gpu_sdf_value_launches.py): with n = the list's row count (P without a list),
+     * the rows are handed off exactly when tail_row0 < n <= tail_row0 + tail_max_rows. Then vdn_sdf_mlp_fwd_bf16 alone writes rows
+     * [0, tail_row0) of every plane and the sdf / normals of their points and nothing else, vdn_sdf_fwd_tail_bf16 alone rows
+     * [tail_row0, n) and nothing else, and the two together leave every plane (PE, H, V, feat), sdf and normals as ONE launch with
+     * tail_max_rows = 0 does, bit for bit. Otherwise vdn_sdf_mlp_fwd_bf16 evaluates every row and the tail launch writes nothing. */
     int32_t tail_row0, tail_max_rows;
     /* != 0: the launch is part of a training step, where every kernel starts on caches full of other kernels' planes: its first
      * round of workgroups then reads the weight stream into L2 up front (csrc/mlp_engine.h: warm_l2). The launches that save
@@ -135,10 +140,17 @@ typedef struct {
 int vdn_sdf_mlp_fwd_f32(int mode, const VdnSdfArgs* args_host, void* stream);
 /* bf16-MFMA variant (csrc/k_sdf_fwd2.h): blob holds bf16 chunks (fmt 1) of the SCALED streams (vdn_hip/images.py:
  * sdf_streams(scaled=True): hidden biases x 100 log2 e, last layer's weights / (100 log2 e), sweep weights / 255);
- * feat / H / V / PE are bf16 arrays in the tile-blocked layout of csrc/mlp_engine.h; sdf / normals stay f32. */
+ * feat / H / V / PE are bf16 arrays in the tile-blocked layout of csrc/mlp_engine.h; sdf / normals stay f32.
+ * One value per point, whichever launch computes it (tests/test_gpu_sdf_value_launches.py holds each to mode 1 with saves, which
+ * tests/test_gpu_mlp_planes.py holds to float64 plane by plane): mode 0 - the feature-split kernel up to 8192 points, the
+ * 128-point kernel beyond, on the "sdf" stream, whose layers 0..7 are those of "full" and whose last chunk is its sdf row -
+ * returns the sdf of mode 1 BIT FOR BIT (the same operations in the same order: the hidden layers, then the f32 chain over
+ * the unrounded activations of layer 7); mode 1 without saves (H = NULL) returns the sdf, normals and feat rows of mode 1 with
+ * saves bit for bit; explicit points and the ray form (z_ld, sdf_ld, a work list) alike; cold_start changes no bit. */
 int vdn_sdf_mlp_fwd_bf16(int mode, const VdnSdfArgs* args_host, void* stream);
 /* mode 1 (+ training saves when H is given) on rows [tail_row0, n) of the work list - see VdnSdfArgs.tail_row0; with
- * tail_row0 = 0 and tail_max_rows >= P it evaluates every row (tests). U_pe must be NULL (-10). */
+ * tail_row0 = 0 and tail_max_rows >= P it evaluates every row (tests). U_pe must be NULL (-10); tail_max_rows <= 0 or a
+ * tail_row0 that is negative or no multiple of 128 is -4; a refused call writes nothing. */
 int vdn_sdf_fwd_tail_bf16(const VdnSdfArgs* args_host, void* stream);
 
 /* ---- RenderingNetwork (colour head / 96-channel VDN head): fields.py:148-176, mode 'idr' ------

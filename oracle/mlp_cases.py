@@ -1,6 +1,8 @@
 """Constructed inputs of the bf16 plane tests (oracle/mlp_ops.py, tests/test_gpu_mlp_planes.py), deterministic from the
-case name: the SDF network first, then the heads, the colour head inside the fused SDF launches (tests/test_gpu_fused_head_planes.py)
-and the background network. tests/test_mlp_ops_model_cpu.py proves their coverage without a GPU.
+case name: the SDF network first, then the heads, the colour head inside the fused SDF launches (tests/test_gpu_fused_head_planes.py),
+the SDF launches that save no planes with the tail hand-off (tests/test_gpu_sdf_value_launches.py: SDF_VALUE_CASES, which alone go
+beyond 300 rows - the entry point routes on P > 8192, the cold-start prologue reads ahead from 128 workgroups on) and the background
+network. tests/test_mlp_ops_model_cpu.py proves their coverage without a GPU.
 
 Row counts: 1 (one row), 33 (one row past a 32-row pad block), 129 (one row past a 128-row workgroup), 300 (two full workgroups
 and a partial one whose last block is partial); one work list: 77 of 200 rows, not ascending, so that saves in compact rows
@@ -180,8 +182,8 @@ def _unit_dirs(tag, n, first=None):
     return np.stack(out)
 
 
-def fused_case(name):
-    B, n, scale, n_active, state = FUSED_CASES[name]
+def _ray_case(name, B, n, scale, n_active, state):
+    """The ray recipe of FUSED_CASES (and of the ray form of SDF_VALUE_CASES): see the comment above FUSED_CASES."""
     u = lambda tag, shape: synth.uniform(SEED, "mlp/%s/%s" % (name, tag), shape)
     rays_o = (1.2 * u("rays_o", (B, 3)) - 0.6).astype(np.float32)
     rays_d = _unit_dirs(name + "/rays_d", B, first=(1.0, 0.0, 0.0))
@@ -199,6 +201,10 @@ def fused_case(name):
     return c
 
 
+def fused_case(name):
+    return _ray_case(name, *FUSED_CASES[name])
+
+
 def fused_rows_of(c):
     """The dense point ids (ray * n_per_ray + sample) behind the rows of the saved planes: the listed ones in list order, or all."""
     return np.arange(c["P"]) if c["active_idx"] is None else c["active_idx"][:c["n_active"]].astype(np.int64)
@@ -209,6 +215,102 @@ def fused_points_of(c):
     the SDF side."""
     p = c["rays_o"][:, None, :] + c["rays_d"][:, None, :] * c["z"][:, :, None]
     return p.reshape(-1, 3).astype(np.float32)
+
+
+# ---- the bf16 SDF launches that save no planes (tests/test_gpu_sdf_value_launches.py) ------------------------------------------
+# vdn_sdf_mlp_fwd_bf16 mode 0 (csrc/k_sdf_fwd0_split.h up to 8192 points, csrc/k_sdf_fwd2.h MODE 0 beyond) and mode 1 without saves.
+# SDF_VALUE_CASES = SDF_CASES as they are (explicit points), the ray cases and the large cases below.
+# Ray form, name: (rays, samples per ray, SDFNetwork scale, n_active, (z_ld, first z column), (sdf_ld, first sdf column)). z and sdf
+# are column slices of wider rows: z_ld > n_per_ray, sdf_ld > n_per_ray, sdf_ld != z_ld, both first columns non-zero; the columns of
+# z outside the slice hold depths in [1.5, 2.5], which no sample has. Rays and depths: the recipe of FUSED_CASES (DIR_GAP; ray 0 from
+# the origin along +x; the last depth 0, the middle one negative). 1 row; 33 rows with ray boundaries at lanes 11 and 22 of a wave;
+# 5 rays of 16 = the split kernel's two rays per 32-point workgroup, 2 1/2 workgroups; 2 rays of 64 = one 128-point workgroup;
+# 129 rows at scale 1.5 with the ray changing every 43 lanes; a work list of 77 of 200 rows, not ascending. Weight state "init".
+SDF_VALUE_RAY_CASES = {
+    "value-rays-1x1-s1": (1, 1, 1.0, None, (3, 1), (4, 2)),
+    "value-rays-3x11-s1": (3, 11, 1.0, None, (16, 3), (13, 2)),
+    "value-rays-5x16-s1": (5, 16, 1.0, None, (24, 5), (20, 3)),
+    "value-rays-2x64-s1": (2, 64, 1.0, None, (80, 9), (72, 4)),
+    "value-rays-3x43-s1.5": (3, 43, 1.5, None, (50, 6), (47, 1)),
+    "value-rays-worklist-8x25-n77-s1": (8, 25, 1.0, 77, (32, 4), (29, 3)),
+}
+# The large kernel (the entry point routes on P > 8192), name: (P, n_active): 64 workgroups of 128 points and one row; a work list
+# of 77 rows, not ascending, in P = 8200. Point i is point i % 300 of SDF_VALUE_TILE: only 300 rows need a model, and every
+# repetition must carry the same bits.
+SDF_VALUE_LARGE_CASES = {"value-tiled-P8193-s1.5": (8193, None), "value-tiled-worklist-P8200-n77-s1.5": (8200, 77)}
+SDF_VALUE_TILE = "uniform-P300-s1.5"
+SDF_VALUE_CASES = tuple(SDF_CASES) + tuple(SDF_VALUE_RAY_CASES) + tuple(SDF_VALUE_LARGE_CASES)
+Z_GAP_FILL = (1.5, 2.5)
+# cold_start = 1: the prologue only reads ahead in launches whose first round has at least 128 workgroups (csrc/vdn_common.h:
+# warm_l2_issue), so these are the smallest shapes that run it - 129 workgroups of the split kernel (32 points each, P <= 8192) and
+# of the 128-point kernels, on tiled points and in ray form (65 and 257 rays of 64). They are compared with cold_start = 0 only
+# (and, tiled, with the 300-row case); not part of SDF_VALUE_CASES.
+SDF_COLD_TILED_CASES = {"cold-tiled-P4097-s1.5": (4097, None), "cold-tiled-P16385-s1.5": (16385, None)}
+SDF_COLD_RAY_CASES = {"cold-rays-65x64-s1": (65, 64, 1.0, None, (80, 9), (72, 4)), "cold-rays-257x64-s1": (257, 64, 1.0, None, (80, 9), (72, 4))}
+
+
+def sdf_value_case(name):
+    """A case of SDF_VALUE_CASES. "form" = "pts" (sdf_case's keys; "tile" = the period of a large case's points) or "rays" (the
+    ray keys of fused_case, and z_wide [B, z_ld] with z = z_wide[:, z_col0 : z_col0 + n_per_ray], z_ld, z_col0, sdf_ld, sdf_col0)."""
+    if name in SDF_CASES:
+        return dict(sdf_case(name), form="pts", tile=None)
+    if name in SDF_VALUE_LARGE_CASES or name in SDF_COLD_TILED_CASES:
+        P, n_active = SDF_VALUE_LARGE_CASES[name] if name in SDF_VALUE_LARGE_CASES else SDF_COLD_TILED_CASES[name]
+        t = sdf_case(SDF_VALUE_TILE)
+        c = {"name": name, "form": "pts", "tile": t["P"], "P": P, "scale": t["scale"], "pts": t["pts"][np.arange(P) % t["P"]].copy(),
+             "active_idx": None, "n_active": None, "state": t["state"]}
+        if n_active is not None:
+            order = np.argsort(synth.uniform(SEED, "mlp/%s/order" % name, (P,)))
+            idx = np.full(P, -1, np.int32)
+            idx[:n_active] = order[:n_active]
+            c["active_idx"], c["n_active"] = idx, n_active
+        return c
+    B, n, scale, n_active, (z_ld, z_col0), (sdf_ld, sdf_col0) = SDF_VALUE_RAY_CASES[name] if name in SDF_VALUE_RAY_CASES else SDF_COLD_RAY_CASES[name]
+    c = _ray_case(name, B, n, scale, n_active, "init")
+    lo, hi = Z_GAP_FILL
+    z_wide = (lo + (hi - lo) * synth.uniform(SEED, "mlp/%s/z_gap" % name, (B, z_ld))).astype(np.float32)
+    z_wide[:, z_col0:z_col0 + n] = c["z"]
+    c.update(form="rays", tile=None, z_wide=z_wide, z_ld=z_ld, z_col0=z_col0, sdf_ld=sdf_ld, sdf_col0=sdf_col0)
+    del c["squeeze"]
+    return c
+
+
+def value_points_of(c):
+    """The float32 points of every dense point id of a case of SDF_VALUE_CASES (ray form: o + d z, as fused_points_of)."""
+    return c["pts"] if c["form"] == "pts" else fused_points_of(c)
+
+
+def value_rows_of(c):
+    """The dense point ids behind the rows of the saved planes: the listed ones in list order, or all."""
+    return fused_rows_of(c)
+
+
+# The tail hand-off (VdnSdfArgs.tail_row0 / tail_max_rows; csrc/k_sdf_fwd2.h MODE 1 against csrc/k_sdf_fwd1_split.h):
+# (tail_row0, tail_max_rows, n_rows) - the tail idle (the list ends AT tail_row0), one row and 172 rows handed off, the second
+# workgroup boundary, a list that ends beyond the window (the main kernel keeps every row). "dense": the first n_rows points of
+# SDF_VALUE_TILE, P = n_rows; "list": 400 uniform points at scale 1 with a work list of n_rows rows, not ascending, whose
+# count the kernels read on the device.
+SDF_TAIL_SPLITS = ((128, 256, 128), (128, 256, 129), (128, 256, 300), (256, 256, 300), (128, 128, 300))
+SDF_TAIL_LIST_P = 400
+
+
+def sdf_tail_case(kind, n_rows):
+    if kind == "dense":
+        t = sdf_case(SDF_VALUE_TILE)
+        return {"name": "tail-dense-n%d" % n_rows, "form": "pts", "tile": None, "P": n_rows, "scale": t["scale"], "pts": t["pts"][:n_rows].copy(),
+                "active_idx": None, "n_active": None, "state": t["state"]}
+    P = SDF_TAIL_LIST_P
+    pts = (2.2 * synth.uniform(SEED, "mlp/tail-list/pts", (P, 3)) - 1.1).astype(np.float32)
+    order = np.argsort(synth.uniform(SEED, "mlp/tail-list/order", (P,)))
+    idx = np.full(P, -1, np.int32)
+    idx[:n_rows] = order[:n_rows]
+    return {"name": "tail-list-n%d" % n_rows, "form": "pts", "tile": None, "P": P, "scale": 1.0, "pts": pts, "active_idx": idx,
+            "n_active": n_rows, "state": "init"}
+
+
+def handed_off(tail_row0, tail_max_rows, n_rows):
+    """Whether the rows from tail_row0 on are the tail launch's (include/vdn_render.h: VdnSdfArgs.tail_row0)."""
+    return tail_max_rows > 0 and n_rows > tail_row0 and n_rows - tail_row0 <= tail_max_rows
 
 
 # MODE 2 (vdn_shade_fused_bf16), name: (rays, T). One workgroup is one ray of 128 samples; T = 160 brings the background inputs

@@ -337,9 +337,10 @@ def pe_jacobian_T(pts, scale, U, dtype=torch.float64, n_freqs=6, trig=HW_TRIG):
     return {"y": (n * torch.tensor(sc, dtype=dtype)).double().numpy(), "mag": mag.numpy() * sc, "extra": terr.numpy() * sc}
 
 
-def sdf_sweep_models(ops_sweep, w8row, pts, scale, planes):
+def sdf_sweep_models(ops_sweep, w8row, pts, scale, planes, pts_err=None):
     """{plane: dict(y64, y32, unit, extra, stored)} of V7..V0, U_pe and normals, each from the saved planes before it:
-    V[l] from V[l+1] and H[l]; U_pe from V[0] and V[4]; normals from the launch's own U_pe. ops_sweep[l] = the image of W_l^T."""
+    V[l] from V[l+1] and H[l]; U_pe from V[0] and V[4]; normals from the launch's own U_pe. ops_sweep[l] = the image of W_l^T.
+    pts_err: see sdf_plane_models (the normal moves by at most scale^2 sum_k 4^k (|u_sin| + |u_cos|) per unit of the point)."""
     out = {}
     pe_part = {}
     for l in range(7, -1, -1):
@@ -365,7 +366,11 @@ def sdf_sweep_models(ops_sweep, w8row, pts, scale, planes):
         y64, mag = y[torch.float64]
         out["U_pe"] = dict(y64=y64, y32=y[torch.float32][0], unit=U24 * (mag + np.abs(y64)), extra=2.0 ** -8 * mag, stored="f32")
         n64, n32 = (pe_jacobian_T(pts, scale, planes["U_pe"], dt) for dt in (torch.float64, torch.float32))
-        out["normals"] = dict(y64=n64["y"], y32=n32["y"], unit=U24 * 3.0 * n64["mag"], extra=n64["extra"], stored="f32")
+        n_extra = n64["extra"]
+        if pts_err is not None:
+            au = np.abs(np.asarray(planes["U_pe"], np.float64))
+            n_extra = n_extra + float(scale) ** 2 * pts_err * sum(4.0 ** k * (au[:, 3 + 6 * k:6 + 6 * k] + au[:, 6 + 6 * k:9 + 6 * k]) for k in range(6))
+        out["normals"] = dict(y64=n64["y"], y32=n32["y"], unit=U24 * 3.0 * n64["mag"], extra=n_extra, stored="f32")
     return out
 
 
@@ -1076,12 +1081,28 @@ def sdf_sweep_ops(img, rounded=True):
     return [operand_weights(img, "full", sweep_stream_layer(l), rounded) for l in range(8)]
 
 
-def sdf_plane_models(ops, pts, scale, planes, ops_sweep=None):
+def ray_points(rays_o, rays_d, z, rows):
+    """The points o + d z of the dense point ids `rows` (ray * n_per_ray + sample) in float64, and pts_err [n,3]: how far the
+    launch's float32 point may lie from them - the product d z and the sum are one rounding each, or one fused rounding:
+    2^-24 (|d z| + |o + d z|) <= 2^-24 (|o| + 2 |d z|) - for sdf_plane_models."""
+    o, d, zz = (np.asarray(a, np.float64) for a in (rays_o, rays_d, z))
+    r, s = np.asarray(rows) // zz.shape[1], np.asarray(rows) % zz.shape[1]
+    dz = d[r] * zz[r, s][:, None]
+    return o[r] + dz, U24 * (np.abs(o[r]) + 2.0 * np.abs(dz))
+
+
+def sdf_plane_models(ops, pts, scale, planes, ops_sweep=None, pts_err=None):
     """{plane: dict(y64, y32, unit, extra, stored)} of one launch, each from the saved planes before it (`planes`: PE [P,39],
-    H0..H7 [P,256] as the launch left them, float64 numpy): PE, H0..H7 (H3: 217 columns), feat, sdf."""
+    H0..H7 [P,256] as the launch left them, float64 numpy): PE, H0..H7 (H3: 217 columns), feat, sdf.
+    pts_err [P,3] (the ray form: ray_points): the launch forms its point itself, within pts_err of `pts`; column (d, octave k) of
+    the encoding then moves by at most C scale 2^k |d column / d arg| pts_err_d, which joins the extra term of PE and, through
+    e_pe, of the residue slots of layers 0 and 4 (and of the normals)."""
     out = {}
     pe64, pe32 = posenc_scaled(pts, scale, torch.float64), posenc_scaled(pts, scale, torch.float32)
     unit, extra = posenc_units(pe64)
+    if pts_err is not None:
+        freq = np.concatenate([np.ones(3)] + [np.full(6, 2.0 ** k) for k in range(6)])
+        extra = extra + C * float(scale) * freq * pe64["deriv"] * np.tile(np.asarray(pts_err, np.float64), (1, 13))
     out["PE"] = dict(y64=pe64["y"], y32=pe32["y"], unit=unit, extra=extra, stored="bf16")
     e_pe = max(1.0, 3.0 * _ratio(np.abs(pe32["y"] - pe64["y"]), unit)) * unit + extra
     for l in range(8):
@@ -1098,7 +1119,7 @@ def sdf_plane_models(ops, pts, scale, planes, ops_sweep=None):
     out["feat"] = dict(y64=l64["feat"], y32=l32["feat"], unit=fu, extra=0.0, stored="bf16")
     out["sdf"] = dict(y64=l64["sdf"], y32=l32["sdf"], unit=su, extra=se, stored="f32")
     if ops_sweep is not None:
-        out.update(sdf_sweep_models(ops_sweep, ops[8]["tail"], pts, scale, planes))
+        out.update(sdf_sweep_models(ops_sweep, ops[8]["tail"], pts, scale, planes, pts_err))
     return out
 
 

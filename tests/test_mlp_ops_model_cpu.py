@@ -5,7 +5,9 @@ models on unrounded weight images, fed their own unrounded outputs in float64, A
 every range switch; the comparator accepts a float32 evaluation rounded to bf16 either way and rejects it with each planted
 structural error, in every case, at the plane the error is in and at no other; a pre-activation that is exactly zero admits
 nothing but an exact zero; the chunk decoder inverts the documented layout. The float32 floors of every (case, plane) are printed
-(pytest -rA)."""
+(pytest -rA). For the launches that save no planes (tests/test_gpu_sdf_value_launches.py, held bit for bit): the cases reach what
+they claim, the "sdf" stream holds the first nine layers of "full", every planted ray / column / stride / weight / scale defect
+moves the sdf of every row, and the ray-form models (pts_err) accept either way of forming the point and reject those defects."""
 import functools
 import math
 
@@ -318,6 +320,201 @@ def test_the_other_weight_state_is_rejected():
     # init's constant sqrt(pi) / 16 in both states)
     free = ("PE", "normals", "sdf", "V7")
     assert res["PE"]["ok"] and res["normals"]["ok"] and all(not res[k]["ok"] for k in res if k not in free)
+
+
+# ---- the launches that save no planes (tests/test_gpu_sdf_value_launches.py): cases, premise, the ray form's anchor --------------------
+# Those launches are held to the training launch bit for bit, so the comparator is torch.equal; what has to be proven here is that
+# the cases reach what they claim, that the two streams hold the same network, that a wrong ray, column or stride moves the sdf of
+# EVERY row by more than the last-layer model's whole allowance (so by far more than a bit), and that the models with which the GPU
+# test holds the ray-form TRAINING launch - the anchor of the ray cases - accept either way of forming the point and reject each
+# planted defect at the PE plane.
+
+RAY_NAMES = list(mlp_cases.SDF_VALUE_RAY_CASES)
+
+
+def test_sdf_value_cases_reach_what_they_claim():
+    assert set(mlp_cases.SDF_VALUE_CASES) == set(mlp_cases.SDF_CASES) | set(RAY_NAMES) | set(mlp_cases.SDF_VALUE_LARGE_CASES)
+    for n in mlp_cases.SDF_CASES:                            # the pts form: SDF_CASES as they are
+        a, b = mlp_cases.sdf_case(n), mlp_cases.sdf_value_case(n)
+        assert b["form"] == "pts" and all(np.array_equal(a[k], b[k]) for k in a)
+    cs = {n: mlp_cases.sdf_value_case(n) for n in RAY_NAMES}
+    assert [(c["B"], c["n_per_ray"]) for c in cs.values()] == [(1, 1), (3, 11), (5, 16), (2, 64), (3, 43), (8, 25)]
+    assert cs["value-rays-3x43-s1.5"]["scale"] == 1.5 and cs["value-rays-3x43-s1.5"]["P"] == 129
+    assert cs["value-rays-5x16-s1"]["P"] == 2 * 32 + 16      # the split kernel's two rays per workgroup, 2 1/2 workgroups
+    for n, c in cs.items():
+        B, k = c["B"], c["n_per_ray"]
+        assert c["form"] == "rays" and "pts" not in c and c["state"] == "init"
+        assert c["z_ld"] > k and c["sdf_ld"] > k and c["sdf_ld"] != c["z_ld"], n
+        assert 0 < c["z_col0"] <= c["z_ld"] - k and 0 < c["sdf_col0"] <= c["sdf_ld"] - k, n
+        assert c["z_wide"].shape == (B, c["z_ld"]) and c["z_wide"].dtype == np.float32
+        assert np.array_equal(c["z_wide"][:, c["z_col0"]:c["z_col0"] + k], c["z"])
+        gap = np.ones(c["z_ld"], bool)
+        gap[c["z_col0"]:c["z_col0"] + k] = False
+        assert gap.sum() == c["z_ld"] - k > 0                # non-empty, and no depth of the slice is a depth of the gap
+        assert c["z_wide"][:, gap].min() >= mlp_cases.Z_GAP_FILL[0] > 1.0 >= c["z"].max()
+        assert (c["rays_o"][0] == 0).all() and (c["rays_d"][0] == (1.0, 0.0, 0.0)).all(), n
+        if B > 1:
+            assert np.abs(np.diff(c["rays_d"], axis=0)).min() >= mlp_cases.DIR_GAP > 4 * 2.0 ** -7, n
+        if c["P"] >= 3:
+            assert (c["z"] == 0).sum() == 1 and (c["z"] < 0).sum() == 1, n
+    assert all(32 % cs[n]["n_per_ray"] for n in ("value-rays-3x11-s1", "value-rays-3x43-s1.5", "value-rays-worklist-8x25-n77-s1"))   # ray boundaries inside a wave
+    w = cs["value-rays-worklist-8x25-n77-s1"]
+    idx = w["active_idx"][:77]
+    assert w["P"] == 200 and len(set(idx.tolist())) == 77 and (np.diff(idx) < 0).any() and (w["active_idx"][77:] == -1).all()
+    tile = mlp_cases.sdf_case(mlp_cases.SDF_VALUE_TILE)
+    for n, (P, n_active) in mlp_cases.SDF_VALUE_LARGE_CASES.items():
+        c = mlp_cases.sdf_value_case(n)
+        assert c["P"] == P > 8192 and c["tile"] == tile["P"] == 300 and c["scale"] == tile["scale"] and c["state"] == tile["state"]
+        assert np.array_equal(c["pts"], tile["pts"][np.arange(P) % 300])
+        if n_active is None:
+            assert P == 64 * 128 + 1
+        else:
+            idx = c["active_idx"][:n_active]
+            assert len(set(idx.tolist())) == n_active == 77 and (np.diff(idx) < 0).any() and (c["active_idx"][n_active:] == -1).all()
+            assert idx.max() >= 128 and len(set((idx % 300).tolist())) > 60       # beyond the first workgroup's points; many tile rows
+    # cold_start = 1 reads ahead only from 128 workgroups on: 129 of the split kernel's (P <= 8192), 129 of the 128-point kernels'
+    cold = {n: mlp_cases.sdf_value_case(n) for n in list(mlp_cases.SDF_COLD_TILED_CASES) + list(mlp_cases.SDF_COLD_RAY_CASES)}
+    assert sorted((c["P"] + 31) // 32 for c in cold.values() if c["P"] <= 8192) == [129, 130]
+    assert sorted((c["P"] + 127) // 128 for c in cold.values() if c["P"] > 8192) == [129, 129]
+    assert {c["form"] for c in cold.values() if c["P"] <= 8192} == {c["form"] for c in cold.values() if c["P"] > 8192} == {"pts", "rays"}
+    assert all(c["active_idx"] is None and c["tile"] == (300 if c["form"] == "pts" else None) for c in cold.values())
+    for r0, rmax, n in mlp_cases.SDF_TAIL_SPLITS:            # the hand-off's every branch, at both workgroup boundaries
+        assert r0 % 128 == 0 and n <= 300 < mlp_cases.SDF_TAIL_LIST_P
+    assert [mlp_cases.handed_off(*s) for s in mlp_cases.SDF_TAIL_SPLITS] == [False, True, True, True, False]
+    assert {s[0] for s in mlp_cases.SDF_TAIL_SPLITS if mlp_cases.handed_off(*s)} == {128, 256}
+    t = mlp_cases.sdf_tail_case("list", 300)
+    idx = t["active_idx"][:300]
+    assert len(set(idx.tolist())) == 300 and (np.diff(idx) < 0).any() and (t["active_idx"][300:] == -1).all()
+    assert np.array_equal(mlp_cases.sdf_tail_case("list", 129)["active_idx"][:129], idx[:129])
+    assert np.array_equal(mlp_cases.sdf_tail_case("dense", 129)["pts"], tile["pts"][:129])
+
+
+@pytest.mark.parametrize("state", ["init", "hot", "other"])
+def test_the_sdf_stream_holds_the_first_nine_layers_of_the_full_stream(state):
+    """The premise of mode 0 = mode 1 bit for bit, on the host: layers 0..7 of "sdf" are those of "full" (operand, bias, tail,
+    k-tiles, chunk count); layer 8 of "sdf" is one chunk whose row 0 is the sdf row - row 256 of "full"'s layer 8 - with the same
+    bias and tail, every other row zero."""
+    host = mlp_ops.HostImages.of_sdf_state(mlp_cases.states(state)["sdf_network_fine"], _streams())
+    assert len(host.streams["sdf"]) == 9 and len(host.streams["full"]) == 17
+    for l in range(8):
+        a, b = mlp_ops.operand_weights(host, "sdf", l), mlp_ops.operand_weights(host, "full", l)
+        assert a["kt"] == b["kt"] and a["n_chunks"] == b["n_chunks"]
+        assert all(np.array_equal(a[k], b[k]) for k in ("W", "b", "tail"))
+    a, b = mlp_ops.operand_weights(host, "sdf", 8), mlp_ops.operand_weights(host, "full", 8)
+    assert (a["n_chunks"], b["n_chunks"], a["kt"], b["kt"]) == (1, 9, 8, 8) and np.array_equal(a["tail"], b["tail"])
+    assert np.array_equal(a["W"][0], b["W"][256]) and a["b"][0] == b["b"][256] and not a["W"][1:].any() and not a["b"][1:].any()
+    assert a["W"][0].any() and a["b"][0] != 0
+
+
+SHOWS = 2.0 ** -20              # 16 float32 steps at 1: what a defect has to move a row's sdf by to count as shown (|sdf| < 1.1 here)
+
+
+def _value_sdf(c, pts, state="init"):
+    """The sdf of the network the blob holds (bf16 operand weights) in float64, nothing else rounded, at the given points: a
+    function of the point alone - the float32 stand-in's last bits depend on which rows share its matrix product."""
+    ops = _ops(state)
+    x = mlp_ops.posenc_scaled(pts, c["scale"])["y"]
+    g = None
+    for l in range(8):
+        g = mlp_ops.sdf_hidden(l, g, (x, x) if l in (0, 4) else None, ops[l]["W"], ops[l]["b"])["y"]
+    return mlp_ops.sdf_last(g, ops[8]["W"], ops[8]["b"], ops[8]["tail"], c["scale"])["sdf"]
+
+
+def _ray_pts(c, z, rows, o=None, d=None):
+    """o + d z in float32 (two roundings) at the dense point ids `rows`, z [B, n_per_ray]."""
+    o, d = c["rays_o"] if o is None else o, c["rays_d"] if d is None else d
+    r, s = rows // c["n_per_ray"], rows % c["n_per_ray"]
+    return (o[r] + (d[r] * z[r, s][:, None]).astype(np.float32)).astype(np.float32)
+
+
+def _value_defects(c):
+    """{defect: float32 points [rows, 3] a launch with that defect would evaluate}, in the rows of the list."""
+    rows = mlp_cases.value_rows_of(c)
+    B, n, col0 = c["B"], c["n_per_ray"], c["z_col0"]
+    flat = c["z_wide"].reshape(-1)
+    out = {"z_ld taken as n_per_ray": _ray_pts(c, flat[col0:col0 + B * n].reshape(B, n), rows),
+           "the column offset of z dropped": _ray_pts(c, c["z_wide"][:, :n], rows)}
+    if B > 1:
+        out["the neighbouring ray's z"] = _ray_pts(c, np.roll(c["z"], -1, axis=0), rows)
+        out["the neighbouring ray's origin and direction"] = _ray_pts(c, c["z"], rows, np.roll(c["rays_o"], -1, axis=0), np.roll(c["rays_d"], -1, axis=0))
+    if c["P"] > 1:
+        out["the neighbouring sample's z"] = _ray_pts(c, np.roll(c["z"].reshape(-1), -1).reshape(B, n), rows)
+    return out
+
+
+@pytest.mark.parametrize("name", RAY_NAMES)
+def test_value_ray_cases_show_a_wrong_ray_column_or_stride_in_every_row(name):
+    """The GPU test's comparator is bit equality, so a defect shows in a row as soon as that row's sdf moves at all. Here, on the
+    float64 network: each defect moves the point of EVERY row it can reach (with B = 1 there is no neighbouring ray; with z_ld
+    taken as n_per_ray ray 0 still reads its own depths, every later ray reads others) and its sdf by more than SHOWS; so do the
+    "other" weight state and, at scale 1.5, a missing 1 / scale; the share of rows moved beyond the last-layer model's whole
+    allowance (sdf_last + last_units: what a comparison through a model would have needed) is printed; and the positions
+    r sdf_ld + s of the outputs are not the dense ones."""
+    c = mlp_cases.sdf_value_case(name)
+    rows = mlp_cases.value_rows_of(c)
+    pts = mlp_cases.value_points_of(c)[rows]
+    sdf = _value_sdf(c, pts)
+    assert np.abs(sdf).max() < 1.1
+    planes = mlp_ops.simulate_sdf_forward(_ops(), pts, c["scale"])
+    m = mlp_ops.sdf_plane_models(_ops(), pts, c["scale"], planes)["sdf"]
+    allowance = 3.0 * m["unit"] + m["extra"]
+
+    def shows(other, sel, what):
+        d = np.abs(other - sdf)[sel]
+        print("%-34s %-45s moved by >= %.2e, %3.0f %% of the rows beyond the model's allowance" % (name, what, d.min(), 100 * (d > allowance[sel]).mean()))
+        assert d.size and (d > SHOWS).all(), (name, what, d.min())
+
+    defects = _value_defects(c)
+    assert len(defects) == (2 if c["P"] == 1 else 5)
+    for what, bad_pts in defects.items():
+        moved = np.abs(bad_pts - pts).max(1) > 0
+        sel = np.ones(len(rows), bool)
+        if what == "z_ld taken as n_per_ray":                # (ray 0 starts at the same column: it reads its own depths)
+            sel = rows // c["n_per_ray"] > 0
+            if c["B"] == 1:
+                continue
+        assert moved[sel].all() and not moved[~sel].any(), (name, what)
+        shows(_value_sdf(c, bad_pts), sel, what)
+    everywhere = np.ones(len(rows), bool)
+    shows(_value_sdf(c, pts, state="other"), everywhere, "the other weight state")
+    if c["scale"] != 1.0:
+        shows(sdf * c["scale"], everywhere, "1 / scale omitted")
+    r, s = rows // c["n_per_ray"], rows % c["n_per_ray"]
+    assert (r * c["sdf_ld"] + s + c["sdf_col0"] != rows).all()      # a dense write lands elsewhere in the wide, NaN-filled buffer
+
+
+def test_one_over_scale_and_the_other_state_show_in_every_row_of_the_point_cases():
+    for name in ("uniform-P33-s1.5", "uniform-P300-s1.5", "uniform-P129-s1"):
+        c = mlp_cases.sdf_case(name)
+        sdf = _value_sdf(c, c["pts"])
+        assert (np.abs(_value_sdf(c, c["pts"], state="other") - sdf) > SHOWS).all(), name
+        if c["scale"] != 1.0:
+            assert (np.abs(sdf * c["scale"] - sdf) > SHOWS).all(), name
+
+
+@pytest.mark.parametrize("name", RAY_NAMES)
+def test_ray_form_models_accept_either_point_and_reject_each_planted_defect(name):
+    """The anchor of the ray cases is the ray-form TRAINING launch, which the GPU test holds to sdf_plane_models at the float64
+    points o + d z with pts_err = ray_points' bound. Here: the stand-in passes at every plane whether it forms the point with two
+    roundings or with one (a fused multiply-add); with each planted defect the PE plane is rejected."""
+    c = mlp_cases.sdf_value_case(name)
+    rows = mlp_cases.value_rows_of(c)
+    p64, err = mlp_ops.ray_points(c["rays_o"], c["rays_d"], c["z"], rows)
+    assert err.shape == p64.shape and (err <= 2.0 ** -24 * 4.0).all()
+    two, one = _ray_pts(c, c["z"], rows), p64.astype(np.float32)
+    assert np.abs(two - p64).max() > 0 or c["P"] == 1
+    assert (np.abs(two - p64) <= err).all() and (np.abs(one - p64) <= err).all()
+    for pts in (two, one):
+        planes = mlp_ops.simulate_sdf_forward(_ops(), pts, c["scale"], ops_sweep=_sweep_ops())
+        res = mlp_ops.judge_planes(mlp_ops.sdf_plane_models(_ops(), p64, c["scale"], planes, _sweep_ops(), pts_err=err), planes)
+        assert all(j["ok"] for j in res.values()), (name, [k for k, j in res.items() if not j["ok"]])
+    for what, bad_pts in _value_defects(c).items():
+        if np.array_equal(bad_pts, two):                     # (one ray: its stride does not matter)
+            assert c["B"] == 1 and what == "z_ld taken as n_per_ray"
+            continue
+        planes = mlp_ops.simulate_sdf_forward(_ops(), bad_pts, c["scale"])
+        res = mlp_ops.judge_planes(mlp_ops.sdf_plane_models(_ops(), p64, c["scale"], planes, pts_err=err), planes)
+        assert not res["PE"]["ok"] and res["PE"]["err"] > 1e3, (name, what, res["PE"])
 
 
 # ---- the heads' forward -------------------------------------------------------------------------------------------------------
