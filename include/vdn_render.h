@@ -1249,6 +1249,80 @@ typedef struct {
 int vdn_cluster_quadrics(const VdnClusterQuadricArgs* args_host, void* stream);
 int vdn_cluster_place(const VdnClusterQuadricArgs* args_host, void* stream);
 
+/* ---- adaptive simplification: octree vertex clustering under an error bound (csrc/mesh_simplify.hip; vdn_hip/mesh.py: cluster_octree,
+ * select_octree, count_octree_faces, simplify_mesh(tolerance=..); restated in tests/test_mesh_octree_cpu.py) -------------
+ * Levels. Level 0 is the clustering above at cell size h0 from `origin`, cells i0 = floor((double(v) - origin) / h0). The level-l
+ * cell of a level-0 cell is i0 >> l per axis (an arithmetic shift: floor, also for negative indices), its edge h_l = h0 2^l, its
+ * centre origin + (i_l + 0.5) h_l: the cell floor((v - origin) / h_l), since scaling by a power of two is exact. The grid of level l
+ * covers lo_l = lo_0 >> l .. hi_l = hi_0 >> l per axis; its cells are numbered in ascending key
+ * (ix - lo_x) + nx ((iy - lo_y) + ny (iz - lo_z)), as at level 0. 1 <= levels <= 8.
+ * Node record, per level: quadric[10] and mean[3] relative to the node's own centre, count (the referenced vertices in it),
+ * position[3] = centre + x, status, error, trace. Level 0 takes quadric and mean from vdn_cluster_quadrics / vdn_segment_mean.
+ *   vdn_octree_merge:  one thread per node p of level l. Merge mode (children != NULL): the child in slot s = bx + 2 by + 4 bz is the
+ *                      cell 2 i_l + (bx, by, bz) of level l - 1, found by binary search of its key in child_key (ascending);
+ *                      children[p][s] = its index, -1 when absent. The present children are taken in ascending s, every sum starting
+ *                      from +0.0. With d = (bx ? q : -q, by ? q : -q, bz ? q : -q), q = 0.25 h (the child's centre minus the
+ *                      parent's) and (A, b, c), m, n the child's record:
+ *                          Ad_i = (A_i0 d0 + A_i1 d1) + A_i2 d2;   A' = A;   b'_i = b_i - Ad_i;
+ *                          c' = (c - 2 ((b0 d0 + b1 d1) + b2 d2)) + ((d0 Ad_0 + d1 Ad_1) + d2 Ad_2);
+ *                          quadric += (A', b', c');   count += n;   S_i += double(n) (m_i + d_i);
+ *                      mean_i = S_i / double(count). Measure mode (children == NULL): quadric and mean are inputs (level 0).
+ *                      Then, in both modes, place and measure: x and status are vdn_cluster_place's, by the same device function,
+ *                      called with this level's h and eps; with Ax_i = (A_i0 x0 + A_i1 x1) + A_i2 x2,
+ *                          e = (((x0 Ax_0 + x1 Ax_1) + x2 Ax_2) + 2 ((b0 x0 + b1 x1) + b2 x2)) + c;   error = e > 0 ? e : 0   (NaN -> 0)
+ *                          trace = (Axx + Ayy) + Azz.
+ *                      error / trace is the area-squared-weighted mean squared distance from x to the planes of the node's triangles.
+ *   vdn_octree_select: one thread per node of a level l >= 1: accept = trace > 0 and trace < inf and error < tolerance2 * trace
+ *                      (strict; tolerance2 = tolerance * tolerance, rounded once by the caller); solid = accept and every present
+ *                      child's child_solid byte is set. Level 0 is solid by definition (the caller fills ones).
+ *   vdn_octree_assign: one thread per level-0 cluster over the level-major concatenation of the levels (node g of level l has the
+ *                      global number level_start[l] + g): parent[n] = the global number of n's parent, -1 at the top; while the
+ *                      parent is solid, climb (at most `levels` times). Solidity is hereditary downwards, so this is the highest
+ *                      solid ancestor. level[c] = its level, node[c] = its number inside that level.
+ * All arithmetic is double, every product and sum rounded on its own. Status -10: C, Cc or N beyond 32-bit indexing. */
+typedef struct {
+    const int64_t* cell;           /* [C][3] this level's cell indices   (merge mode) */
+    const double* centre;          /* [C][3] */
+    const int64_t* child_key;      /* [Cc] the previous level's keys, ascending   (merge mode) */
+    const double* child_quadric;   /* [Cc][10]   (merge mode) */
+    const double* child_mean;      /* [Cc][3]   (merge mode) */
+    const int64_t* child_count;    /* [Cc]   (merge mode) */
+    int64_t* children;             /* [C][8] out, or NULL: measure mode */
+    double* quadric;               /* [C][10] out (merge mode), in (measure mode) */
+    double* mean;                  /* [C][3] out (merge mode), in (measure mode) */
+    int64_t* count;                /* [C] out   (merge mode) */
+    double* position;              /* [C][3] out */
+    uint8_t* status;               /* [C] out */
+    double* error;                 /* [C] out */
+    double* trace;                 /* [C] out */
+    int64_t C, Cc;
+    int64_t lo_x, lo_y, lo_z, nx, ny, nz;   /* the previous level's grid   (merge mode) */
+    double h, eps;                 /* this level's edge */
+} VdnOctreeMergeArgs;
+int vdn_octree_merge(const VdnOctreeMergeArgs* args_host, void* stream);
+
+typedef struct {
+    const double* error;           /* [C] */
+    const double* trace;           /* [C] */
+    const int64_t* children;       /* [C][8] indices into the previous level, -1: absent */
+    const uint8_t* child_solid;    /* [Cc] */
+    uint8_t* solid;                /* [C] out */
+    int64_t C, Cc;
+    double tolerance2;
+} VdnOctreeSelectArgs;
+int vdn_octree_select(const VdnOctreeSelectArgs* args_host, void* stream);
+
+typedef struct {
+    const int64_t* parent;         /* [N] global numbers, -1 at the top */
+    const uint8_t* solid;          /* [N] */
+    const int64_t* level_start;    /* [levels + 2] ascending, level_start[0] = 0, level_start[levels + 1] = N */
+    uint8_t* level;                /* [C0] out */
+    int64_t* node;                 /* [C0] out */
+    int64_t C0, N;
+    int32_t levels, _pad;
+} VdnOctreeAssignArgs;
+int vdn_octree_assign(const VdnOctreeAssignArgs* args_host, void* stream);
+
 /* ---- textured meshes: a per-face atlas baked on the device (csrc/mesh_texture.hip; vdn_hip/mesh.py: texel_points, project_step,
  * gather_atlas, sample_texture, bake_texture) -----------------------------------------------------------------------
  * The atlas is S x S texels, uint8 RGB, row 0 at the top, cut into C x C square cells of n x n texels, C = S / n (integer), n >= 4;

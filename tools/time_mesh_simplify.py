@@ -8,6 +8,14 @@ wall time of the whole call (host clock, device synchronised: every launch, ever
 host reads - what a caller waits for) as the median of --repeats calls after one warm-up call, for quadric and for mean placement and
 for the count-only pass a face budget is searched with; and from one more, instrumented call of the quadric arm the device time of
 every kernel launch and of every torch.sort / torch.unique call between device events, with the sorts' share of the whole.
+--adaptive adds one leg on the same surface: the adaptive call (--adaptive-cell-size, --levels, --tolerance) against
+the uniform call at that cell size, its parts as calls of their own - the level-0 stages (cluster_quadrics), the whole tree
+(cluster_octree: the merges are the difference), select and assign (select_octree), one count pass (count_octree_faces), the call
+on a built tree (select, records, emit) - the instrumented stages of one adaptive call, and one target_faces search at half the
+uniform call's faces (vdn_train.mesh_simplify):
+
+    python tools/time_mesh_simplify.py --cell-sizes --adaptive --out profiles/mesh_simplify_adaptive.json
+
 Prints one JSON line."""
 import argparse
 import json
@@ -27,6 +35,10 @@ def main():
     ap.add_argument("--resolution", type=int, default=512)
     ap.add_argument("--cell-sizes", type=float, nargs="*", default=[2.0, 4.0], help="in lattice spacings")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--adaptive", action="store_true", help="add the adaptive leg")
+    ap.add_argument("--adaptive-cell-size", type=float, default=1.0, help="the adaptive leg's finest cell, in lattice spacings")
+    ap.add_argument("--levels", type=int, default=3)
+    ap.add_argument("--tolerance", type=float, default=0.05, help="in lattice spacings")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -93,11 +105,36 @@ def main():
         rows.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
         del res
+    adaptive = None
+    if a.adaptive:
+        from vdn_train import mesh_simplify
+        h0, L, tol = a.adaptive_cell_size, a.levels, a.tolerance
+        kw = {"tolerance": tol, "levels": L}
+        res, uni = mesh.simplify_mesh(v, t, h0, **kw), mesh.simplify_mesh(v, t, h0)
+        tree = mesh.cluster_octree(v, t, h0, L)
+        budget = uni["report"]["faces_out"] // 2
+        adaptive = {"cell_size": h0, "levels": L, "tolerance": tol, "report": res["report"], "uniform_report": uni["report"],
+                    "nodes_in_tree_per_level": [int(x["cell"].shape[0]) for x in tree["levels"]],
+                    "adaptive": median_wall(lambda: mesh.simplify_mesh(v, t, h0, **kw)),
+                    "uniform_at_cell_size": median_wall(lambda: mesh.simplify_mesh(v, t, h0)),
+                    "level0_stages": median_wall(lambda: mesh.cluster_quadrics(v, t, h0)),
+                    "tree": median_wall(lambda: mesh.cluster_octree(v, t, h0, L)),
+                    "select_assign": median_wall(lambda: mesh.select_octree(tree, tol)),
+                    "count_pass": median_wall(lambda: mesh.count_octree_faces(tree, tol)),
+                    "emit_on_built_tree": median_wall(lambda: mesh.simplify_mesh(v, t, h0, tree=tree, **kw)),
+                    "adaptive_stages": stages(lambda: mesh.simplify_mesh(v, t, h0, **kw))}
+        del res, uni
+        search_s, found = wall(lambda: mesh_simplify.simplify_mesh(v, t, cell_size=h0, levels=L, target_faces=budget))
+        adaptive["target_search"] = {"target_faces": budget, "wall_ms_one_call": 1e3 * search_s, "count_passes": len(found["report"]["tried"]),
+                                     "tolerance_found": found["report"]["tolerance"], "faces_out": found["report"]["faces_out"]}
+        print(json.dumps(adaptive), file=sys.stderr, flush=True)
     out = {"device": torch.cuda.get_device_name(0), "host_cpus": os.cpu_count(),
            "timer": "wall: host clock around the call, device synchronised, median of %d calls after one warm-up; stages: device events around "
                     "each launch and each torch.sort / torch.unique in one further call (torch.unique sorts inside)" % a.repeats,
            "scene": "marching_cubes of a rippled sphere on a %d^3 lattice, lattice-index coordinates, fp32" % R,
            "vertices": int(v.shape[0]), "triangles": int(t.shape[0]), "rows": rows}
+    if adaptive is not None:
+        out["adaptive"] = adaptive
     line = json.dumps(out)
     print(line, flush=True)
     if a.out:

@@ -1,9 +1,10 @@
-// Mesh simplification on the device (include/vdn_render.h: vdn_simplify_*, vdn_segment_mean, vdn_cluster_*): vertex clustering on a
+// Mesh simplification on the device (include/vdn_render.h: vdn_simplify_*, vdn_segment_mean, vdn_cluster_*, vdn_octree_*): vertex clustering on a
 // uniform grid with quadric error placement (vdn_hip/mesh.py: cluster_quadrics, simplify_mesh). A mark pass and a key
 // pass per triangle / vertex, the corner records per triangle, then two segmented sums - a wave per cluster, lanes striding the
 // cluster's list, a fixed-order tree across the lanes - and one thread per cluster for the 3 x 3 solve. All arithmetic is double on
 // the widened fp32 vertices; the file is built with -ffp-contract=off, so every product and sum rounds on its own and a numpy model
-// can follow the sums to the bit. No float atomics, no LDS.
+// can follow the sums to the bit. No float atomics, no LDS. The octree levels of the adaptive mode follow below the
+// placement they share: a thread per node merges its children's records, a thread per node decides, a thread per finest cluster climbs.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <climits>
@@ -136,38 +137,142 @@ __global__ void cluster_quadrics_kernel(VdnClusterQuadricArgs a) {
     }
 }
 
+// the placement of vdn_cluster_place and of every octree level (include/vdn_render.h): x relative to the cell centre -> status
+__device__ inline int place_quadric(const double* q, const double* m, double h, double eps, double* x) {
+    x[0] = m[0]; x[1] = m[1]; x[2] = m[2];
+    const double tr = (q[0] + q[3]) + q[5];
+    if (!(tr > 0.0 && tr < INFINITY)) return 1;
+    const double r = eps * tr;
+    const double A00 = q[0] + r, A01 = q[1], A02 = q[2], A11 = q[3] + r, A12 = q[4], A22 = q[5] + r;
+    const double g0 = -q[6] - ((q[0] * m[0] + q[1] * m[1]) + q[2] * m[2]);
+    const double g1 = -q[7] - ((q[1] * m[0] + q[3] * m[1]) + q[4] * m[2]);
+    const double g2 = -q[8] - ((q[2] * m[0] + q[4] * m[1]) + q[5] * m[2]);
+    // the inverse of the symmetric matrix by cofactors
+    const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
+    const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
+    const double det = (A00 * c00 + A01 * c01) + A02 * c02;
+    const double y[3] = {m[0] + ((c00 * g0 + c01 * g1) + c02 * g2) / det, m[1] + ((c01 * g0 + c11 * g1) + c12 * g2) / det,
+                         m[2] + ((c02 * g0 + c12 * g1) + c22 * g2) / det};
+    const double half = 0.5 * h;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ok = ok && fabs(y[k]) <= half;          // (NaN fails the comparison)
+    if (!ok) return 2;
+    x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
+    return 0;
+}
+
 __global__ void cluster_place_kernel(VdnClusterQuadricArgs a) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long s = (long)blockIdx.x * blockDim.x + threadIdx.x; s < (long)a.C; s += stride) {
-        const double* q = a.quadric + s * 10;
         const double m[3] = {a.mean[s * 3 + 0], a.mean[s * 3 + 1], a.mean[s * 3 + 2]};
-        double x[3] = {m[0], m[1], m[2]};
-        int status = 0;
-        const double tr = (q[0] + q[3]) + q[5];
-        if (!(tr > 0.0 && tr < INFINITY)) {
-            status = 1;
-        } else {
-            const double r = a.eps * tr;
-            const double A00 = q[0] + r, A01 = q[1], A02 = q[2], A11 = q[3] + r, A12 = q[4], A22 = q[5] + r;
-            const double g0 = -q[6] - ((q[0] * m[0] + q[1] * m[1]) + q[2] * m[2]);
-            const double g1 = -q[7] - ((q[1] * m[0] + q[3] * m[1]) + q[4] * m[2]);
-            const double g2 = -q[8] - ((q[2] * m[0] + q[4] * m[1]) + q[5] * m[2]);
-            // the inverse of the symmetric matrix by cofactors
-            const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
-            const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
-            const double det = (A00 * c00 + A01 * c01) + A02 * c02;
-            const double y[3] = {m[0] + ((c00 * g0 + c01 * g1) + c02 * g2) / det, m[1] + ((c01 * g0 + c11 * g1) + c12 * g2) / det,
-                                 m[2] + ((c02 * g0 + c12 * g1) + c22 * g2) / det};
-            const double half = 0.5 * a.h;
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ok = ok && fabs(y[k]) <= half;          // (NaN fails the comparison)
-            if (ok) { x[0] = y[0]; x[1] = y[1]; x[2] = y[2]; }
-            else status = 2;
-        }
+        double x[3];
+        const int status = place_quadric(a.quadric + s * 10, m, a.h, a.eps, x);
 #pragma unroll
         for (int k = 0; k < 3; ++k) a.position[s * 3 + k] = a.centre[s * 3 + k] + x[k];
         a.status[s] = (uint8_t)status;
+    }
+}
+
+// ---- octree levels (include/vdn_render.h: vdn_octree_*) ----------------------------------------------------------------
+// the index of `key` in the ascending keys[0 .. n), or -1
+__device__ inline long find_key(const int64_t* keys, long n, long key) {
+    long lo = 0, hi = n;
+    while (lo < hi) {
+        const long mid = lo + ((hi - lo) >> 1);
+        if ((long)keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < n && (long)keys[lo] == key) ? lo : -1;
+}
+
+__global__ void octree_merge_kernel(VdnOctreeMergeArgs a) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < (long)a.C; p += stride) {
+        double q[10], m[3];
+        if (a.children != nullptr) {
+            double S[3] = {0.0, 0.0, 0.0};
+            long n = 0;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) q[k] = 0.0;
+            const long i[3] = {(long)a.cell[p * 3 + 0], (long)a.cell[p * 3 + 1], (long)a.cell[p * 3 + 2]};
+            const double quarter = 0.25 * a.h;
+            for (int s = 0; s < 8; ++s) {
+                const int bit[3] = {s & 1, (s >> 1) & 1, (s >> 2) & 1};
+                const long rx = 2 * i[0] + bit[0] - (long)a.lo_x, ry = 2 * i[1] + bit[1] - (long)a.lo_y, rz = 2 * i[2] + bit[2] - (long)a.lo_z;
+                long c = -1;
+                if (rx >= 0 && rx < (long)a.nx && ry >= 0 && ry < (long)a.ny && rz >= 0 && rz < (long)a.nz)
+                    c = find_key(a.child_key, (long)a.Cc, rx + (long)a.nx * (ry + (long)a.ny * rz));
+                a.children[p * 8 + s] = c;
+                if (c < 0) continue;
+                const double* cq = a.child_quadric + c * 10;
+                const double* cm = a.child_mean + c * 3;
+                const double d[3] = {bit[0] ? quarter : -quarter, bit[1] ? quarter : -quarter, bit[2] ? quarter : -quarter};
+                const double Ad0 = (cq[0] * d[0] + cq[1] * d[1]) + cq[2] * d[2];
+                const double Ad1 = (cq[1] * d[0] + cq[3] * d[1]) + cq[4] * d[2];
+                const double Ad2 = (cq[2] * d[0] + cq[4] * d[1]) + cq[5] * d[2];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) q[k] += cq[k];
+                q[6] += cq[6] - Ad0; q[7] += cq[7] - Ad1; q[8] += cq[8] - Ad2;
+                q[9] += (cq[9] - 2.0 * ((cq[6] * d[0] + cq[7] * d[1]) + cq[8] * d[2])) + ((d[0] * Ad0 + d[1] * Ad1) + d[2] * Ad2);
+                const long nc = (long)a.child_count[c];
+                n += nc;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) S[k] += (double)nc * (cm[k] + d[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) m[k] = S[k] / (double)n;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) a.quadric[p * 10 + k] = q[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.mean[p * 3 + k] = m[k];
+            a.count[p] = n;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) q[k] = a.quadric[p * 10 + k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) m[k] = a.mean[p * 3 + k];
+        }
+        double x[3];
+        const int status = place_quadric(q, m, a.h, a.eps, x);
+        const double Ax0 = (q[0] * x[0] + q[1] * x[1]) + q[2] * x[2];
+        const double Ax1 = (q[1] * x[0] + q[3] * x[1]) + q[4] * x[2];
+        const double Ax2 = (q[2] * x[0] + q[4] * x[1]) + q[5] * x[2];
+        const double e = (((x[0] * Ax0 + x[1] * Ax1) + x[2] * Ax2) + 2.0 * ((q[6] * x[0] + q[7] * x[1]) + q[8] * x[2])) + q[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.position[p * 3 + k] = a.centre[p * 3 + k] + x[k];
+        a.status[p] = (uint8_t)status;
+        a.error[p] = e > 0.0 ? e : 0.0;                                   // (NaN fails the comparison)
+        a.trace[p] = (q[0] + q[3]) + q[5];
+    }
+}
+
+__global__ void octree_select_kernel(VdnOctreeSelectArgs a) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < (long)a.C; p += stride) {
+        const double tr = a.trace[p];
+        bool solid = tr > 0.0 && tr < INFINITY && a.error[p] < a.tolerance2 * tr;
+        for (int s = 0; s < 8; ++s) {
+            const long c = (long)a.children[p * 8 + s];
+            if (c >= 0 && c < (long)a.Cc && a.child_solid[c] == 0) solid = false;
+        }
+        a.solid[p] = solid ? 1 : 0;
+    }
+}
+
+__global__ void octree_assign_kernel(VdnOctreeAssignArgs a) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < (long)a.C0; c += stride) {
+        long n = c;
+        int level = 0;
+        while (level < a.levels) {
+            const long up = (long)a.parent[n];
+            if (up < 0 || up >= (long)a.N || a.solid[up] == 0) break;
+            n = up;
+            ++level;
+        }
+        a.level[c] = (uint8_t)level;
+        a.node[c] = n - (long)a.level_start[level];
     }
 }
 
@@ -247,5 +352,33 @@ extern "C" int vdn_cluster_place(const VdnClusterQuadricArgs* a, void* stream) {
     if (rc != 0) return rc;
     if (a->mean == nullptr || a->position == nullptr || a->status == nullptr || !(a->h > 0.0) || !(a->eps > 0.0)) return -1;
     hipLaunchKernelGGL(vdn::cluster_place_kernel, dim3(grid_of(a->C)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_octree_merge(const VdnOctreeMergeArgs* a, void* stream) {
+    if (a == nullptr || a->centre == nullptr || a->quadric == nullptr || a->mean == nullptr || a->position == nullptr ||
+        a->status == nullptr || a->error == nullptr || a->trace == nullptr || a->C < 1 || !(a->h > 0.0) || !(a->eps > 0.0)) return -1;
+    if (a->children != nullptr &&
+        (a->cell == nullptr || a->child_key == nullptr || a->child_quadric == nullptr || a->child_mean == nullptr ||
+         a->child_count == nullptr || a->count == nullptr || a->Cc < 1 || a->nx < 1 || a->ny < 1 || a->nz < 1 ||
+         !((double)a->nx * (double)a->ny * (double)a->nz < 4611686018427387904.0))) return -1;
+    if (a->C > INT_MAX || a->Cc > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::octree_merge_kernel, dim3(grid_of(a->C)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_octree_select(const VdnOctreeSelectArgs* a, void* stream) {
+    if (a == nullptr || a->error == nullptr || a->trace == nullptr || a->children == nullptr || a->child_solid == nullptr ||
+        a->solid == nullptr || a->C < 1 || a->Cc < 1 || !(a->tolerance2 >= 0.0)) return -1;
+    if (a->C > INT_MAX || a->Cc > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::octree_select_kernel, dim3(grid_of(a->C)), dim3(256), 0, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int vdn_octree_assign(const VdnOctreeAssignArgs* a, void* stream) {
+    if (a == nullptr || a->parent == nullptr || a->solid == nullptr || a->level_start == nullptr || a->level == nullptr ||
+        a->node == nullptr || a->C0 < 1 || a->N < a->C0 || a->levels < 1 || a->levels > 8) return -1;
+    if (a->N > INT_MAX) return -10;
+    hipLaunchKernelGGL(vdn::octree_assign_kernel, dim3(grid_of(a->C0)), dim3(256), 0, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
 }

@@ -783,6 +783,29 @@ def _segments(ids, n_segments):
     return members, start
 
 
+def _records_stage(a, st, vertex_cluster, C, F, dev):
+    """Corner records of a vertex map (vdn_simplify_records; `a` holds the mesh and its live bytes) and the duplicate rule
+    -> (corner [3 F], survive [F] uint8, emit [F] bool)"""
+    corner = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    canonical = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    survive = torch.empty(F, dtype=torch.uint8, device=dev)
+    a.vertex_cluster, a.corner_cluster, a.canonical, a.survive, a.C = (vertex_cluster.data_ptr(), corner.data_ptr(), canonical.data_ptr(),
+                                                                         survive.data_ptr(), C)
+    _call_sized("vdn_simplify_records", a, st)
+    # the duplicate rule: among the survivors with one canonical triple the first in input order is emitted
+    idx = torch.nonzero(survive).reshape(-1)
+    emit = torch.zeros(F, dtype=torch.bool, device=dev)
+    if idx.numel() > 0:
+        tri = canonical[idx]
+        if C <= 1 << 21:
+            codes = (tri[:, 0] * C + tri[:, 1]) * C + tri[:, 2]
+        else:                                            # (three 31-bit ids do not fit one word: pair the first two, then the third)
+            pair = torch.unique(tri[:, 0] * C + tri[:, 1], return_inverse=True)[1]
+            codes = pair * C + tri[:, 2]
+        emit[idx[_first_of_each(codes, idx.numel())]] = True
+    return corner, survive, emit
+
+
 def _cluster_stage(name, vertices, triangles, cell_size, origin):
     """The part simplify_mesh, cluster_quadrics and count_simplified_faces share: mark, keys, clusters, corner records and the
     duplicate rule -> dict (None-valued arrays for an empty mesh). Two host reads."""
@@ -846,24 +869,9 @@ def _cluster_stage(name, vertices, triangles, cell_size, origin):
         C = int(uniq.shape[0])
         vertex_cluster = inv.contiguous()
         cell = torch.stack([uniq % dims[0] + i_lo[0], (uniq // dims[0]) % dims[1] + i_lo[1], uniq // (dims[0] * dims[1]) + i_lo[2]], dim=1)
-        corner = torch.empty(3 * F, dtype=torch.int64, device=dev)
-        canonical = torch.empty(F, 3, dtype=torch.int64, device=dev)
-        survive = torch.empty(F, dtype=torch.uint8, device=dev)
-        a.vertex_cluster, a.corner_cluster, a.canonical, a.survive, a.C = (vertex_cluster.data_ptr(), corner.data_ptr(), canonical.data_ptr(),
-                                                                             survive.data_ptr(), C)
-        _call_sized("vdn_simplify_records", a, st)
-        # the duplicate rule: among the survivors with one canonical triple the first in input order is emitted
-        idx = torch.nonzero(survive).reshape(-1)
-        emit = torch.zeros(F, dtype=torch.bool, device=dev)
-        if idx.numel() > 0:
-            tri = canonical[idx]
-            if C <= 1 << 21:
-                codes = (tri[:, 0] * C + tri[:, 1]) * C + tri[:, 2]
-            else:                                            # (three 31-bit ids do not fit one word: pair the first two, then the third)
-                pair = torch.unique(tri[:, 0] * C + tri[:, 1], return_inverse=True)[1]
-                codes = pair * C + tri[:, 2]
-            emit[idx[_first_of_each(codes, idx.numel())]] = True
+        corner, survive, emit = _records_stage(a, st, vertex_cluster, C, F, dev)
         s.update(origin=origin, C=C, vertex_cluster=vertex_cluster, cell=cell, corner=corner, survive=survive, emit=emit, live=live,
+                 grid_lo=i_lo, grid_hi=i_hi, key=uniq.contiguous(), args=a,
                  centre=(torch.tensor(origin, dtype=torch.float64, device=dev)[None] + (cell.double() + 0.5) * h).contiguous())
     return s
 
@@ -926,7 +934,165 @@ def count_simplified_faces(vertices, triangles, cell_size, origin=None):
     return int(s["emit"].sum()) if s["C"] > 0 else 0
 
 
-def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="quadric", eps=SIMPLIFY_EPS, attributes=()):
+# ---- adaptive simplification: octree vertex clustering under an error bound (csrc/mesh_simplify.hip: vdn_octree_*) ----
+OCTREE_LEVELS = 3            # the levels above the finest cells when a tolerance is given without them: an interface default
+OCTREE_MAX_LEVELS = 8
+
+
+def _check_levels(levels):
+    try:
+        ok = not isinstance(levels, bool) and int(levels) == levels and 1 <= levels <= OCTREE_MAX_LEVELS
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("levels must be an integer in [1, %d], got %r" % (OCTREE_MAX_LEVELS, levels))
+    return int(levels)
+
+
+def _check_tolerance(tolerance):
+    try:
+        tolerance = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a number, got %r" % (tolerance,))
+    if not tolerance >= 0.0:
+        raise ValueError("tolerance must not be negative, got %r" % (tolerance,))
+    return tolerance
+
+
+def _octree_node(lv, h, eps, prev=None, grid=None):
+    """vdn_octree_merge on one level: fills position, status, error, trace of the level dict lv (and quadric, mean, count, children
+    from the level below, `prev` on the grid `grid` = (lo, dims), in merge mode)"""
+    C, dev = lv["cell"].shape[0], lv["cell"].device
+    a = lib.VdnOctreeMergeArgs()
+    if prev is not None:
+        lv["quadric"], lv["mean"] = torch.empty(C, 10, dtype=torch.float64, device=dev), torch.empty(C, 3, dtype=torch.float64, device=dev)
+        lv["count"], lv["children"] = torch.empty(C, dtype=torch.int64, device=dev), torch.empty(C, 8, dtype=torch.int64, device=dev)
+        a.cell, a.child_key, a.child_quadric, a.child_mean, a.child_count = (lv["cell"].data_ptr(), prev["key"].data_ptr(),
+                                                                             prev["quadric"].data_ptr(), prev["mean"].data_ptr(), prev["count"].data_ptr())
+        a.children, a.count, a.Cc = lv["children"].data_ptr(), lv["count"].data_ptr(), prev["cell"].shape[0]
+        (a.lo_x, a.lo_y, a.lo_z), (a.nx, a.ny, a.nz) = grid
+    lv["position"], lv["status"] = torch.empty(C, 3, dtype=torch.float64, device=dev), torch.empty(C, dtype=torch.uint8, device=dev)
+    lv["error"], lv["trace"] = torch.empty(C, dtype=torch.float64, device=dev), torch.empty(C, dtype=torch.float64, device=dev)
+    a.centre, a.quadric, a.mean = lv["centre"].data_ptr(), lv["quadric"].data_ptr(), lv["mean"].data_ptr()
+    a.position, a.status, a.error, a.trace = lv["position"].data_ptr(), lv["status"].data_ptr(), lv["error"].data_ptr(), lv["trace"].data_ptr()
+    a.C, a.h, a.eps = C, h, eps
+    _call_sized("vdn_octree_merge", a, lib.stream_handle())
+
+
+def _build_octree(name, vertices, triangles, cell_size, levels, origin, eps):
+    levels, eps = _check_levels(levels), _positive_finite("eps", eps)
+    s = _cluster_stage(name, vertices, triangles, cell_size, origin)
+    dev, h0 = vertices.device, s["h"]
+    if not math.isfinite(h0 * 2.0 ** levels):
+        raise ValueError("%s: a cell size of %g is too large for %d levels" % (name, h0, levels))
+    tree = {"vertex_cluster": s["vertex_cluster"], "origin": s["origin"], "cell_size": h0, "eps": eps, "levels": [], "_stage": s}
+    if s["C"] == 0:
+        e = lambda *shape, dtype=torch.float64: torch.empty(*shape, dtype=dtype, device=dev)
+        for l in range(levels + 1):
+            lv = {"cell": e(0, 3, dtype=torch.int64), "quadric": e(0, 10), "mean": e(0, 3), "count": e(0, dtype=torch.int64), "position": e(0, 3),
+                  "status": e(0, dtype=torch.uint8), "error": e(0), "trace": e(0)}
+            if l < levels:
+                lv["parent"] = e(0, dtype=torch.int64)
+            tree["levels"].append(lv)
+        return tree
+    with torch.cuda.device(dev):
+        quadric, mean, vm, vstart = _quadric_stage(s)
+        origin_t = torch.tensor(s["origin"], dtype=torch.float64, device=dev)[None]
+        lv = {"cell": s["cell"].contiguous(), "key": s["key"], "centre": s["centre"], "quadric": quadric, "mean": mean,
+              "count": (vstart[1:] - vstart[:-1]).contiguous()}
+        _octree_node(lv, h0, eps)
+        tree["levels"].append(lv)
+        lo, hi = list(s["grid_lo"]), list(s["grid_hi"])
+        for l in range(1, levels + 1):
+            prev, grid = lv, (lo, [b - c + 1 for b, c in zip(hi, lo)])
+            lo, hi = [x >> 1 for x in lo], [x >> 1 for x in hi]                # (Python's shift is the floor, as the tensors' is)
+            dims = [b - c + 1 for b, c in zip(hi, lo)]
+            up = prev["cell"] >> 1
+            uniq, inv = torch.unique((up[:, 0] - lo[0]) + dims[0] * ((up[:, 1] - lo[1]) + dims[1] * (up[:, 2] - lo[2])), sorted=True,
+                                     return_inverse=True)                      # (the host learns C_l here: one read per level)
+            prev["parent"] = inv.contiguous()
+            cell = torch.stack([uniq % dims[0] + lo[0], (uniq // dims[0]) % dims[1] + lo[1], uniq // (dims[0] * dims[1]) + lo[2]], dim=1).contiguous()
+            h = h0 * 2.0 ** l
+            lv = {"cell": cell, "key": uniq.contiguous(), "centre": (origin_t + (cell.double() + 0.5) * h).contiguous()}
+            _octree_node(lv, h, eps, prev, grid)
+            tree["levels"].append(lv)
+        sizes = [x["cell"].shape[0] for x in tree["levels"]]
+        start = [0]
+        for n in sizes:
+            start.append(start[-1] + n)
+        # the level-major concatenation vdn_octree_assign walks, and what the final nodes are gathered from
+        tree["_start"] = start
+        tree["_start_t"] = torch.tensor(start, dtype=torch.int64, device=dev)
+        tree["_parent"] = torch.cat([x["parent"] + start[l + 1] for l, x in enumerate(tree["levels"][:-1])] +
+                                    [torch.full((sizes[-1],), -1, dtype=torch.int64, device=dev)]).contiguous()
+        tree["_level_of"] = torch.cat([torch.full((n,), l, dtype=torch.uint8, device=dev) for l, n in enumerate(sizes)])
+    return tree
+
+
+def cluster_octree(vertices, triangles, cell_size, levels, origin=None, eps=SIMPLIFY_EPS):
+    """The octree of clusters above cluster_quadrics' cells (vdn_octree_merge, include/vdn_render.h): level l has cubic cells of
+    edge cell_size 2^l from `origin`, the cell of a level-0 cell being its index >> l per axis, 1 <= levels <= 8 -> dict:
+    vertex_cluster [V] int64 (the level-0 cluster, -1: none), origin, cell_size, eps and `levels`, a list of levels + 1 dicts of
+    device tensors: cell [C_l,3] int64 (ascending key order), quadric [C_l,10] and mean [C_l,3] float64 relative to the cell centre
+    (level 0: cluster_quadrics'; above: the children's, moved to the parent's centre and added in slot order), count [C_l] int64
+    (referenced vertices), position [C_l,3] float64 (absolute: simplify_mesh's placement, with that level's edge), status [C_l]
+    uint8, error [C_l] (the quadric at the placed vertex, clamped at 0), trace [C_l], parent [C_l] int64 (the index in the next
+    level; absent at the top) and, above level 0, children [C_l,8] int64 (-1: absent). The tree does not depend on a tolerance.
+    Host reads: the two of the level-0 stage and one per level above it (C_l). ValueError as simplify_mesh."""
+    return _build_octree("cluster_octree", vertices, triangles, cell_size, levels, origin, eps)
+
+
+def select_octree(tree, tolerance):
+    """The node of every level-0 cluster of a cluster_octree tree under a tolerance (vdn_octree_select, vdn_octree_assign): a node
+    is ACCEPTED when its trace is positive and finite and error < tolerance^2 trace (error / trace is the area-squared-weighted
+    mean squared distance of the placed vertex to the planes of the node's triangles: the tolerance is an rms distance in the
+    mesh's units), SOLID when it is accepted and all its children are solid (level 0 is solid); a cluster's node is its highest
+    solid ancestor -> (level [C_0] uint8, node [C_0] int64: the index inside that level). No host read."""
+    tol = _check_tolerance(tolerance)
+    lv = tree["levels"]
+    C0, dev = lv[0]["cell"].shape[0], lv[0]["cell"].device
+    if C0 == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        start, st = tree["_start"], lib.stream_handle()
+        solid = torch.ones(start[-1], dtype=torch.uint8, device=dev)
+        for l in range(1, len(lv)):
+            a = lib.VdnOctreeSelectArgs()
+            a.error, a.trace, a.children = lv[l]["error"].data_ptr(), lv[l]["trace"].data_ptr(), lv[l]["children"].data_ptr()
+            a.child_solid, a.solid = solid[start[l - 1]:].data_ptr(), solid[start[l]:].data_ptr()
+            a.C, a.Cc, a.tolerance2 = start[l + 1] - start[l], start[l] - start[l - 1], tol * tol
+            _call_sized("vdn_octree_select", a, st)
+        level, node = torch.empty(C0, dtype=torch.uint8, device=dev), torch.empty(C0, dtype=torch.int64, device=dev)
+        a = lib.VdnOctreeAssignArgs()
+        a.parent, a.solid, a.level_start, a.level, a.node = (tree["_parent"].data_ptr(), solid.data_ptr(), tree["_start_t"].data_ptr(),
+                                                             level.data_ptr(), node.data_ptr())
+        a.C0, a.N, a.levels = C0, start[-1], len(lv) - 1
+        _call_sized("vdn_octree_assign", a, st)
+    return level, node
+
+
+def _octree_map(tree, tolerance):
+    """-> (vertex map [V] int64 onto the nodes in use, numbered level-major; their global numbers [C'] ascending). One host read."""
+    level, node = select_octree(tree, tolerance)
+    used, inv = torch.unique(tree["_start_t"][level.long()] + node, sorted=True, return_inverse=True)
+    vc = tree["vertex_cluster"]
+    return torch.where(vc >= 0, inv[vc.clamp_min(0)], torch.full_like(vc, -1)).contiguous(), used
+
+
+def count_octree_faces(tree, tolerance):
+    """The number of triangles simplify_mesh emits for a tolerance, from a built cluster_octree tree: select, assign, corner records
+    and the duplicate rule; no quadrics (what a search for a tolerance needs)."""
+    s = tree["_stage"]
+    if s["C"] == 0:
+        return 0
+    with torch.cuda.device(s["v"].device):
+        vmap, used = _octree_map(tree, tolerance)
+        emit = _records_stage(s["args"], lib.stream_handle(), vmap, int(used.shape[0]), s["F"], s["v"].device)[2]
+        return int(emit.sum())
+
+
+def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="quadric", eps=SIMPLIFY_EPS, attributes=(), tolerance=None,
+                  levels=None, tree=None):
     """Vertex clustering with quadric error placement: vertices [V,3] CUDA float (taken as fp32), triangles [F,3] CUDA int64 or int32
     -> dict(vertices [V',3] (the input's float dtype), triangles [F',3] (the input's integer dtype), attributes, vertex_cluster [V]
     int64 (the NEW vertex of each old one, -1 where it has none), status [V'] uint8, report).
@@ -944,31 +1110,72 @@ def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="qua
     come back in their dtype, uint8 ones as the float mean rounded to nearest, halves to even.
     report: vertices_in, faces_in, clusters, vertices_out, faces_out, faces_collapsed, faces_duplicate, faces_non_finite,
     cell_size, origin, placement, eps, status (the count of each status value).
-    ValueError on CPU tensors, wrong shapes, a corner index outside [0, V), a cell_size or eps that is not positive and finite, or a
-    grid whose nx ny nz does not fit 62 bits. An empty mesh (or one without a live triangle) returns an empty mesh."""
+
+    tolerance (keyword, with levels, default OCTREE_LEVELS): the adaptive mode. cell_size is the finest cell; the clusters are the
+    nodes select_octree picks in a cluster_octree of `levels` levels, numbered level-major (ascending level, then index): cells
+    grow, up to cell_size 2^levels, wherever the placed vertex stays within `tolerance` (rms) of the planes it replaces. tolerance
+    = 0 gives the uniform result at cell_size, a tolerance beyond sqrt(3) cell_size 2^levels the uniform result at the coarsest
+    size. Everything after the vertex map - records, survive and duplicate rule, attributes - is as above. The result gains level
+    [V'] uint8 (the level of each new vertex's node; status and the fallback refer to that node's cell), the report tolerance,
+    levels and nodes_per_level (the nodes in use per level; clusters is their sum). `tree`: a cluster_octree tree of the same
+    mesh, cell size, origin, levels and eps, to spare building it again. Needs placement="quadric".
+
+    ValueError on CPU tensors, wrong shapes, a corner index outside [0, V), a cell_size or eps that is not positive and finite, a
+    negative tolerance, levels outside [1, 8] or without a tolerance, or a grid whose nx ny nz does not fit 62 bits. An empty mesh
+    (or one without a live triangle) returns an empty mesh."""
     if placement not in ("quadric", "mean"):
         raise ValueError("placement must be 'quadric' or 'mean', got %r" % (placement,))
     eps = _positive_finite("eps", eps)
+    adaptive = tolerance is not None
+    if adaptive:
+        tolerance, levels = _check_tolerance(tolerance), _check_levels(OCTREE_LEVELS if levels is None else levels)
+        if placement != "quadric":
+            raise ValueError("a tolerance needs placement='quadric': the error it bounds is the quadric's")
+    elif levels is not None or tree is not None:
+        raise ValueError("levels and tree belong to the adaptive mode: give a tolerance")
     attributes = list(attributes)
     V = vertices.shape[0] if torch.is_tensor(vertices) and vertices.dim() > 0 else 0
     for x in attributes:
         if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.shape[0] == V and (x.is_floating_point() or x.dtype == torch.uint8)):
             raise ValueError("an attribute must be a float or uint8 CUDA tensor with one row per vertex")
-    s = _cluster_stage("simplify_mesh", vertices, triangles, cell_size, origin)
+    if adaptive:
+        if tree is None:
+            tree = _build_octree("simplify_mesh", vertices, triangles, cell_size, levels, origin, eps)
+        elif (len(tree["levels"]) != levels + 1 or tree["cell_size"] != float(cell_size) or tree["eps"] != eps or tree["_stage"]["V"] != V or
+              tree["_stage"]["F"] != triangles.shape[0] or (origin is not None and tree["origin"] is not None and
+                                                            [float(x) for x in origin] != list(tree["origin"]))):
+            raise ValueError("the tree was built with other arguments")
+        s = tree["_stage"]
+    else:
+        s = _cluster_stage("simplify_mesh", vertices, triangles, cell_size, origin)
     dev, C, F = vertices.device, s["C"], s["F"]
     report = {"vertices_in": s["V"], "faces_in": F, "clusters": C, "cell_size": s["h"], "origin": s["origin"], "placement": placement,
               "eps": eps, "faces_non_finite": F - s["n_live"]}
+    if adaptive:
+        report.update(tolerance=tolerance, levels=levels, nodes_per_level=[0] * (levels + 1))
     if C == 0:
         report.update(vertices_out=0, faces_out=0, faces_collapsed=0, faces_duplicate=0, status={"0": 0, "1": 0, "2": 0})
-        return {"vertices": torch.empty(0, 3, dtype=vertices.dtype, device=dev), "triangles": torch.empty(0, 3, dtype=triangles.dtype, device=dev),
-                "attributes": [torch.empty((0,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in attributes],
-                "vertex_cluster": s["vertex_cluster"], "status": torch.empty(0, dtype=torch.uint8, device=dev), "report": report}
+        res = {"vertices": torch.empty(0, 3, dtype=vertices.dtype, device=dev), "triangles": torch.empty(0, 3, dtype=triangles.dtype, device=dev),
+               "attributes": [torch.empty((0,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev) for x in attributes],
+               "vertex_cluster": s["vertex_cluster"], "status": torch.empty(0, dtype=torch.uint8, device=dev), "report": report}
+        if adaptive:
+            res["level"] = torch.empty(0, dtype=torch.uint8, device=dev)
+        return res
     with torch.cuda.device(dev):
-        status = torch.zeros(C, dtype=torch.uint8, device=dev)
-        if placement == "mean":
+        vertex_cluster, corner, survive, emit, level = s["vertex_cluster"], s["corner"], s["survive"], s["emit"], None
+        if adaptive:
+            vertex_cluster, used = _octree_map(tree, tolerance)
+            C = int(used.shape[0])
+            corner, survive, emit = _records_stage(s["args"], lib.stream_handle(), vertex_cluster, C, F, dev)
+            vm, vstart = _segments(torch.where(vertex_cluster < 0, torch.full_like(vertex_cluster, C), vertex_cluster), C)
+            position = torch.cat([x["position"] for x in tree["levels"]])[used]
+            status, level = torch.cat([x["status"] for x in tree["levels"]])[used], tree["_level_of"][used]
+        elif placement == "mean":
+            status = torch.zeros(C, dtype=torch.uint8, device=dev)
             vm, vstart = _vertex_members(s)
             position = _segment_mean(s["v"], vm, vstart, C)          # (= centre + the mean relative to it, without the round trip)
         else:
+            status = torch.zeros(C, dtype=torch.uint8, device=dev)
             quadric, mean, vm, vstart = _quadric_stage(s)
             position = torch.empty(C, 3, dtype=torch.float64, device=dev)
             a = lib.VdnClusterQuadricArgs()
@@ -977,8 +1184,8 @@ def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="qua
             a.V, a.F, a.C, a.h, a.eps = s["V"], F, C, s["h"], eps
             _call_sized("vdn_cluster_place", a, lib.stream_handle())
         # (the records of a triangle that is not emitted may hold the sentinel C: not an index filter_mesh accepts)
-        corner = torch.where(s["emit"][:, None], s["corner"].reshape(F, 3), torch.zeros((), dtype=torch.int64, device=dev)).to(triangles.dtype)
-        new_v, new_t, kept = filter_mesh(position, corner, keep_faces=s["emit"])
+        corner = torch.where(emit[:, None], corner.reshape(F, 3), torch.zeros((), dtype=torch.int64, device=dev)).to(triangles.dtype)
+        new_v, new_t, kept = filter_mesh(position, corner, keep_faces=emit)
         out_attrs = []
         for x in attributes:
             m = _segment_mean(x.reshape(V, -1).float(), vm, vstart, C)[kept].reshape((kept.shape[0],) + tuple(x.shape[1:]))
@@ -986,11 +1193,16 @@ def simplify_mesh(vertices, triangles, cell_size, *, origin=None, placement="qua
         new_of_cluster = torch.full((C + 1,), -1, dtype=torch.int64, device=dev)
         new_of_cluster[kept] = torch.arange(kept.shape[0], device=dev)
         status = status[kept]
-        n_surv, n_stat = int(s["survive"].sum()), torch.bincount(status.long(), minlength=3).tolist()       # host read 3
+        n_surv, n_stat = int(survive.sum()), torch.bincount(status.long(), minlength=3).tolist()       # host read 3
+        if adaptive:
+            report.update(clusters=C, nodes_per_level=torch.bincount(level.long(), minlength=levels + 1).tolist())
     report.update(vertices_out=int(new_v.shape[0]), faces_out=int(new_t.shape[0]), faces_collapsed=s["n_live"] - n_surv,
                   faces_duplicate=n_surv - int(new_t.shape[0]), status={str(k): int(n) for k, n in enumerate(n_stat)})
-    return {"vertices": new_v.to(vertices.dtype), "triangles": new_t, "attributes": out_attrs,
-            "vertex_cluster": new_of_cluster[s["vertex_cluster"]], "status": status, "report": report}
+    res = {"vertices": new_v.to(vertices.dtype), "triangles": new_t, "attributes": out_attrs,
+           "vertex_cluster": new_of_cluster[vertex_cluster], "status": status, "report": report}
+    if adaptive:
+        res["level"] = level[kept]
+    return res
 
 
 # ---- textured meshes: a per-face atlas (csrc/mesh_texture.hip) ----------------------------------------------------------

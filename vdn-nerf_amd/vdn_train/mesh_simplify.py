@@ -1,7 +1,8 @@
 """Mesh simplification: bring an extracted surface down to a chosen density before it is viewed, shipped or compared - vertex
 clustering with quadric error placement on the device (vdn_hip/mesh.py: simplify_mesh, csrc/mesh_simplify.hip; DESIGN.md 3p,
 INTEGRATION.md "Mesh simplification"). simplify_mesh here is the front door for arrays of either kind: it takes a cell size, or a
-face budget that it turns into a cell size by bisection on a count-only pass."""
+face budget that it turns into a cell size by bisection on a count-only pass; with a tolerance (or a budget and levels) the cells
+grow adaptively, by octree merging under an error bound."""
 import math
 
 import numpy as np
@@ -66,15 +67,68 @@ def find_cell_size(vertices, triangles, target_faces, origin=None):
     return best, tried
 
 
-def simplify_mesh(vertices, triangles, *, cell_size=None, target_faces=None, origin=None, placement="quadric", eps=None, attributes=()):
+def find_tolerance(tree, target_faces):
+    """The smallest tolerance tried whose adaptive mesh (vdn_hip.mesh.simplify_mesh(tolerance=..) on the built cluster_octree `tree`)
+    has at most target_faces triangles -> (tolerance, tried), tried = the (tolerance, faces) pairs in the order they were counted.
+    A bisection of log(tolerance) between 1e-6 finest cells (nothing merges) and sqrt(3) (1 + 1e-6) coarsest cells - above that
+    every cell with a positive trace is accepted, because each recorded triangle's plane passes through a corner inside the cell,
+    no further from the placed vertex than the cell's diagonal - with at most TARGET_PASSES count passes
+    (vdn_hip.mesh.count_octree_faces: select, assign, records and the duplicate rule on the one tree; no quadrics). The count is
+    monotone only in the large; the answer is the smallest tolerance SEEN to fit. ValueError when the upper end does not fit: the
+    coarsest cells are too fine for the budget."""
+    from vdn_hip import mesh
+    if int(target_faces) != target_faces or target_faces < 0:
+        raise ValueError("target_faces must be a non-negative integer, got %r" % (target_faces,))
+    h0, levels = tree["cell_size"], len(tree["levels"]) - 1
+    lo, hi = 1e-6 * h0, math.sqrt(3.0) * h0 * 2.0 ** levels * (1.0 + 1e-6)
+    tried = []
+
+    def count(tol):
+        n = mesh.count_octree_faces(tree, tol)
+        tried.append((tol, n))
+        return n
+    if count(lo) <= target_faces:
+        return lo, tried
+    if count(hi) > target_faces:
+        raise ValueError("even with every cell merged up to %g (cell_size %g, %d levels) the mesh keeps %d faces, more than %d: raise "
+                         "levels or cell_size" % (h0 * 2.0 ** levels, h0, levels, tried[-1][1], target_faces))
+    best = hi
+    while len(tried) < TARGET_PASSES:
+        mid = math.sqrt(lo * hi)
+        if count(mid) <= target_faces:
+            best = hi = mid
+        else:
+            lo = mid
+    return best, tried
+
+
+def simplify_mesh(vertices, triangles, *, cell_size=None, target_faces=None, origin=None, placement="quadric", eps=None, attributes=(),
+                  tolerance=None, levels=None):
     """vertices [V,3] float, triangles [F,3] integer (numpy arrays or CUDA tensors) -> dict(vertices, triangles, attributes,
     vertex_cluster, status, report), arrays of the inputs' kind and dtypes: vdn_hip.mesh.simplify_mesh. Exactly one of cell_size
     (the clustering cells' edge, in the mesh's units) and target_faces (a face budget: find_cell_size picks the cell size, and the
     report lists every (size, faces) pair it tried under "tried") is given. `attributes` (a sequence of [V,...] float or uint8 arrays:
     normals, colours) are averaged per new vertex; an averaged normal is no unit vector any more - renormalise it, or shade the new
-    vertices afresh (validate_mesh(simplify=...) does that)."""
+    vertices afresh (validate_mesh(simplify=...) does that).
+
+    The adaptive mode is on when `tolerance` or `levels` is given, and then cell_size is required: it is the finest cell, and cells
+    grow by octree merging, up to cell_size 2^levels (levels defaults to vdn_hip.mesh.OCTREE_LEVELS), wherever the merged cell's
+    vertex stays within `tolerance` (an rms distance, in the mesh's units) of the planes it replaces; the result gains `level`.
+    With target_faces in place of the tolerance the tree is built once and find_tolerance picks the tolerance; the report lists
+    the (tolerance, faces) pairs under "tried"."""
     from vdn_hip import mesh
-    if (cell_size is None) == (target_faces is None):
+    adaptive = tolerance is not None or levels is not None
+    if adaptive:
+        if cell_size is None:
+            raise ValueError("the adaptive mode (tolerance, levels) needs cell_size, its finest cell")
+        if (tolerance is None) == (target_faces is None):
+            raise ValueError("the adaptive mode needs exactly one of tolerance and target_faces")
+        if placement != "quadric":
+            raise ValueError("the adaptive mode needs placement='quadric': the error it bounds is the quadric's")
+        levels = mesh._check_levels(mesh.OCTREE_LEVELS if levels is None else levels)
+        if tolerance is not None:
+            tolerance = mesh._check_tolerance(tolerance)
+    elif (cell_size is None) == (target_faces is None):
         raise ValueError("exactly one of cell_size and target_faces must be given")
     as_numpy = not torch.is_tensor(vertices)
     v_in = vertices if torch.is_tensor(vertices) else np.asarray(vertices)
@@ -96,14 +150,21 @@ def simplify_mesh(vertices, triangles, *, cell_size=None, target_faces=None, ori
     kw = {} if eps is None else {"eps": eps}
     tried = None
     with torch.cuda.device(dev):
-        if target_faces is not None:
-            cell_size, tried = find_cell_size(v, t, target_faces, origin=origin)
-        res = mesh.simplify_mesh(v, t, cell_size, origin=origin, placement=placement, attributes=[to_dev(x) for x in attributes], **kw)
+        if adaptive:
+            tree = mesh.cluster_octree(v, t, cell_size, levels, origin=origin, **kw)
+            if target_faces is not None:
+                tolerance, tried = find_tolerance(tree, target_faces)
+            res = mesh.simplify_mesh(v, t, cell_size, origin=origin, attributes=[to_dev(x) for x in attributes], tolerance=tolerance,
+                                     levels=levels, tree=tree, **kw)
+        else:
+            if target_faces is not None:
+                cell_size, tried = find_cell_size(v, t, target_faces, origin=origin)
+            res = mesh.simplify_mesh(v, t, cell_size, origin=origin, placement=placement, attributes=[to_dev(x) for x in attributes], **kw)
     if tried is not None:
         res["report"].update(target_faces=int(target_faces), tried=[[float(h), int(n)] for h, n in tried])
     res["triangles"] = res["triangles"].to(t_dtype)
     if as_numpy:
-        for k in ("vertices", "triangles", "vertex_cluster", "status"):
+        for k in ("vertices", "triangles", "vertex_cluster", "status") + (("level",) if adaptive else ()):
             res[k] = res[k].cpu().numpy()
     res["attributes"] = [x if torch.is_tensor(a) else x.cpu().numpy() for a, x in zip(attributes, res["attributes"])]
     return res

@@ -159,8 +159,9 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     `clean` (a dict of vdn_train.mesh_clean.clean_mesh's keyword arguments, or None: the raw surface) cleans the mesh in object
     space, before the world_space map; normals and colours follow their vertices, and V, F are the cleaned mesh's. `sparse` is
     extract_geometry's: None (dense, or what VDN_MESH_SPARSE says), True or a dict - the same file from the bricks near the surface.
-    `simplify` (a dict of vdn_train.mesh_simplify.simplify_mesh's keyword arguments - cell_size or target_faces, in object-space
-    units - or None: the file as it always was) thins the mesh after `clean` and before the world_space map. The vertices are then
+    `simplify` (a dict of vdn_train.mesh_simplify.simplify_mesh's keyword arguments - cell_size or target_faces, or cell_size with
+    tolerance / levels for the adaptive mode, in object-space units - or None: the file as it always was) thins the mesh after
+    `clean` and before the world_space map. The vertices are then
     shaded AFTER the simplification, at their new positions (renderer.shade_vertices): normals and colours come from the networks,
     not from averages, and the fine surface is never shaded at all - one shading pass, over the vertices that reach the file.
     `texture` (a dict of vdn_hip.mesh.bake_texture's keyword arguments - texture_size, patch, project, ... - or None: nothing beyond
