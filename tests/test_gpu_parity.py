@@ -963,8 +963,11 @@ def test_train_prep_equals_the_separate_launches(dev):
 @pytest.mark.parametrize("wdepth", [False, True], ids=["womsk_white", "womsk_white_wdepth"])
 def test_render_plan_replays_equal_render_calls(wdepth):
     """NeuSRenderer.plan(): render() captured once as a HIP graph and replayed on new
-    rays is bit-identical to plain render() calls; a parameter changed in place is picked up by the next replay; with the
+    rays is bit-identical to plain render() calls; a parameter changed in place is picked up by the next replay - plan and
+    render() share the renderer's weight images, so that step is also held to a renderer freshly built from the changed
+    state_dict (tests/coherence.py: twin) and must differ from the unchanged weights' output; with the
     jitter on, every replay draws its own."""
+    import coherence
     from vdn_train import synth, factory
     dev = torch.device("cuda:0")
     rend = factory.build_renderer(wdepth=wdepth, device=dev, states=synth.make_all_states(3, wdepth=wdepth), precision="bf16")
@@ -979,15 +982,22 @@ def test_render_plan_replays_equal_render_calls(wdepth):
     with torch.no_grad():
         plan = rend.plan(512, **kw)
         for step in range(3):
+            b = batch(step)
             if step == 2:
+                unchanged = {k: v.clone() for k, v in rend.render(*b, **kw).items() if v is not None}
                 for p in rend.sdf_network.parameters():
                     p.mul_(1.01)
                 rend.color_network.parameters().__next__().add_(0.003)
-            b = batch(step)
             got = {k: v.clone() for k, v in plan(*b).items() if v is not None}
             want = rend.render(*b, **kw)
             for k, v in got.items():
                 assert torch.equal(v, want[k]), (step, k)
+            if step == 2:
+                fresh = coherence.twin(rend, trainer=False).render(*b, **kw)
+                for k, v in got.items():
+                    assert torch.equal(v, fresh[k]), ("twin", k)
+                for k in ("color_fine", "weights", "gradients", "gradient_error"):
+                    assert not torch.equal(got[k], unchanged[k]), ("the changed weights moved nothing", k)
         with pytest.raises(ValueError):
             plan(*[t[:100] for t in batch(0)])
         jit = rend.plan(512, background_rgb=bg, cos_anneal_ratio=0.7, perturb_overwrite=1)

@@ -185,7 +185,10 @@ class _HipNet(nn.Module):
         hook = self.__dict__.get("_stream_join")
         if hook is not None:
             hook = hook()             # (a weakref.WeakMethod: the network does not keep its Trainer alive, and copies / pickles of
-            if hook is not None:      # the module carry no Trainer - __getstate__ below)
+            # the module carry no Trainer - __getstate__ below). Not inside a stream capture: a graph cannot carry a wait for work
+            # issued outside it - whoever replays the graph places the wait on the replaying stream (render() and
+            # RenderPlan.__call__ do, through this method, before they capture or replay)
+            if hook is not None and not torch.cuda.is_current_stream_capturing():
                 hook()
 
     def _image_state(self):
@@ -197,10 +200,19 @@ class _HipNet(nn.Module):
         st = self.__dict__.get("_img")
         fmt = images.FMT_F32 if self._sfx() == "_f32" else images.FMT_BF16
         if st is None or st.device != dev or st.fmt != fmt:
-            st = images.NetImages(self._matrices(), self._streams(), dev, fmt)
+            # (source=self: the images follow Parameter objects that are replaced later - images.NetImages)
+            st = images.NetImages(self._matrices(), self._streams(), dev, fmt, source=self)
             self.__dict__["_img"] = st
         return st
 
+    def weights_changed(self):
+        """Tell the network that its parameters were written in a way it cannot see: `p.data.add_()` / `p.data.copy_()` (torch
+        bumps no version counter for writes through .data) or a kernel writing through raw pointers. The next use rebuilds the
+        weight images. Everything else - in-place ops on the Parameters, optimizers, load_state_dict (assign=True too), nn.init,
+        p.data = t, .to(...), a replaced Parameter object - is detected without this call."""
+        st = self.__dict__.get("_img")
+        if st is not None:
+            st.invalidate()
 
     def __getstate__(self):
         # device state and Trainer hooks are per-process / per-object: copy.deepcopy and torch.save(module) rebuild them lazily

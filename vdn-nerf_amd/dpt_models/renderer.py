@@ -377,6 +377,23 @@ class NeuSRenderer:
             raise ValueError("a depth_network needs a background NeRF with gen_depth_feats=True (the shipped wdepth configuration)")
         self._const_cache = {}
 
+    def __getstate__(self):
+        # engines, graph plans and the other device-side caches belong to this object and this process (streams, events, captured
+        # graphs with raw pointers into its own buffers): copy.deepcopy and pickles carry the networks and rebuild the rest lazily
+        st = dict(self.__dict__)
+        for k in ("_engines", "_img_tables", "_jitter", "_shade_ticket", "_pending_merge", "last_eikonal_terms"):
+            st.pop(k, None)
+        st["_const_cache"] = {}
+        return st
+
+    def weights_changed(self):
+        """The parameters of some network of this renderer were written behind torch's back (`p.data.add_()`, raw pointers): every
+        network rebuilds its weight images at its next use (fields.py: _HipNet.weights_changed; INTEGRATION.md says which writes
+        need this call). The variance has no image - the kernels read the parameter itself."""
+        for m in (self.nerf, self.sdf_network, self.color_network, self.depth_network):
+            if m is not None:
+                m.weights_changed()
+
     @property
     def precision(self):
         """The kernels' precision when all networks agree, else "mixed". Assigning sets every network (one line instead of four)."""
@@ -778,7 +795,13 @@ class NeuSRenderer:
     def _engine_for(self, B, dev, params):
         from vdn_hip.train import TrainEngine
         engines = self.__dict__.setdefault("_engines", {})
-        pkey = (dev, tuple(p.data_ptr() for p in params), self.precision)
+        # An engine - and the _TrainPlan graphs it owns - holds raw pointers to the parameters' storage, keeps the Parameter objects
+        # (its gradient views are found by them) and points into the networks' weight-image buffers: it is valid for exactly these
+        # addresses, these objects and these NetImages (a precision switch and back builds NEW images at the old precision; the
+        # engine keeps the images it was built on alive, so an id() here is never a recycled one)
+        nets = (self.nerf, self.sdf_network, self.color_network, self.depth_network)
+        pkey = (dev, tuple(p.data_ptr() for p in params), tuple(map(id, params)), self.precision,
+                tuple(id(m.__dict__.get("_img")) for m in nets if m is not None))
         key = (B,) + pkey
         eng = engines.pop(key, None)
         if eng is None:
@@ -918,7 +941,12 @@ class RenderPlan:
         self.o, self.d = torch.zeros(batch, 3, device=dev), torch.zeros(batch, 3, device=dev)
         self.d[:, 2] = 1.0
         self.near, self.far = torch.zeros(batch, 1, device=dev), torch.ones(batch, 1, device=dev)
-        side = torch.cuda.Stream(device=dev)
+        self.captures = 0
+        self._capture()
+
+    def _capture(self):
+        renderer = self.renderer
+        side = torch.cuda.Stream(device=self.o.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                         # warm-up outside capture: weight images, lazy workspaces
             renderer.render(self.o, self.d, self.near, self.far, **self.kw)
@@ -926,16 +954,34 @@ class RenderPlan:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = renderer.render(self.o, self.d, self.near, self.far, **self.kw)
+        self._captured = self._signature()
+        # ... and keeps those objects alive: the ids above are never recycled ones, and the storage the graph points into is not
+        # freed under it
+        self._held = (renderer._all_parameters(), [m.__dict__.get("_img") for m in self._nets()])
+        self.captures += 1
 
     def _nets(self):
         r = self.renderer
         return [m for m in (r.nerf, r.sdf_network, r.color_network, r.depth_network) if m is not None]
+
+    def _signature(self):
+        """What the graph's nodes hold by raw pointer or took a launch decision on: every parameter's storage and object (the
+        compositor reads the variance itself; the weight images follow the others), and each network's NetImages object (its
+        blobs and effective weights) and precision (the kernels that were captured)."""
+        ps = self.renderer._all_parameters()
+        return (tuple(p.data_ptr() for p in ps), tuple(map(id, ps)),
+                tuple((id(m.__dict__.get("_img")), m.precision) for m in self._nets()))
 
     def __call__(self, rays_o, rays_d, near, far):
         if rays_o.shape[0] != self.batch:
             raise ValueError("this plan renders batches of %d rays, got %d" % (self.batch, rays_o.shape[0]))
         for m in self._nets():
             m._images()                                       # re-materialise the weight images if a parameter changed
+        if self._signature() != self._captured:
+            # a parameter moved (module.to(...), p.data = t, a Trainer built on the renderer) or was replaced, or a network
+            # switched precision: the captured pointers are stale - capture again, never replay them
+            with torch.no_grad():                             # (the plan is the inference path, whatever the caller's grad mode)
+                self._capture()
         self.o.copy_(rays_o.detach())
         self.d.copy_(rays_d.detach())
         self.near.copy_(near.detach().reshape(-1, 1))

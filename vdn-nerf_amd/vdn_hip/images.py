@@ -7,7 +7,9 @@ described by a padded input map (kmap: padded k -> source column, -1 = zero), an
 source matrix, a bias vector and a 32-entry output-row map. Transposed layers (reverse sweeps,
 backward chains) swap the strides, nothing else.
 """
+import itertools
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -15,6 +17,7 @@ import torch
 from . import lib
 
 FMT_F32, FMT_BF16 = 0, 1
+_TABLE_GEN = itertools.count(1)      # one number per descriptor-table build in this process (NetImages.tables_gen)
 
 
 def chunk_bytes(kt, fmt=FMT_F32):
@@ -94,18 +97,69 @@ def transposed_layer(name, fwd_kmap, fwd_nmap, scale=1.0):
                  [(name, False, fwd_kmap[i:i + 32]) for i in range(0, len(fwd_kmap), 32)], scale, transposed=True)
 
 
+def _member_dicts(module):
+    """Every _parameters / _modules dict of a module tree: what a Parameter or a layer holder is replaced IN."""
+    out = [module._parameters, module._modules]
+    for c in module._modules.values():
+        if c is not None:
+            out += _member_dicts(c)
+    return out
+
+
+def _member_ids(dicts):
+    return tuple(map(id, itertools.chain.from_iterable(map(dict.values, dicts))))
+
+
+_LIVE = weakref.WeakSet()            # every NetImages alive in the process (_fused_step_hook)
+_HOOKED = []
+
+
+def _fused_step_hook(optimizer, args, kwargs):
+    """torch's fused optimizers (torch.optim.Adam(fused=True), AdamW, SGD ...) update all parameters in one multi-tensor kernel
+    that bumps NO version counter (tests/test_weight_coherence_cpu.py pins it): in-place, same address, same object - nothing
+    the staleness test could see. This hook runs behind every optimizer step in the process and invalidates the image sets
+    that hold a parameter of a fused optimizer."""
+    if not any(g.get("fused") for g in optimizer.param_groups):
+        return
+    ids = {id(p) for g in optimizer.param_groups for p in g["params"]}
+    for im in list(_LIVE):
+        if any(id(t) in ids for t in im._flat):
+            im.invalidate()
+
+
+def _watch(im):
+    _LIVE.add(im)
+    if not _HOOKED:
+        from torch.optim.optimizer import register_optimizer_step_post_hook
+        _HOOKED.append(register_optimizer_step_post_hook(_fused_step_hook))
+
+
 class NetImages:
     """Device-side state of one network: effective weights + chunk-stream blobs.
 
     matrices: ordered {name: (g or None, v, bias or None)} of torch Parameters.
     streams:  {stream_name: [Layer, ...]}.
+    source:   the module that owns the parameters (held weakly), or None. With a source the images follow the module's CURRENT
+              Parameter objects: one that was replaced (load_state_dict(assign=True), `layer.weight_v = nn.Parameter(...)`) is
+              picked up by the next staleness test - `matrices` is read again from source._matrices() and the tables are rebuilt.
+              The device buffers (weff, inv_norm, blobs) never move, so pointers launches or captured graphs hold stay valid.
+
+    What the staleness test sees (tests/test_weight_coherence_cpu.py pins the table for the installed torch): a parameter's
+    _version (in-place ops on the Parameter or an alias of it: optimizers, load_state_dict, nn.init), its data_ptr() (p.data = t,
+    module.to(...)) and its identity. Writes that move none of them - p.data.add_(), kernels writing through raw pointers - need
+    invalidate() (the modules' weights_changed()); for torch's fused optimizers, which are such writers, _fused_step_hook calls it.
     """
 
-    def __init__(self, matrices, streams, device, fmt=FMT_F32):
+    def __init__(self, matrices, streams, device, fmt=FMT_F32, source=None):
         self.device = device
         self.fmt = fmt
         self.matrices = matrices
         self.streams = streams
+        self._source = None if source is None else weakref.ref(source)
+        self._flat = [t for n in matrices for t in matrices[n] if t is not None]
+        # identities of the source's parameters and submodules, read through the dicts that hold them (a few us per staleness test)
+        self._dicts = None if source is None else _member_dicts(source)
+        self._ids = None if source is None else _member_ids(self._dicts)
         self._key = None
         # counts every (re)build and every invalidation of the images: what "the weights changed" means to consumers that cache
         # something derived from them (fields.py: the NeRF scratch buffer). torch's version counters are not enough - the Trainer's
@@ -147,7 +201,9 @@ class NetImages:
                     off += stride
         self.maps = torch.from_numpy(np.concatenate(maps)).to(device)
         self._chunk_rows = chunk_rows
+        _watch(self)
         self._tables_key = None
+        self.tables_gen = 0          # the process-wide number of the latest _build_tables(): what a cache of the tables' contents is keyed by
         self.wn_table = None
         self.chunk_table = None
 
@@ -193,38 +249,60 @@ class NetImages:
         self.wn_table = torch.from_numpy(wn.view(np.uint8)).to(self.device)
         self.chunk_table = torch.from_numpy(ch.view(np.uint8)).to(self.device)
         self._n_wn, self._n_ch = len(wn), len(ch)
+        self.tables_gen = next(_TABLE_GEN)
 
     def invalidate(self):
-        """Parameters were written outside torch's version tracking (fused Adam through raw pointers)."""
+        """Parameters were written outside torch's version tracking (fused Adam through raw pointers, p.data.add_())."""
         self._key = None
         self.builds += 1
 
     def _params(self):
-        return [t for n in self.names for t in self.matrices[n] if t is not None]
+        return self._flat
+
+    def _follow(self):
+        """Parameter objects of the source module that were replaced since `matrices` was read: read it again."""
+        if _member_ids(self._dicts) != self._ids:
+            src = self._source()
+            if src is None:
+                return
+            self._dicts = _member_dicts(src)
+            ids = _member_ids(self._dicts)
+            matrices = src._matrices()
+            if list(matrices) != self.names or any(matrices[n][1].shape != self.matrices[n][1].shape for n in self.names):
+                raise RuntimeError("%s: a replaced parameter changes the network's shapes; the weight images are laid out for "
+                                   "the shapes the network was built with" % type(src).__name__)
+            self.matrices = matrices
+            self._flat = [t for n in self.names for t in matrices[n] if t is not None]
+            self._ids = ids
+            self._tables_key = None
 
     def _ensure_tables(self):
-        ptr_key = tuple(t.data_ptr() for t in self._params())
+        if self._source is not None:
+            self._follow()
+        ptr_key = tuple(t.data_ptr() for t in self._flat)
         if ptr_key != self._tables_key:
             self._build_tables()
             self._tables_key = ptr_key
             self._key = None
 
+    def mark_fresh(self):
+        """The images were just built from the parameters as they are now."""
+        self._key = tuple(t._version for t in self._flat)
+        self.builds += 1
+
     def stale(self):
         self._ensure_tables()
-        return tuple(t._version for t in self._params()) != self._key
+        return tuple(t._version for t in self._flat) != self._key
 
     def refresh(self, stream):
         """Re-materialise W_eff and all chunk images if any parameter changed (in place or rebound)."""
         if _TRUSTED is not None and id(self) in _TRUSTED:
             return False
-        self._ensure_tables()
-        key = tuple(t._version for t in self._params())
-        if key == self._key:
+        if not self.stale():
             return False
         lib.call("vdn_weightnorm_materialize", lib.ptr(self.wn_table), self._n_wn, self.max_rows, stream)
         lib.call("vdn_build_images", lib.ptr(self.chunk_table), self._n_ch, stream)
-        self._key = key
-        self.builds += 1
+        self.mark_fresh()
         return True
 
 
@@ -244,7 +322,8 @@ def refresh_together(images, stream, cache):
     network at once: 2 launches instead of 2 per network. `cache` (a dict) keeps the concatenated tables."""
     for im in images:
         im._ensure_tables()
-    key = tuple(im.wn_table.data_ptr() for im in images)
+    # (keyed by what the tables hold, not by where they lie: a rebuilt table may land on the address of one freed earlier)
+    key = tuple(im.tables_gen for im in images)
     if cache.get("key") != key:
         cache["key"] = key
         cache["wn"] = torch.cat([im.wn_table for im in images])
@@ -254,8 +333,7 @@ def refresh_together(images, stream, cache):
     lib.call("vdn_weightnorm_materialize", lib.ptr(cache["wn"]), cache["n_wn"], cache["max_rows"], stream)
     lib.call("vdn_build_images", lib.ptr(cache["ch"]), cache["n_ch"], stream)
     for im in images:
-        im._key = tuple(t._version for t in im._params())
-        im.builds += 1
+        im.mark_fresh()
 
 
 # ---------------------------------------------------------------------------------------------

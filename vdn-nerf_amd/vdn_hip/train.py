@@ -357,7 +357,8 @@ class TrainEngine:
             raise ValueError("all networks of a renderer must share one precision, got %s" % sorted(precs))
         self.precision = precs.pop()
         self.sfx = "_f32" if self.precision == "fp32" else "_bf16"
-        sdt = torch.float32 if self.precision == "fp32" else torch.bfloat16     # MLP-internal workspaces
+        self._fmt = images.FMT_F32 if self.precision == "fp32" else images.FMT_BF16
+        sdt =torch.float32 if self.precision == "fp32" else torch.bfloat16     # MLP-internal workspaces
         f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         fs = lambda *shape: torch.empty(*shape, dtype=sdt, device=dev)
         P, Q, N, T = self.P, self.Q, self.N, self.T
@@ -555,6 +556,9 @@ class TrainEngine:
             net.img = net.module._images(join=before_heads is None)           # refresh weight images if parameters changed
         if self._ptr_key() != self._param_ptrs:
             raise RuntimeError("parameters were re-allocated after the training engine was built; rebuild it")
+        if any(net.img.fmt != self._fmt for net in self.nets.values()):
+            # (its kernels, workspaces and weight-gradient tables are those of one precision; the images just fetched are the new one's)
+            raise RuntimeError("a network's precision changed after the training engine was built (%s); rebuild it" % self.precision)
         sample_dist = 2.0 / r.n_samples
         O = r.n_outside
         # without a background pass (n_outside = 0) render_core does not blend with inside_sphere (renderer.py:289): every
