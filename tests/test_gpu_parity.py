@@ -1012,6 +1012,41 @@ def test_render_plan_replays_equal_render_calls(wdepth):
 
 
 @pytest.mark.gpu
+def test_render_plan_follows_the_switches(monkeypatch):
+    """A RenderPlan keys on the run-time switches that select launches on the inference path (vdn_hip/switches.py, region
+    "render"): called after one of them changed it captures again, and replays exactly what render() beside it launches under
+    that setting; a switch outside the region leaves the captured graph alone. 8 rays x 128 samples: one workgroup per ray in
+    the fused shading launch, 1 024 points in the four launches of its VDN_SHADE_FUSED=0 arm."""
+    from vdn_train import synth, factory
+    dev = torch.device("cuda:0")
+    for name in ("VDN_SHADE_FUSED", "VDN_RENDER_ENGINES"):
+        monkeypatch.delenv(name, raising=False)
+    rend = factory.build_renderer(wdepth=False, device=dev, states=synth.make_all_states(3), precision="bf16")
+    kw = dict(background_rgb=torch.ones(1, 3, device=dev), cos_anneal_ratio=0.7, perturb_overwrite=0)
+    o, d = synth.random_pixel_batch(3, 0, 0, 8, rank=0)
+    near, far = synth.near_far_from_sphere(o, d)
+    b = tuple(torch.tensor(x).to(dev) for x in (o, d, near, far))
+
+    def plan_equals_render(captures):
+        got = {k: v.clone() for k, v in plan(*b).items() if v is not None}
+        assert plan.captures == captures
+        want = rend.render(*b, **kw)
+        for k, v in got.items():
+            assert torch.equal(v, want[k]), (captures, k)
+    with torch.no_grad():
+        plan = rend.plan(8, **kw)
+        assert rend.shade_launches() == 1
+        plan_equals_render(1)
+        monkeypatch.setenv("VDN_SHADE_FUSED", "0")
+        assert rend.shade_launches() == 4
+        plan_equals_render(2)
+        monkeypatch.delenv("VDN_SHADE_FUSED")
+        plan_equals_render(3)
+        monkeypatch.setenv("VDN_RENDER_ENGINES", "1")
+        plan_equals_render(3)
+
+
+@pytest.mark.gpu
 def test_small_sdf_passes_equal_the_large_kernel_bit_for_bit():
     """vdn_sdf_mlp_fwd_bf16(mode 0) routes launches of <= 8192 points (the sampler's up-sampling passes, renderer.py:352-372)
     to the feature-split kernel (csrc/k_sdf_fwd0_split.h) and larger ones to the 128-point kernel: same values, bit for bit,

@@ -10,13 +10,12 @@ Extra, optional keyword arguments (not in the reference): `t_rand` [B,1] and `t_
 [B,n_outside] inject the two uniform draws of renderer.py:348,355; `z_vals_inject` [B,N] skips the
 hierarchical sampler. They exist for parity tests (hard part 6).
 """
-import os
-
 import numpy as np
 import torch
 
-from vdn_hip import lib
-from vdn_hip.train import PLAN_STATE          # engine attributes a replayed forward restores as its capture left them
+from vdn_hip import lib, switches
+# PLAN_STATE: engine attributes a replayed forward restores as its capture left them; background_active: re-exported
+from vdn_hip.train import PLAN_STATE, background_active          # noqa: F401
 from dpt_models.fields import _require_gpu, _stream
 
 
@@ -53,7 +52,7 @@ def parse_sparse(sparse, method=None):
     values vdn_hip.mesh.check_sparse_options declines, and on sparse together with method "tets". Touches no device."""
     from vdn_hip import mesh
     if sparse is None or sparse is False:
-        env = os.environ.get("VDN_MESH_SPARSE", "")
+        env = switches.text("VDN_MESH_SPARSE")
         if env in ("", "0"):
             return None
         if env == "1":
@@ -76,7 +75,7 @@ def parse_sparse(sparse, method=None):
     else:
         raise ValueError("sparse must be None, a bool or a dict, got %r" % (sparse,))
     opts = dict(zip(mesh.SPARSE_KEYS, mesh.check_sparse_options(**opts)))
-    if (method or os.environ.get("VDN_MESH_METHOD", "cubes")) == "tets":
+    if (method or switches.text("VDN_MESH_METHOD")) == "tets":
         raise ValueError("sparse extraction is marching cubes only: method='tets' cannot be combined with it")
     return opts
 
@@ -92,7 +91,7 @@ def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, me
     SparseExtractionError where the surface is seen to leave the evaluated bricks."""
     from vdn_hip import mesh
     opts = parse_sparse(sparse, method)
-    method = method or os.environ.get("VDN_MESH_METHOD", "cubes")
+    method = method or switches.text("VDN_MESH_METHOD")
     if method not in ("cubes", "tets"):
         raise ValueError("method must be 'cubes' or 'tets', got %r" % (method,))
     if opts is not None:
@@ -109,36 +108,7 @@ def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, me
     return vertices, triangles.cpu().numpy()
 
 
-_FUSE_ROUNDS = __import__("os").environ.get("VDN_FUSE_ROUNDS", "1") != "0"      # A/B switch: vdn_merge_upsample vs the two launches
-
-
-def fuse_sdf_rounds():
-    """VDN_FUSE_SDF_ROUNDS=0: the sampler's rounds as two launches each (SDF pass, merge + up-sample) instead of one."""
-    import os
-    return os.environ.get("VDN_FUSE_SDF_ROUNDS", "1") != "0"
-
-
-def bg_compaction():
-    """VDN_BG_COMPACT=0 evaluates every background sample as the reference does (A/B switch for the parity tests)."""
-    import os
-    return os.environ.get("VDN_BG_COMPACT", "1") != "0"
-
-
-def background_active(rays_o, rays_d, mid_z, T, out=None):
-    """The background samples render_core does not multiply by zero (vdn_background_active, include/vdn_render.h):
-    -> (idx int32 [B*T], n int32 [1]) on the device. Inside-sphere samples get weight (1 - inside_sphere) = 0 for the
-    NeRF++ output (renderer.py:284-299), so the background network skips them - same outputs, same gradients."""
-    B, N = mid_z.shape
-    dev = mid_z.device
-    if out is None:
-        out = (torch.empty(B * T, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-               torch.empty(B, dtype=torch.int32, device=dev))
-    a = lib.VdnBackgroundActiveArgs()
-    a.rays_o, a.rays_d, a.mid_z = rays_o.data_ptr(), rays_d.data_ptr(), mid_z.data_ptr()
-    a.B, a.N, a.T = B, N, T
-    a.active_idx, a.n_active, a.ray_counts = out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()
-    lib.call("vdn_background_active", a, _stream())
-    return out[0], out[1]
+_FUSE_ROUNDS = switches.flag("VDN_FUSE_ROUNDS")      # A/B switch: vdn_merge_upsample vs the two launches
 
 
 class _RenderCoreFn(torch.autograd.Function):
@@ -157,7 +127,7 @@ class _RenderCoreFn(torch.autograd.Function):
         # list's complement delivers `sdf` / `normals` there (rest_normals). Same outputs bit for bit; parameter gradients differ
         # by the dW summation order. backward() below re-runs the forward on every sample in the one case that needs the saves
         # everywhere: a loss on `gradients` or `cdf_fine` (the reference's own loss uses neither, dpt_runner.py:215-243).
-        ctx.skipped = not ctx.ray_grads and os.environ.get("VDN_RENDER_FG_COMPACT", "1") != "0"
+        ctx.skipped = not ctx.ray_grads and switches.flag("VDN_RENDER_FG_COMPACT")
         ctx.fwd_args = (bgc, car)
         # a _TrainPlan (below): sampler + this forward were captured once as a HIP graph on the plan's fixed input buffers
         # (rays_o ... z_out ARE those buffers); one replay instead of ~20 launches issued from Python
@@ -228,11 +198,6 @@ class _RenderCoreFn(torch.autograd.Function):
         return (None,) + rays + (None, None) + tuple(flat)
 
 
-# environment switches that select launches inside the captured region: a plan is valid for one setting of them
-_PLAN_ENV = ("VDN_RENDER_FG_COMPACT", "VDN_FG_COMPACT", "VDN_BG_COMPACT", "VDN_FUSED_PREP", "VDN_TRAIN_COLOR_FUSED", "VDN_SDF_TAIL",
-             "VDN_SDF_TAIL_ROW0", "VDN_SDF_TAIL_MAX", "VDN_BWD_SPLIT_DW", "VDN_SDF_BWD_SPLIT", "VDN_FUSE_ROUNDS", "VDN_FUSE_SDF_ROUNDS")
-
-
 class _OneStreamCapture:
     """Inside a capture: the engine's side-stream roles point at the capturing stream, so the graph is one chain of the same
     launches, in the order they were issued, instead of forking into parallel branches. The HIP runtime can fail replaying a
@@ -281,7 +246,7 @@ class _TrainPlan:
         self._dst = [self.rays_o, self.rays_d, self.near, self.far] + ([self.bgc] if has_bg else []) + \
                     ([self.t_rand] + ([self.t_rand_out] if O > 0 else []) if inject else [])
         self.bwd = {}
-        skip = os.environ.get("VDN_RENDER_FG_COMPACT", "1") != "0"
+        skip = switches.flag("VDN_RENDER_FG_COMPACT")
         g = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(g), _OneStreamCapture(eng):
             z, z_out = rend._sample(self.rays_o, self.rays_d, self.near, self.far, perturb, self.t_rand, self.t_rand_out, None)
@@ -350,7 +315,7 @@ class NeuSRenderer:
         so an UNCHANGED dpt_runner.py runs on the bf16 kernels with `VDN_PRECISION=bf16 python dpt_runner.py ...`, or with the line
         `precision = bf16` in the conf's `model.neus_renderer` block (the runner splats that block into this constructor)."""
         if precision is None:
-            precision = os.environ.get("VDN_PRECISION", "").strip().lower() or None
+            precision = switches.text("VDN_PRECISION")
         if precision is not None:
             if precision not in ("fp32", "bf16"):
                 raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
@@ -488,7 +453,7 @@ class NeuSRenderer:
                     u.new_z, u.inv_s, u.B, u.M, u.ld, u.n_imp = new_z.data_ptr(), float(64 * 2 ** i), B, M, N, n_imp
                     return u
                 # first pass (renderer.py:369-370) and first round, in one launch where the kernel covers the shape
-                if not (_FUSE_ROUNDS and fuse_sdf_rounds() and self.sdf_network._run_first((rays_o, rays_d, z[:, :S]), sdf[:, :S], upsample_args(0, M))):
+                if not (_FUSE_ROUNDS and switches.flag("VDN_FUSE_SDF_ROUNDS") and self.sdf_network._run_first((rays_o, rays_d, z[:, :S]), sdf[:, :S], upsample_args(0, M))):
                     self.sdf_network._run(0, rays=(rays_o, rays_d, z[:, :S]), sdf_out=sdf[:, :S])
                     lib.call("vdn_upsample_round", upsample_args(0, M), st)
                 for i in range(self.up_sample_steps):
@@ -499,7 +464,7 @@ class NeuSRenderer:
                     if not last:
                         m.sdf, m.new_sdf, m.sdf_out = sdf.data_ptr(), new_sdf.data_ptr(), sdf.data_ptr()
                         # the whole round in one launch where the kernel covers the shape (bf16, 16 new samples per ray)
-                        if _FUSE_ROUNDS and fuse_sdf_rounds() and self.sdf_network._run_round(
+                        if _FUSE_ROUNDS and switches.flag("VDN_FUSE_SDF_ROUNDS") and self.sdf_network._run_round(
                                 (rays_o, rays_d, new_z), new_sdf, m, upsample_args(i + 1, M + n_imp)):
                             M += n_imp
                             continue
@@ -561,7 +526,7 @@ class NeuSRenderer:
         params = self._all_parameters()
         differentiable = torch.is_grad_enabled() and (attached is not None or any(p.requires_grad for p in params))
         # inference with the background work list: the last round's merge rides in vdn_train_prep (as in the training engine)
-        defer = (not differentiable) and O > 0 and bg_compaction()
+        defer = (not differentiable) and O > 0 and switches.flag("VDN_BG_COMPACT")
         if differentiable:
             # an optimizer step changed every network at once: ONE weight-norm launch and ONE image-build launch for all of
             # them here instead of two per network as each is first used (vdn_hip/images.py::refresh_together)
@@ -594,7 +559,7 @@ class NeuSRenderer:
                 _images.trust(None)
         z, z_out = self._sample(rays_o, rays_d, near, far, perturb, t_rand, t_rand_out, z_vals_inject, defer_last_merge=defer)
         bg_density = bg_rgb = bg_feat = bg_dists = bg_mid = None
-        if O > 0 and bg_compaction():
+        if O > 0 and switches.flag("VDN_BG_COMPACT"):
             # z_feed (renderer.py:390-391), both section sets and the background work list in two launches (vdn_train_prep)
             f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
             z = z.contiguous()
@@ -743,7 +708,7 @@ class NeuSRenderer:
         workgroup per ray), the shipped 'idr' colour head (d_feature 256, d_out 3), both networks in one precision; a VDN head's 96
         channels keep their own two launches behind it. VDN_SHADE_FUSED=0 forces the separate launches (SDF / colour / compositor / eikonal reduce)."""
         cn, sn = self.color_network, self.sdf_network
-        return (os.environ.get("VDN_SHADE_FUSED", "1") != "0" and N == 128 and not depth_before_color
+        return (switches.flag("VDN_SHADE_FUSED") and N == 128 and not depth_before_color
                 and sn.precision == cn.precision and sn.precision in ("bf16", "fp32") and cn.conf.get("mode") == "idr"
                 and cn.conf.get("d_feature") == 256 and cn.conf.get("d_out") == 3)
 
@@ -813,7 +778,7 @@ class NeuSRenderer:
                 del engines[k]
             # VDN_RENDER_ENGINES=1..3 (default 3) bounds how many stay alive: on a smaller or shared device one engine per renderer
             # is the round-4 memory footprint, at the price of rebuilding when the batch size changes
-            keep = min(3, max(1, int(os.environ.get("VDN_RENDER_ENGINES", "3") or 3)))
+            keep = switches.integer("VDN_RENDER_ENGINES")
             while len(engines) >= keep:
                 del engines[next(iter(engines))]             # (dicts keep insertion order: the least recently used one)
             eng = TrainEngine(self, B, dev)
@@ -823,13 +788,14 @@ class NeuSRenderer:
     def _plan_for(self, eng, background_rgb, perturb, t_rand, t_rand_out):
         """The _TrainPlan of this call's configuration, or None (first call with the configuration, graphs off, jitter injected
         only in part, a capture already in progress)."""
-        if os.environ.get("VDN_RENDER_GRAPHS", "1") == "0" or torch.cuda.is_current_stream_capturing():
+        if not switches.flag("VDN_RENDER_GRAPHS") or torch.cuda.is_current_stream_capturing():
             return None
         O = self.n_outside
         inject = t_rand is not None or t_rand_out is not None
         if inject and (t_rand is None or (O > 0 and t_rand_out is None) or perturb <= 0):
             return None
-        key = (background_rgb is not None, float(perturb), inject, tuple(os.environ.get(k) for k in _PLAN_ENV))
+        # (the switches that select launches inside the captured region: a plan is valid for one setting of them)
+        key = (background_rgb is not None, float(perturb), inject, switches.signature("train"))
         plans = eng.__dict__.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -966,11 +932,12 @@ class RenderPlan:
 
     def _signature(self):
         """What the graph's nodes hold by raw pointer or took a launch decision on: every parameter's storage and object (the
-        compositor reads the variance itself; the weight images follow the others), and each network's NetImages object (its
-        blobs and effective weights) and precision (the kernels that were captured)."""
+        compositor reads the variance itself; the weight images follow the others), each network's NetImages object (its
+        blobs and effective weights) and precision (the kernels that were captured), and the run-time switches that select
+        launches on the inference path (vdn_hip/switches.py, region "render")."""
         ps = self.renderer._all_parameters()
         return (tuple(p.data_ptr() for p in ps), tuple(map(id, ps)),
-                tuple((id(m.__dict__.get("_img")), m.precision) for m in self._nets()))
+                tuple((id(m.__dict__.get("_img")), m.precision) for m in self._nets()), switches.signature("render"))
 
     def __call__(self, rays_o, rays_d, near, far):
         if rays_o.shape[0] != self.batch:
@@ -978,8 +945,8 @@ class RenderPlan:
         for m in self._nets():
             m._images()                                       # re-materialise the weight images if a parameter changed
         if self._signature() != self._captured:
-            # a parameter moved (module.to(...), p.data = t, a Trainer built on the renderer) or was replaced, or a network
-            # switched precision: the captured pointers are stale - capture again, never replay them
+            # a parameter moved (module.to(...), p.data = t, a Trainer built on the renderer) or was replaced, a network
+            # switched precision, or a switch selects other launches than the captured ones: capture again, never replay them
             with torch.no_grad():                             # (the plan is the inference path, whatever the caller's grad mode)
                 self._capture()
         self.o.copy_(rays_o.detach())

@@ -10,13 +10,15 @@ import subprocess
 import sys
 import time
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 # VDN_BUILD_VARIANT="name:-DFLAG=..": a side copy of the whole library built with extra flags (objects in _build_<name>,
 # libvdn_render_<name>.so) for same-box A/B runs of compile-time switches through VDN_LIB (development only)
-_VARIANT = os.environ.get("VDN_BUILD_VARIANT", "")
+_VARIANT = switches.text("VDN_BUILD_VARIANT")
 _VNAME, _VFLAGS = (_VARIANT.split(":", 1) + [""])[:2] if _VARIANT else ("", "")
 OBJDIR = os.path.join(HERE, "_build" + ("_" + _VNAME if _VNAME else ""))
 LIB = os.path.join(HERE, "libvdn_render%s.so" % ("_" + _VNAME if _VNAME else ""))

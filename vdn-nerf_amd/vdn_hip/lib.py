@@ -10,11 +10,13 @@ import re
 
 import numpy as np
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 HEADER = os.path.join(os.path.dirname(PKG), "include", "vdn_render.h")
 # (VDN_LIB: another build of the same library, for A/B timing of compile-time switches inside one gpurun call; development only)
-LIB_PATH = os.environ.get("VDN_LIB") or os.path.join(HERE, "libvdn_render.so")
+LIB_PATH = switches.text("VDN_LIB") or os.path.join(HERE, "libvdn_render.so")
 
 _SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "int": ctypes.c_int, "double": ctypes.c_double}
 

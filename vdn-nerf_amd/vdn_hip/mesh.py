@@ -25,12 +25,11 @@ patch of a per-face atlas, texel_points / project_points place a surface point u
 colours into the atlas, bake_texture is the three in a row; sample_texture looks an atlas up at points of the mesh and
 render_textured_view does that where rays hit."""
 import math
-import os
 
 import numpy as np
 import torch
 
-from . import lib
+from . import lib, switches
 
 
 def marching_tets(u, threshold=0.0):
@@ -686,7 +685,7 @@ def fused_point_shading(renderer):
     """True where vdn_shade_points_bf16 (csrc/k_sdf_fwd2.h MODE 4) covers the configuration: both networks on the bf16 kernels and
     the colour head the "c2" stream exists for ('idr', d_feature 256, d_out 3). VDN_SHADE_POINTS_FUSED=0 forces the separate launches."""
     sn, cn = renderer.sdf_network, renderer.color_network
-    return (os.environ.get("VDN_SHADE_POINTS_FUSED", "1") != "0" and sn.precision == "bf16" and cn.precision == "bf16"
+    return (switches.flag("VDN_SHADE_POINTS_FUSED") and sn.precision == "bf16" and cn.precision == "bf16"
             and cn.conf.get("mode") == "idr" and cn.conf.get("d_feature") == 256 and cn.conf.get("d_out") == 3)
 
 

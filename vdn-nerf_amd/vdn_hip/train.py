@@ -8,14 +8,12 @@ activation the adjoint needs kept in HBM; backward() runs
   -> one batched weight-gradient GEMM -> finalize/scatter -> weight-norm backward
 and returns d loss / d parameter for every parameter, in module.parameters() order.
 """
-import os
-
 import numpy as np
 import torch
 
-from . import images, layout, lib
+from . import images, layout, lib, switches
 
-PTS_PER_SPLIT = int(os.environ.get("VDN_DW_SPLIT_PTS", "4096"))        # rows one workgroup of the weight-gradient GEMM contracts
+PTS_PER_SPLIT = switches.integer("VDN_DW_SPLIT_PTS")        # rows one workgroup of the weight-gradient GEMM contracts
 
 
 def _pts_per_split(net, precision="bf16"):
@@ -28,16 +26,32 @@ def _pts_per_split(net, precision="bf16"):
     if precision == "fp32":
         # the fp32 GEMM is MFMA-bound (128 x 128 tiles), not HBM-bound: more, shorter splits balance better (2048 / 2048: 8.27 ms per
         # step against 8.60 at 4096 and 8.77 at 6144 / 4096; 1024: 8.32; tools/dev/step_wall.py ... fp32, same box)
-        dflt = "2048"
-        return int(os.environ.get("VDN_DW_SPLIT_PTS_SDF" if net == "sdf" else "VDN_DW_SPLIT_PTS_REST", dflt))
+        return switches.integer("VDN_DW_SPLIT_PTS_SDF" if net == "sdf" else "VDN_DW_SPLIT_PTS_REST", 2048)
     if net == "sdf":
-        return int(os.environ.get("VDN_DW_SPLIT_PTS_SDF", os.environ.get("VDN_DW_SPLIT_PTS", "6144")))
+        return switches.integer("VDN_DW_SPLIT_PTS_SDF", switches.raw("VDN_DW_SPLIT_PTS", 6144))
     # the rest group runs as two launches on the default schedule: the background network's entries and the heads'
-    rest = os.environ.get("VDN_DW_SPLIT_PTS_REST", str(PTS_PER_SPLIT))
-    return int(os.environ.get("VDN_DW_SPLIT_PTS_NERF" if net == "nerf" else "VDN_DW_SPLIT_PTS_HEADS", rest))
+    rest = switches.raw("VDN_DW_SPLIT_PTS_REST", PTS_PER_SPLIT)
+    return switches.integer("VDN_DW_SPLIT_PTS_NERF" if net == "nerf" else "VDN_DW_SPLIT_PTS_HEADS", rest)
 
 
 _stream = lib.stream_handle          # the HIP handle of torch's current stream
+
+
+def background_active(rays_o, rays_d, mid_z, T, out=None):
+    """The background samples render_core does not multiply by zero (vdn_background_active, include/vdn_render.h):
+    -> (idx int32 [B*T], n int32 [1]) on the device. Inside-sphere samples get weight (1 - inside_sphere) = 0 for the
+    NeRF++ output (renderer.py:284-299), so the background network skips them - same outputs, same gradients."""
+    B, N = mid_z.shape
+    dev = mid_z.device
+    if out is None:
+        out = (torch.empty(B * T, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev))
+    a = lib.VdnBackgroundActiveArgs()
+    a.rays_o, a.rays_d, a.mid_z = rays_o.data_ptr(), rays_d.data_ptr(), mid_z.data_ptr()
+    a.B, a.N, a.T = B, N, T
+    a.active_idx, a.n_active, a.ray_counts = out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr()
+    lib.call("vdn_background_active", a, _stream())
+    return out[0], out[1]
 
 
 _SHARED_STREAMS = {}
@@ -330,7 +344,7 @@ class TrainEngine:
         # stream, e.g. for a rocprof kernel trace: concurrent kernels inflate each other's durations there). It pays since the
         # bf16 SDF kernel runs one 128-point workgroup per CU: a work list of ~50 K rows is 1.5 rounds of workgroups, and the
         # half-empty round's CUs take the background network's workgroups (measured: 1.78 -> 1.65 ms per step).
-        use_side = os.environ.get("VDN_SIDE_STREAM", "1") == "1" and torch.device(dev).type == "cuda"
+        use_side = switches.flag("VDN_SIDE_STREAM") and torch.device(dev).type == "cuda"
         self._side = shared_stream(dev, "side") if use_side else None
         self._ev_fork = torch.cuda.Event() if use_side else None
         self._ev_join = torch.cuda.Event() if use_side else None
@@ -397,7 +411,7 @@ class TrainEngine:
         # 1-bit ReLU masks of the heads' and the background network's hidden layers (bf16; csrc/mlp_engine.h: BF16::relu_bits, decoded
         # by layout.mask_from_plane): the forwards write them beside the bf16 planes, the backward chains read them instead of the
         # planes (which the weight-gradient GEMM still reads). VDN_RELU_MASK=0: not written, the chains read the planes
-        self.relu_mask = self.precision == "bf16" and os.environ.get("VDN_RELU_MASK", "1") != "0"
+        self.relu_mask = self.precision == "bf16" and switches.flag("VDN_RELU_MASK")
         fm = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev) if self.relu_mask else None
         w["col_mask"] = fm(4, Pp * 32)
         if self.wdepth:
@@ -563,7 +577,7 @@ class TrainEngine:
         O = r.n_outside
         # without a background pass (n_outside = 0) render_core does not blend with inside_sphere (renderer.py:289): every
         # foreground sample counts, nothing may be skipped
-        self._fg_compact = bool(skip_far) and O > 0 and os.environ.get("VDN_FG_COMPACT", "1") != "0"
+        self._fg_compact = bool(skip_far) and O > 0 and switches.flag("VDN_FG_COMPACT")
         # VDN_TRAIN_COLOR_FUSED=1 (bf16; OFF by default): the colour head rides in the SDF kernel's launch (csrc/k_sdf_fwd2.h MODE 3: the
         # feature vector stays in registers, the head's saved planes are written from there) - one launch and one trip of the
         # feature plane less, and measured SLOWER in the step: same-box A/B, three alternating runs, 1 141 / 1 138 / 1 121 us against
@@ -572,11 +586,10 @@ class TrainEngine:
         # chip with the background network at no such price; and the join with the side stream's update of the head's weights
         # has to move in front of the SDF kernel. Not with ray gradients (U_pe), the depth_before_color input, or the tail split.
         self._color_fused = (self.precision == "bf16" and not self.dbc and not ray_grads and "c2" in self.nets["color"].img.blobs
-                             and r.color_network.conf["d_out"] == 3 and os.environ.get("VDN_TRAIN_COLOR_FUSED", "0") == "1"
+                             and r.color_network.conf["d_out"] == 3 and switches.flag("VDN_TRAIN_COLOR_FUSED")
                              and not self._tail_wanted())
-        from dpt_models.renderer import background_active, bg_compaction
-        self._bg_compact = O > 0 and bg_compaction()
-        fused_prep = self._bg_compact and os.environ.get("VDN_FUSED_PREP", "1") != "0"
+        self._bg_compact = O > 0 and switches.flag("VDN_BG_COMPACT")
+        fused_prep = self._bg_compact and switches.flag("VDN_FUSED_PREP")
         if pending_merge is not None and not fused_prep:
             # NeuSRenderer._sample(defer_last_merge=True) left the last round's samples unmerged: complete z here
             new_z, M_old = pending_merge
@@ -737,7 +750,7 @@ class TrainEngine:
     def _tail_wanted(self):
         """The tail split of the fused SDF forward (csrc/k_sdf_fwd1_split.h): on where there is no side stream, off with one."""
         tail_default = "1" if self._side is None else "0"
-        return (self.precision == "bf16" and self._fg_compact and os.environ.get("VDN_SDF_TAIL", tail_default) != "0"
+        return (self.precision == "bf16" and self._fg_compact and switches.flag("VDN_SDF_TAIL", tail_default)
                 and not self._ray_grads)
 
     def _sdf_args(self, rays_o, rays_d, feat):
@@ -793,10 +806,10 @@ class TrainEngine:
         tail = self._tail_wanted()
         fused = self._color_fused and not tail
         if tail:
-            row0 = int(os.environ.get("VDN_SDF_TAIL_ROW0", str(128 * torch.cuda.get_device_properties(self.dev).multi_processor_count)))
+            row0 = switches.integer("VDN_SDF_TAIL_ROW0", 128 * torch.cuda.get_device_properties(self.dev).multi_processor_count)
             tail = self.P > row0
             if tail:
-                s.tail_row0, s.tail_max_rows = row0, int(os.environ.get("VDN_SDF_TAIL_MAX", "8192"))
+                s.tail_row0, s.tail_max_rows = row0, switches.integer("VDN_SDF_TAIL_MAX")
 
         def launch():
             if fused:
@@ -986,7 +999,7 @@ class TrainEngine:
             # render()'s autograd node (no deferred half): the background network's weight gradients follow its backward on the side
             # stream, beside the heads' and the SDF network's backward on the caller's, instead of waiting in one GEMM launch for
             # all groups behind everything else (the Trainer's schedule, DESIGN.md 3d, minus its deferral past the step's end)
-            split_dw = (not defer_rest and self._side is not None and not rg and os.environ.get("VDN_BWD_SPLIT_DW", "1") != "0"
+            split_dw = (not defer_rest and self._side is not None and not rg and switches.flag("VDN_BWD_SPLIT_DW")
                         and all(k in self.groups for k in ("sdf", "heads", "nerf")))
             if split_dw:
                 self.weight_grads("nerf", self._side.cuda_stream)
@@ -1036,7 +1049,7 @@ class TrainEngine:
         rb.s_from_h = s_from_h
         # bf16 without ray gradients: both chains in one feature-split launch (csrc/k_sdf_bwd_split.h: ex_l never leaves the chip;
         # 218 us against 165 + 140 at the steady-state lists, the step -43 us). VDN_SDF_BWD_SPLIT=0: the two kernels
-        one_launch = self.precision == "bf16" and not rg and os.environ.get("VDN_SDF_BWD_SPLIT", "1") != "0"
+        one_launch = self.precision == "bf16" and not rg and switches.flag("VDN_SDF_BWD_SPLIT")
         fb = lib.VdnSdfFbarArgs()
         fb.blob = img.blobs["fbar"].data_ptr()
         fb.g_sdf, fb.g_feat, fb.S, fb.EX, fb.AB = w["d_sdf"].data_ptr(), w["d_featvec"].data_ptr(), s_planes.data_ptr(), w["EX"].data_ptr(), w["AB"].data_ptr()

@@ -13,10 +13,10 @@ Equivalence with one process on the concatenated batch:
 so each rank back-propagates its colour term scaled by 1/W and its eikonal numerator against the
 GLOBAL denominator; summing the ranks' gradients gives d loss_global / d theta.
 """
-import os
-
 import torch
 import torch.distributed as dist
+
+from vdn_hip import switches
 
 
 # The second communicator (same ranks as the world) is made ONCE per process and shared by every Trainer on the world group
@@ -76,7 +76,7 @@ class Collectives:
         # VDN_DP_SIDE_GROUP=0: one group for all.
         self.side_group = group if side_group is None else side_group
         whole_world = group is None or (dist.is_initialized() and group is dist.group.WORLD)
-        if self.enabled and side_group is None and whole_world and os.environ.get("VDN_DP_SIDE_GROUP", "1") != "0":
+        if self.enabled and side_group is None and whole_world and switches.flag("VDN_DP_SIDE_GROUP"):
             self.side_group = shared_side_group()
         # The gradient slices are summed IN the stream that made them (sum_now: torch.distributed's blocking form enqueues the
         # RCCL kernel on the current stream - no hop to the backend's stream and back, i.e. two marker packets and two queue
@@ -86,7 +86,7 @@ class Collectives:
         # without collectives 1 137 - 1 149 us, through the backend's stream 1 192 - 1 221, in-stream 1 174 - 1 190; a third
         # communicator for the small sums (1 215 - 1 227) and the small sums in-stream too (no different) are not kept.
         # VDN_DP_INSTREAM=0: every sum through begin / finish.
-        self.instream = self.enabled and os.environ.get("VDN_DP_INSTREAM", "1") != "0"
+        self.instream = self.enabled and switches.flag("VDN_DP_INSTREAM")
         self.timing = False         # bench.py: HIP events around finish() -> exposed wait per tag
         self._timed = {}
 

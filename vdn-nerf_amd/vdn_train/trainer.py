@@ -18,13 +18,12 @@ schedule (overlap=False) bit for bit: the same launches on the same data, only o
 """
 import ctypes
 import math
-import os
 import weakref
 
 import numpy as np
 import torch
 
-from vdn_hip import images, lib
+from vdn_hip import images, lib, switches
 from vdn_hip.train import TrainEngine
 from vdn_train import dp
 
@@ -145,7 +144,7 @@ class Trainer:
         if self.coll.enabled:
             self.coll.broadcast(self._param_flat, 0)     # replicas must start from rank 0's parameters (e.g. per-process random init)
         self.engine = TrainEngine(renderer, batch_size, self.dev)
-        self.overlap = (os.environ.get("VDN_OVERLAP", "1") != "0") if overlap is None else bool(overlap)
+        self.overlap = switches.flag("VDN_OVERLAP") if overlap is None else bool(overlap)
         self._ev_gemm, self._ev_rest, self._ev_tail = (torch.cuda.Event() for _ in range(3))
         self._ev_comp, self._ev_log, self._log_stream = torch.cuda.Event(), torch.cuda.Event(), None
         self._ev_ws, self._ws_pending = torch.cuda.Event(), False      # the side stream's last reader of the forward's workspaces
@@ -502,9 +501,9 @@ class Trainer:
         # the step preparation and long done when the compositor needs it; the global numerator is only needed for the scalars, on the
         # logging stream. (VDN_DP_FUSED=0: compositor, early eikonal all-reduce, loss kernel and adjoint as separate launches.)
         dp = self.coll.enabled
-        fusable = (mask is None and self.conf["mask_weight"] == 0.0 and os.environ.get("VDN_FUSED_COMPOSITE", "1") != "0"
-                   and (not dp or (os.environ.get("VDN_DP_FUSED", "1") != "0" and r.n_outside > 0
-                                   and os.environ.get("VDN_FG_COMPACT", "1") != "0")))
+        fusable = (mask is None and self.conf["mask_weight"] == 0.0 and switches.flag("VDN_FUSED_COMPOSITE")
+                   and (not dp or (switches.flag("VDN_DP_FUSED") and r.n_outside > 0
+                                   and switches.flag("VDN_FG_COMPACT"))))
         fuse = fusable and not eng.wdepth
         fl = dict(true_rgb=true_rgb, g_color=self.g_color, igr_weight=self.conf["igr_weight"], grad_scale=1.0 / self.world) if fuse else None
         # ... and with the VDN head in the loss (womsk_white_wdepth): the 96 feature channels keep their streaming launches, but the
@@ -612,11 +611,11 @@ class Trainer:
             images.refresh_together([eng.nets["sdf"].img], stream, self._img_cache.setdefault("sdf", {}))
 
         grad = eng._grad_flat
-        split = self.overlap and os.environ.get("VDN_SPLIT_REST", "1") != "0" and "nerf" in eng.groups and "heads" in eng.groups
+        split = self.overlap and switches.flag("VDN_SPLIT_REST") and "nerf" in eng.groups and "heads" in eng.groups
         # (events on the critical chain are marker packets, 3 - 4 us each: the side stream's fork reuses _ev_comp - nothing was
         # launched on this stream since; not with the VDN head, where the compositor's adjoint is still to come in backward() - the SDF GEMM's event is only recorded for the schedule that waits for it, and the heads'
         # event is covered by the `after` events below, which are recorded later on this stream)
-        trim = os.environ.get("VDN_EVENT_TRIM", "1") != "0"           # (0: the A/B arm that records them all)
+        trim = switches.flag("VDN_EVENT_TRIM")           # (0: the A/B arm that records them all)
         eng.backward(self.g_color, g_feats, g_weights, self.g_eik, defer_rest=True,
                      gemm_event=self._ev_gemm if (self.overlap and not (split and trim)) else None,
                      fork_event=self._ev_comp if (fused and not fused_wd and trim) else None, heads_event=not trim)
@@ -682,7 +681,7 @@ class Trainer:
         # stream would leave a step issued on another stream unordered.
         if self._rest_pending:
             cur = lib.current_stream()
-            if self._joined.get(cur.cuda_stream) != self._rest_gen or os.environ.get("VDN_EVENT_TRIM", "1") == "0":
+            if self._joined.get(cur.cuda_stream) != self._rest_gen or not switches.flag("VDN_EVENT_TRIM"):
                 cur.wait_event(self._ev_rest)
                 self._joined[cur.cuda_stream] = self._rest_gen
 

@@ -9,6 +9,8 @@ import os
 import numpy as np
 import torch
 
+from vdn_hip import switches
+
 
 def _render_batches(renderer, rays_gen, rays_o, rays_d, batch_size, jitter=None, **kw):
     """render() over the rays of one image in batches -> yields (first ray, n rays, outputs). With VDN_RENDER_GRAPH=1 the
@@ -18,7 +20,7 @@ def _render_batches(renderer, rays_gen, rays_o, rays_d, batch_size, jitter=None,
     torch.rand draws of render() (renderer.py:348,355) - how the parity tests reproduce the reference's runs."""
     n = rays_o.shape[0]
     plan = None
-    if os.environ.get("VDN_RENDER_GRAPH", "0") == "1" and n >= 2 * batch_size and jitter is None:
+    if switches.flag("VDN_RENDER_GRAPH") and n >= 2 * batch_size and jitter is None:
         plan = renderer.plan(batch_size, **kw)
     for b, s in enumerate(range(0, n, batch_size)):
         o, d = rays_o[s:s + batch_size], rays_d[s:s + batch_size]
