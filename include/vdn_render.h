@@ -375,6 +375,12 @@ int vdn_shade_fused_f32(const VdnSdfArgs* sdf_host, const VdnRenderNetArgs* colo
  * launched) ray-gradient saves (U_pe) and the tail split (tail_max_rows). */
 int vdn_sdf_color_train_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, void* col_h, void* col_small,
                              float* col_out, void* stream);
+/* ... with a two-class work list (VdnForegroundActiveArgs.n_inner): n_color_rows = n_inner + 1, a device row count of whole
+ * 128-row workgroups (or the whole list). Workgroups behind it write no col_h / col_small / col_out - the rows
+ * vdn_rendernet_fwd_bf16 leaves alone with that count as its n_active; the SDF side covers the whole list as before. They still
+ * run the head's chunk steps (one straight instruction stream per workgroup): the rows are skipped in memory, not in time. */
+int vdn_sdf_color_train_rows_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, void* col_h, void* col_small,
+                                  float* col_out, const int32_t* n_color_rows, void* stream);
 int vdn_shade_fused_bf16(const VdnSdfArgs* sdf_host, const void* color_blob, int32_t squeeze_out, const VdnCompositeArgs* comp_host,
                          int32_t* ticket, void* stream);
 /* Shading of free-standing points in ONE launch (bf16; csrc/k_sdf_fwd2.h MODE 4) - the vertex attributes of a mesh that goes to
@@ -441,6 +447,12 @@ typedef struct {
     /* bf16, optional: the forward's VdnRenderNetArgs.save_mask. Given, the ReLU' of the chain comes from it and save_h is not
      * read (it stays required: the weight-gradient GEMM reads it). fp32: must be NULL (-5). */
     const void* mask;
+    /* optional (appended), with a two-class work list (VdnForegroundActiveArgs.n_inner): n_active is then the first class's
+     * row count and n_rows_all the whole list's. On the rows [*n_active, *n_rows_all) the output adjoint is exactly zero,
+     * so every delta and input adjoint is: with acc_feat = 0 the workgroups there store +0.0 into d_feat (which the SDF
+     * backward and its weight-gradient entry read on every listed row) and return - no weight stream, no MFMA; with
+     * acc_feat = 1 they return at once (x + 0 = x). d_normals must accumulate (acc_normals = 1) and d_pts must be off (-6). */
+    const int32_t* n_rows_all;
 } VdnRenderNetBwdArgs;
 int vdn_rendernet_bwd_f32(const VdnRenderNetBwdArgs* args_host, void* stream);
 int vdn_rendernet_bwd_bf16(const VdnRenderNetBwdArgs* args_host, void* stream);   /* bf16-MFMA variant: bf16 chunk blob, bf16 activation workspaces */
@@ -579,6 +591,11 @@ int vdn_dw_gemm_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void*
  * kernel reads whole 32-row blocks and zeroes the rows beyond P itself); with two segments `splits` must be even (first
  * half = segment 1). One workgroup contracts one K split of a 256 x 256 output block. */
 int vdn_dw_gemm_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void* stream);
+/* ... with a launch-wide row cap: descriptors [cap_lo, cap_hi) of this launch contract over at most *cap_rows rows, on top of their
+ * own P / P_dev. The training engine caps the colour / VDN heads' entries at the rows the heads evaluated
+ * (VdnForegroundActiveArgs.n_inner[1]); the descriptor tables stay as they are. */
+int vdn_dw_gemm_rows_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, const int32_t* cap_rows, int cap_lo, int cap_hi, void* stream);
+int vdn_dw_gemm_rows_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, const int32_t* cap_rows, int cap_lo, int cap_hi, void* stream);
 /* workgroups one descriptor occupies in the launch (the two kernels tile differently); total_wgs = their sum */
 int vdn_dw_entry_wgs_f32(int m_tiles, int n_tiles, int splits);
 int vdn_dw_entry_wgs_bf16(int m_tiles, int n_tiles, int splits);
@@ -786,7 +803,16 @@ typedef struct {
                                 * `gradients` (dpt_models/renderer.py::_RenderCoreFn) */
     int32_t* active_idx;       /* [B*N] out */
     int32_t* n_active;         /* [1] out */
-    int32_t* ray_counts;       /* [B] scratch */
+    int32_t* ray_counts;       /* [B] scratch; [2B] with inner_radius */
+    /* Two-class list (appended to the struct; both zero: the list above, byte for byte; not with complement). The colour and the VDN head
+     * enter the loss only where inside_sphere = 1 (|p| < 1): with inner_radius = 1 the ids with |p| < inner_radius come
+     * first (ascending) and those with inner_radius <= |p| < radius behind them (ascending), so compact rows
+     * [0, n_inner[0]) are exactly the rows the heads need. n_active[0] stays the total; n_inner[1] = n_inner[0] rounded up
+     * to whole 128-row workgroups, capped at the total: the device-side row count of every kernel that runs on the first
+     * class only (all of them then touch the same rows). A NaN norm is in neither class. */
+    float inner_radius;
+    int32_t _pad_inner;
+    int32_t* n_inner;          /* [2] out */
 } VdnForegroundActiveArgs;
 
 /* The per-ray preparation of a training step in two launches instead of seven: z_feed = sort(cat(z, z_out))
@@ -808,6 +834,7 @@ typedef struct {
     float* bg_dists; float* bg_mid;        /* [B,T] out */
     int32_t* fg_active_idx; int32_t* fg_n_active; int32_t* fg_ray_counts;     /* as VdnForegroundActiveArgs, or NULL */
     int32_t* bg_active_idx; int32_t* bg_n_active; int32_t* bg_ray_counts;     /* as VdnBackgroundActiveArgs */
+    float fg_inner_radius; int32_t _pad_inner; int32_t* fg_n_inner;          /* as VdnForegroundActiveArgs (appended), or zero */
 } VdnTrainPrepArgs;
 int vdn_train_prep(const VdnTrainPrepArgs* args_host, void* stream);
 int vdn_foreground_active(const VdnForegroundActiveArgs* args_host, void* stream);

@@ -79,7 +79,10 @@ VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src&
                 eikonal_add(pn, g0, g1, g2, eik_num, eik_den);
                 a.cdf[q] = prev_cdf;
                 a.inside_sphere[q] = inside;
-                float c0 = src.color(q, i, 0), c1 = src.color(q, i, 1), c2 = src.color(q, i, 2);
+                // where inside = 0 the blend multiplies the colour head's output by an exact zero: the slot is not read (the head
+                // need not have written it; its outputs are sigmoid / ReLU values, so c * 0 is +0 like the 0 that stands in)
+                const bool heads = !has_bg || pn < 1.0f;
+                float c0 = heads ? src.color(q, i, 0) : 0.0f, c1 = heads ? src.color(q, i, 1) : 0.0f, c2 = heads ? src.color(q, i, 2) : 0.0f;
                 if (has_bg) {
                     const long qb = (long)r * T + i;
                     al = al * inside + bg_a * (1.0f - inside);                     // renderer.py:290
@@ -144,11 +147,12 @@ VDN_DEV RowOut composite_row(const CompositeArgs& a, int r, int lane, const Src&
 // ------------------------------------------------------------------------------------------
 struct FeatRaw { float fg[2], bg[2]; };      // what memory holds for the two channels: foreground / background feature (0 where absent)
 struct FeatPair { float f0, f1; };
+// inside: as feat_mix; where the blend gives the foreground feature weight 0 it is not read (+0 stands in: see composite_row)
 template <class A>
-VDN_DEV FeatRaw feat_load(const A& a, int r, int i, int ch0, int ch1) {
+VDN_DEV FeatRaw feat_load(const A& a, int r, int i, int ch0, int ch1, float inside) {
     const int N = a.N, T = a.T, C = a.feat_ch;
     const bool v0 = ch0 < C, v1 = ch1 < C;
-    const bool fg = i < N, bg = i < T && (a.bg_density != nullptr || i >= N) && a.bg_feat != nullptr;
+    const bool fg = i < N && (a.bg_density == nullptr || inside != 0.0f), bg = i < T && (a.bg_density != nullptr || i >= N) && a.bg_feat != nullptr;
     const long qf = ((long)r * N + i) * C, qb = ((long)r * T + i) * C;
     FeatRaw v;
     v.fg[0] = (fg && v0) ? a.feat[qf + ch0] : 0.0f;
@@ -168,7 +172,7 @@ VDN_DEV FeatPair feat_mix(const A& a, int i, const FeatRaw& v, float inside) {
 // blended feature pair of sample i
 template <class A>
 VDN_DEV FeatPair feat_pair(const A& a, int r, int i, int ch0, int ch1, float inside) {
-    return feat_mix(a, i, feat_load(a, r, i, ch0, ch1), inside);
+    return feat_mix(a, i, feat_load(a, r, i, ch0, ch1, inside), inside);
 }
 // ... of the 8 samples i0 .. i0+7 (those below i_end; zero behind), all 32 loads of the group issued before the first use: a plain
 // loop waits out one memory round trip per sample (160 us for 160 samples x 96 channels inside the per-ray kernel)
@@ -176,7 +180,7 @@ template <class A>
 VDN_DEV void feat_group(const A& a, int r, int i0, int i_end, int ch0, int ch1, const float (&inside)[8], FeatPair (&f)[8]) {
     FeatRaw v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = i0 + k < i_end ? feat_load(a, r, i0 + k, ch0, ch1) : FeatRaw{};
+    for (int k = 0; k < 8; ++k) v[k] = i0 + k < i_end ? feat_load(a, r, i0 + k, ch0, ch1, inside[k]) : FeatRaw{};
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[k] = i0 + k < i_end ? feat_mix(a, i0 + k, v[k], inside[k]) : FeatPair{};
 }

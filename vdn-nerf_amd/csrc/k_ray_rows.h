@@ -307,6 +307,12 @@ struct ActiveJob {
     int32_t* active_idx;
     int32_t* n_active;
     int32_t* ray_counts;
+    // two-class foreground list (inner > 0; foreground without complement only): the ids with norm < inner come first, ascending,
+    // those with inner <= norm < radius behind them, ascending; n_active[0] stays the total, n_inner[0] = the first class's
+    // length, n_inner[1] = that length rounded up to whole 128-row workgroups (capped at the total): the row count of the
+    // kernels that only need the first class. ray_counts then holds [2B]: first-class counts, second-class counts.
+    float inner;
+    int32_t* n_inner;
 };
 
 VDN_DEV bool sample_active(const ActiveJob& a, int r, int s, const float (&o)[3], const float (&d)[3]) {
@@ -317,8 +323,48 @@ VDN_DEV bool sample_active(const ActiveJob& a, int r, int s, const float (&o)[3]
 
 // one ray of a work list. FILL = false: count the ray's active samples into ray_counts[r]; FILL = true: write their ids behind
 // those of the rays before (ascending dense order, deterministic), the last ray also the list's length
+// ... of a two-class foreground list (ActiveJob::inner). A NaN norm is in neither class.
+template <bool FILL>
+VDN_DEV void active_list_row_classes(const ActiveJob& a, int r, int lane, const float (&o)[3], const float (&d)[3]) {
+    int base0 = 0, base1 = 0, total0 = 0;
+    if (FILL) {      // first class: behind the first-class ids of the rays before; second class: behind ALL first-class ids
+        int acc0 = 0, acc1 = 0, all0 = 0;
+        for (int i = lane; i < a.B; i += 64) {
+            const int c0 = a.ray_counts[i];
+            all0 += c0;
+            if (i < r) { acc0 += c0; acc1 += a.ray_counts[a.B + i]; }
+        }
+        base0 = (int)wave_sum((double)acc0);
+        total0 = (int)wave_sum((double)all0);
+        base1 = total0 + (int)wave_sum((double)acc1);
+    }
+    int n0 = 0, n1 = 0;
+    for (int s0 = 0; s0 < a.N; s0 += 64) {
+        const int s = s0 + lane;
+        const float pn = s < a.N ? sample_norm(o, d, a.mid_z[(long)r * a.N + s]) : 2.0f * a.radius;
+        const bool in0 = s < a.N && pn < a.inner, in1 = s < a.N && pn < a.radius && !(pn < a.inner);
+        const unsigned long long m0 = __ballot(in0), m1 = __ballot(in1), below = (1ull << lane) - 1ull;
+        if (FILL && in0) a.active_idx[base0 + n0 + __popcll(m0 & below)] = r * a.N + s;
+        if (FILL && in1) a.active_idx[base1 + n1 + __popcll(m1 & below)] = r * a.N + s;
+        n0 += __popcll(m0);
+        n1 += __popcll(m1);
+    }
+    if (lane == 0) {
+        if (!FILL) {
+            a.ray_counts[r] = n0;
+            a.ray_counts[a.B + r] = n1;
+        } else if (r == a.B - 1) {
+            const int total = base1 + n1;
+            a.n_active[0] = total;
+            a.n_inner[0] = total0;
+            a.n_inner[1] = min(total, (total0 + 127) / 128 * 128);
+        }
+    }
+}
+
 template <bool FILL>
 VDN_DEV void active_list_row(const ActiveJob& a, int r, int lane, const float (&o)[3], const float (&d)[3]) {
+    if (a.inner > 0.0f) return active_list_row_classes<FILL>(a, r, lane, o, d);
     int base = 0;
     if (FILL) {      // offset of this ray = sum of the counts of the rays before it
         int acc = 0;

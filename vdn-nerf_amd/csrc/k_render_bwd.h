@@ -20,7 +20,23 @@ __global__ __launch_bounds__(P::kWaves * 64, P::kMinWavesPerEU) void rendernet_b
     ws.init(a.blob, smem, 42 + EX);
     const int lane = ws.lane, c = lane & 31, h = lane >> 5;
     const WorkRow wr = work_row(a.active_idx, a.n_active, a.P, P::kWaves, ws.wave, c);
-    if (wr.none) return;
+    if (wr.none) {
+        // two-class work list (a.n_rows_all): the listed rows behind the first class have an output adjoint of exactly zero,
+        // hence zero deltas and zero input adjoints. Nobody reads their deltas (the weight-gradient entries stop at the first
+        // class too) and d_normals accumulates (+ 0); d_feat is read on every listed row by the SDF backward, so the launch
+        // that overwrites it stores +0.0 there
+        if (a.n_rows_all != nullptr && !a.acc_feat) {
+            const WorkRow wz = work_row(a.active_idx, a.n_rows_all, a.P, P::kWaves, ws.wave, c);
+            if (!wz.none) {
+                f32x16 zero;
+#pragma unroll
+                for (int t = 0; t < 16; ++t) zero[t] = 0.0f;
+#pragma unroll
+                for (int nt = 0; nt < 8; ++nt) P::store_tile(reinterpret_cast<typename P::store_t*>(a.d_feat), wz.row, 256, nt, h, zero, wz.ok);
+            }
+        }
+        return;
+    }
     ws.warm_issue(wr.n_wg, 256 * P::kMinWavesPerEU);      // (mlp_engine.h; ends before the ring starts)
     warm_code_issue((std::is_same<P, BF16>::value) ? kWarmCodeRenderBwd : 0, wr.n_wg, 256 * P::kMinWavesPerEU, ws.warm_dump());      // (the kernel's own code: vdn_common.h)
     const bool ok = wr.ok;
@@ -160,6 +176,7 @@ int launch_rendernet_bwd(const VdnRenderNetBwdArgs* args, void* stream_) {
         !args->delta_h || !args->d_feat || !args->d_normals) return -1;
     if (!(args->d_out == 96 || (args->d_out >= 1 && args->d_out <= 4))) return -2;
     if (args->d_pts && (!args->d_dirs || (!args->dirs && (!args->rays_d || args->n_per_ray <= 0)))) return -3;
+    if (args->n_rows_all && (!args->active_idx || !args->n_active || !args->acc_normals || args->d_pts)) return -6;
     const int ppw = P::kWaves * 32;
     const int grid = (args->P + ppw - 1) / ppw;
     const size_t lds = 3 * P::stride(8);

@@ -313,6 +313,11 @@ struct ShadeExtra {
     void* col_h;                // MODE 3: [4, rows, 256] the colour head's saved hidden activations (PT32 planes, compact rows)
     void* col_small;            // MODE 3: [rows, 64] its 33 small inputs (points, PE4(view), normal) as the weight-gradient GEMM reads them
     float* col_out;             // MODE 3 / 4: [P,3] the sampled colour (dense point id)
+    // MODE 3, optional: device row count of the colour head's OUTPUTS (a two-class work list, include/vdn_render.h:
+    // VdnForegroundActiveArgs.n_inner[1]: whole 128-row workgroups or the whole list). Workgroups behind it leave col_h / col_small /
+    // col_out alone, exactly as vdn_rendernet_fwd_bf16 on that row count; they still run the head's chunk steps (the flat stream
+    // is one straight line per workgroup), so this launch saves no time on those rows
+    const int32_t* n_col_rows;
     CompositeArgs cm;           // sdf / normals / color are not read (the samples come through LDS)
 };
 
@@ -350,6 +355,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
 #endif
     const bool ok = wr.ok;
     const long p = wr.row, pd = wr.point;
+    const bool col_wg = MODE != 3 || ex.n_col_rows == nullptr || (long)blockIdx.x * (kWaves * 32) < (long)*ex.n_col_rows;     // (ShadeExtra::n_col_rows)
     const int c16 = lane & 15, q4 = lane >> 4;      // shape 1: this lane's column of both 16-point halves, and its row quad
     (void)c16; (void)q4;
 
@@ -656,7 +662,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                     cur[pr & 3] = pk;
                     D.r[T * 2 + (pr >> 2)] = __builtin_bit_cast(bf16x8, cur);
                     if constexpr (MODE == 3 && (pr & 3) == 3)          // the saved plane piece k = pr >> 2 = this k-step's whole B fragment (as the H planes)
-                        plane_store16(reinterpret_cast<ST*>(ex.col_h) + L.l * PS + piece(T, pr >> 2), cur);
+                        if (col_wg) plane_store16(reinterpret_cast<ST*>(ex.col_h) + L.l * PS + piece(T, pr >> 2), cur);
                 });
             } else if constexpr (L.kind == COLOUT) {
                 // rows 0..2 of the output tile = registers 0..2 of the h = 0 lanes (fields.py:166-171)
@@ -771,7 +777,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                     for (int i = 0; i < 32; ++i) s33[i] = small[i];
                     s33[32] = nz;
 #pragma unroll
-                    for (int kt = 0; kt < 2; ++kt) P::store_tile(reinterpret_cast<ST*>(ex.col_small), p, 64, kt, h, vals_tile<33>(s33, h, kt), true);
+                    for (int kt = 0; kt < 2; ++kt) P::store_tile(reinterpret_cast<ST*>(ex.col_small), p, 64, kt, h, vals_tile<33>(s33, h, kt), col_wg);
                 }
             }
         } else {
@@ -786,7 +792,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
             for (int d = 0; d < 3; ++d) a.normals[pd * 3 + d] = n[d] * a.scale;
             if constexpr (MODE == 3 || MODE == 4) {
 #pragma unroll
-                for (int d = 0; d < 3; ++d) ex.col_out[pd * 3 + d] = col[d];
+                for (int d = 0; d < 3; ++d) if (col_wg) ex.col_out[pd * 3 + d] = col[d];
             }
         }
     }

@@ -300,7 +300,10 @@ extern "C" int vdn_background_active(const VdnBackgroundActiveArgs* a, void* str
 extern "C" int vdn_foreground_active(const VdnForegroundActiveArgs* a, void* stream) {
     if (!a || a->B <= 0 || a->N <= 0 || !a->rays_o || !a->rays_d || !a->mid_z || !(a->radius > 0.0f) ||
         !a->active_idx || !a->n_active || !a->ray_counts) return -1;
-    const ActiveJob j = {a->rays_o, a->rays_d, a->mid_z, a->B, a->N, a->N, a->radius, false, a->complement != 0, a->active_idx, a->n_active, a->ray_counts};
+    // two classes: an inner radius inside the list's own, its counters, and not on the complement
+    if ((a->inner_radius != 0.0f || a->n_inner) && (!(a->inner_radius > 0.0f) || !(a->inner_radius <= a->radius) || !a->n_inner || a->complement)) return -2;
+    const ActiveJob j = {a->rays_o, a->rays_d, a->mid_z, a->B, a->N, a->N, a->radius, false, a->complement != 0, a->active_idx, a->n_active, a->ray_counts,
+                         a->inner_radius, a->n_inner};
     return launch_active(j, stream);
 }
 
@@ -352,7 +355,8 @@ __global__ __launch_bounds__(kRayWaves * 64) void train_prep_kernel(TrainPrepArg
     // the two lists: foreground (inside samples with |p| < radius) and background (not inside the unit sphere, plus every
     // outside sample); pass 1 fills one of them per block
     if (a.fg_active_idx != nullptr && !second)
-        active_list_row<PASS == 1>(ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.N, a.fg_radius, false, false, a.fg_active_idx, a.fg_n_active, a.fg_ray_counts},
+        active_list_row<PASS == 1>(ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.N, a.fg_radius, false, false, a.fg_active_idx, a.fg_n_active, a.fg_ray_counts,
+                                             a.fg_inner_radius, a.fg_n_inner},
                                    r, lane, o, d);
     if (PASS == 0 || second)
         active_list_row<PASS == 1>(ActiveJob{a.rays_o, a.rays_d, a.mid_z, a.B, a.N, a.T, 1.0f, true, false, a.bg_active_idx, a.bg_n_active, a.bg_ray_counts},
@@ -366,6 +370,8 @@ extern "C" int vdn_train_prep(const VdnTrainPrepArgs* a, void* stream) {
     if (a->new_z && (a->M_old < 1 || a->M_old >= a->N || a->N - a->M_old > 64)) return -2;
     if (!a->bg_active_idx || !a->bg_n_active || !a->bg_ray_counts) return -3;
     if (a->fg_active_idx && (!a->fg_n_active || !a->fg_ray_counts || !(a->fg_radius > 0.0f))) return -4;
+    if ((a->fg_inner_radius != 0.0f || a->fg_n_inner) &&
+        (!a->fg_active_idx || !(a->fg_inner_radius > 0.0f) || !(a->fg_inner_radius <= a->fg_radius) || !a->fg_n_inner)) return -4;
     launch_rays(train_prep_kernel<0>, a->B, stream, *a);
     launch_ray_blocks(train_prep_kernel<1>, 2 * ray_blocks(a->B), stream, *a);      // one set of blocks per list
     return (int)hipGetLastError();

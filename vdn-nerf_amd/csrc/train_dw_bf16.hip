@@ -79,7 +79,7 @@ VDN_DEV bf16x8 dw_frag(const lds_char* p) {
 
 VDN_DEV int dw_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-__global__ __launch_bounds__(512, 1) void dw_gemm_bf16_kernel(const DwDesc* descs, int n_desc) {
+__global__ __launch_bounds__(512, 1) void dw_gemm_bf16_kernel(const DwDesc* descs, int n_desc, DwRowCap cap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wg = blockIdx.x;
     int di = 0;
@@ -106,6 +106,8 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_bf16_kernel(const DwDesc* desc
     const int s_in = seg2 ? split - seg_splits : split;
     int P = dw_uni(d.P);
     if (d.P_dev != nullptr) P = min(P, dw_uni(*d.P_dev));
+    // (the launch's row cap, vdn_dw_gemm_rows_bf16: the heads' entries stop at the rows the heads evaluated)
+    if (cap.rows != nullptr && dw_uni(di) >= cap.lo && dw_uni(di) < cap.hi) P = dw_uni(min(P, max(dw_uni(*cap.rows), 0)));
     int per = (P + seg_splits - 1) / seg_splits;
     per = (per + 127) / 128 * 128;
     const int k_begin = s_in * per, k_end = min(k_begin + per, P);
@@ -233,11 +235,21 @@ extern "C" int vdn_dw_entry_wgs_bf16(int m_tiles, int n_tiles, int splits) {
     return splits * mg * ng;
 }
 
-extern "C" int vdn_dw_gemm_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void* stream) {
+static int dw_gemm_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, vdn::DwRowCap cap, void* stream) {
     using namespace vdn;
     if (!descs_dev || n_desc <= 0 || total_wgs <= 0) return -1;
     static bool once = (allow_big_lds(dw_gemm_bf16_kernel, kDwBuf * kDwStageBytes), true);
     (void)once;
-    hipLaunchKernelGGL(dw_gemm_bf16_kernel, dim3(total_wgs), dim3(512), kDwBuf * kDwStageBytes, (hipStream_t)stream, descs_dev, n_desc);
+    hipLaunchKernelGGL(dw_gemm_bf16_kernel, dim3(total_wgs), dim3(512), kDwBuf * kDwStageBytes, (hipStream_t)stream, descs_dev, n_desc, cap);
     return (int)hipGetLastError();
+}
+
+extern "C" int vdn_dw_gemm_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void* stream) {
+    return dw_gemm_bf16(descs_dev, n_desc, total_wgs, vdn::DwRowCap{nullptr, 0, 0}, stream);
+}
+
+extern "C" int vdn_dw_gemm_rows_bf16(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, const int32_t* cap_rows, int cap_lo, int cap_hi,
+                                     void* stream) {
+    if (!cap_rows || cap_lo < 0 || cap_hi < cap_lo || cap_hi > n_desc) return -2;
+    return dw_gemm_bf16(descs_dev, n_desc, total_wgs, vdn::DwRowCap{cap_rows, cap_lo, cap_hi}, stream);
 }

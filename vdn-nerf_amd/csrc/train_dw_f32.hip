@@ -15,7 +15,7 @@ namespace vdn {
 constexpr int kF32StagePts = 32;
 constexpr int kF32PanelBytes = kF32StagePts * 128 * 4;          // 16 KiB per operand per stage
 
-__global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs, int n_desc) {
+__global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs, int n_desc, DwRowCap cap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [buffer(2)][operand(2)][32][128] fp32
     const int wg = blockIdx.x;
     int di = 0;
@@ -41,7 +41,8 @@ __global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs
     const int seg_splits = two ? d.splits / 2 : d.splits;       // two segments: first half of the splits = segment 1
     const bool seg2 = two && split >= seg_splits;
     const int s_in = seg2 ? split - seg_splits : split;
-    const long P = d.P_dev != nullptr ? min((long)d.P, (long)*d.P_dev) : (long)d.P;
+    long P = d.P_dev != nullptr ? min((long)d.P, (long)*d.P_dev) : (long)d.P;
+    if (cap.rows != nullptr && di >= cap.lo && di < cap.hi) P = min(P, max((long)*cap.rows, 0L));
     long per = (P + seg_splits - 1) / seg_splits;
     per = (per + kF32StagePts - 1) / kF32StagePts * kF32StagePts;
     const long k_begin = (long)s_in * per, k_end = min(k_begin + per, P);
@@ -204,12 +205,22 @@ extern "C" int vdn_dw_entry_wgs_f32(int m_tiles, int n_tiles, int splits) {
     return 8 * ((splits + 7) / 8) * mt4 * nt4;          // a multiple of 8: see the id space in dw_gemm_f32_kernel
 }
 
-extern "C" int vdn_dw_gemm_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void* stream) {
+static int dw_gemm_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, vdn::DwRowCap cap, void* stream) {
     if (!descs_dev || n_desc <= 0 || total_wgs <= 0) return -1;
     static bool once = (vdn::allow_big_lds(vdn::dw_gemm_f32_kernel, 4 * vdn::kF32PanelBytes), true);
     (void)once;
-    hipLaunchKernelGGL(vdn::dw_gemm_f32_kernel, dim3(total_wgs), dim3(256), 4 * vdn::kF32PanelBytes, (hipStream_t)stream, descs_dev, n_desc);
+    hipLaunchKernelGGL(vdn::dw_gemm_f32_kernel, dim3(total_wgs), dim3(256), 4 * vdn::kF32PanelBytes, (hipStream_t)stream, descs_dev, n_desc, cap);
     return (int)hipGetLastError();
+}
+
+extern "C" int vdn_dw_gemm_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, void* stream) {
+    return dw_gemm_f32(descs_dev, n_desc, total_wgs, vdn::DwRowCap{nullptr, 0, 0}, stream);
+}
+
+extern "C" int vdn_dw_gemm_rows_f32(const VdnDwDesc* descs_dev, int n_desc, int total_wgs, const int32_t* cap_rows, int cap_lo, int cap_hi,
+                                    void* stream) {
+    if (!cap_rows || cap_lo < 0 || cap_hi < cap_lo || cap_hi > n_desc) return -2;
+    return dw_gemm_f32(descs_dev, n_desc, total_wgs, vdn::DwRowCap{cap_rows, cap_lo, cap_hi}, stream);
 }
 
 extern "C" int vdn_dw_finalize(const VdnDwFinalizeDesc* descs_dev, int n_desc, int max_M, int phase, void* stream) {

@@ -136,7 +136,8 @@ VDN_DEV void composite_bwd_row(const CompositeBwdArgs& a, int r, int wave, int l
                 const long q = (long)r * N + i;
                 pn[e] = sample_norm(o, d, a.mid_z[q]);              // the sample's norm, once: inside here, relax below
                 inside = pn[e] < 1.0f ? 1.0f : 0.0f;
-                c0 = a.color[q * 3]; c1 = a.color[q * 3 + 1]; c2 = a.color[q * 3 + 2];
+                const bool heads = !has_bg || inside != 0.0f;       // (k_composite_row.h: a colour with weight 0 is not read)
+                c0 = heads ? a.color[q * 3] : 0.0f; c1 = heads ? a.color[q * 3 + 1] : 0.0f; c2 = heads ? a.color[q * 3 + 2] : 0.0f;
                 if (has_bg) {
                     c0 = c0 * inside + a.bg_rgb[qt * 3] * (1.0f - inside);
                     c1 = c1 * inside + a.bg_rgb[qt * 3 + 1] * (1.0f - inside);

@@ -19,6 +19,12 @@ using NerfBwdArgs = ::VdnNerfBwdArgs;
 using SdfRbarArgs = ::VdnSdfRbarArgs;
 using SdfFbarArgs = ::VdnSdfFbarArgs;
 using DwDesc = ::VdnDwDesc;
+// a launch-wide row cap of the weight-gradient GEMMs (vdn_dw_gemm_rows_*): descriptors [lo, hi) of the launch contract over at
+// most *rows rows (on top of their own P / P_dev); rows == nullptr: no cap
+struct DwRowCap {
+    const int32_t* rows;
+    int lo, hi;
+};
 using DwFinalizeDesc = ::VdnDwFinalizeDesc;
 using WeightNormBwdDesc = ::VdnWeightNormBwdDesc;
 using CompositeBwdArgs = ::VdnCompositeBwdArgs;

@@ -795,7 +795,7 @@ class NeuSRenderer:
         if inject and (t_rand is None or (O > 0 and t_rand_out is None) or perturb <= 0):
             return None
         # (the switches that select launches inside the captured region: a plan is valid for one setting of them)
-        key = (background_rgb is not None, float(perturb), inject, switches.signature("train"))
+        key = (background_rgb is not None, float(perturb), inject, switches.signature("train"), bool(eng._heads_inside))
         plans = eng.__dict__.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:

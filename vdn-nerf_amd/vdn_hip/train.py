@@ -283,8 +283,14 @@ class DwGroup:
         self.dw, self.n_dw, self.wgs = dw, n_dw, wgs
         self.fin, self.n_fin, self.max_m, self.phase1 = fin, n_fin, max_m, phase1
         self.wn, self.n_wn, self.wn_rows = wn, n_wn, wn_rows
+        # optional row cap of the GEMM launch: (device int32 tensor, first, end) - descriptors [first, end) of THIS group contract
+        # over at most that many rows (vdn_dw_gemm_rows_*); the ray engine caps the heads' entries at the rows the heads evaluated
+        self.cap = None
 
     def launch_gemm(self, sfx, stream):
+        if self.cap is not None:
+            lib.call("vdn_dw_gemm_rows" + sfx, lib.ptr(self.dw), self.n_dw, self.wgs, lib.ptr(self.cap[0]), self.cap[1], self.cap[2], stream)
+            return
         lib.call("vdn_dw_gemm" + sfx, lib.ptr(self.dw), self.n_dw, self.wgs, stream)
 
     def launch(self, sfx, stream, gemm_event=None, event_stream=None):
@@ -359,6 +365,12 @@ class TrainEngine:
         self._ctx = self._fwd_rays = self._car_dev = self._bwd_train = self._fused_keep = None
         self._pending = self._ray_grads = self._color_fused = self._composite_bwd_done = False
         self._fg_compact = self._bg_compact = False
+        # The colour and the VDN head only on the listed samples INSIDE the unit sphere (DESIGN.md "Work lists", third consequence):
+        # the foreground list comes in two classes (|p| < 1 first, 1 <= |p| < 1.2 behind; include/vdn_render.h:
+        # VdnForegroundActiveArgs.inner_radius), the heads' forward, backward and weight-gradient entries stop behind the first. False
+        # (the A/B arm): the list's inner radius is its own radius, i.e. one class in today's order, the heads on all of it - the
+        # same launches with the same pointers, so toggling it needs no rebuild (a graph plan is keyed on it, renderer.py)
+        self._heads_inside = True
         # ... and the rest: `generation` counts forwards (render()'s autograd node checks its result is the latest), _bwd_warm = a
         # backward ran eagerly, _bwd_args_keep holds the adjoints the compositor's argument block points at, join_hook (the
         # Trainer) orders the caller's stream behind a deferred half of the backward, sdf_probe (bench.py) collects event pairs
@@ -398,24 +410,31 @@ class TrainEngine:
         self._out_arena, self._out_slots = fz(n_out), slots
         out = lambda name: self._out_arena[slots[name][0]:slots[name][0] + int(np.prod(slots[name][1]))].view(slots[name][1])
         w["sdf"], w["feat"], w["normals"], w["mid_z"] = fz(P), fs(Pp, 256), out("normals"), out("mid_z")
-        w["fg_active"] = (torch.zeros(P, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
-                          torch.zeros(B, dtype=torch.int32, device=dev))
+        # the foreground list's device-side counters in one allocation: [rows listed, rows of the first class, rows the heads
+        # evaluate (the first class in whole 128-row workgroups), pad]; written by the step preparation, or filled with P
+        self._fg_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
+        w["fg_active"] = (torch.zeros(P, dtype=torch.int32, device=dev), self._fg_cnt[0:1], torch.zeros(2 * B, dtype=torch.int32, device=dev))
+        w["fg_inner"] = self._fg_cnt[1:3]
         w["H"], w["V"], w["PE"] = fs(8, Pp, 256), fs(8, Pp, 256), fs(Pp, 64)
         if self.precision == "fp32":          # the bf16 SDF kernel keeps softplus' on the chip (csrc/k_sdf_fwd2.h)
             w["S"] = fs(8, Pp, 256)
-        w["col_out"], w["col_h"], w["col_small"] = fz(P, 3), fs(4, Pp, 256), fs(Pp, 64)
+        # the heads' saves, masks and deltas are zero-initialised too: the heads run on a prefix of the list, the rows behind it
+        # are written by no kernel (and read by none) and stay defined
+        fsz = lambda *shape: torch.zeros(*shape, dtype=sdt, device=dev)
+        w["col_out"], w["col_h"], w["col_small"] = fz(P, 3), fsz(4, Pp, 256), fsz(Pp, 64)
         if self.wdepth:
-            w["vdn_out"], w["vdn_h"], w["vdn_small"] = fz(P, 96), fs(4, Pp, 256), fs(Pp, 64)
+            w["vdn_out"], w["vdn_h"], w["vdn_small"] = fz(P, 96), fsz(4, Pp, 256), fsz(Pp, 64)
         if self.dbc:
-            w["col_extra"] = fs(Pp, 96)
+            w["col_extra"] = fsz(Pp, 96)
         # 1-bit ReLU masks of the heads' and the background network's hidden layers (bf16; csrc/mlp_engine.h: BF16::relu_bits, decoded
         # by layout.mask_from_plane): the forwards write them beside the bf16 planes, the backward chains read them instead of the
         # planes (which the weight-gradient GEMM still reads). VDN_RELU_MASK=0: not written, the chains read the planes
         self.relu_mask = self.precision == "bf16" and switches.flag("VDN_RELU_MASK")
         fm = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev) if self.relu_mask else None
-        w["col_mask"] = fm(4, Pp * 32)
+        fmz = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=dev) if self.relu_mask else None
+        w["col_mask"] = fmz(4, Pp * 32)
         if self.wdepth:
-            w["vdn_mask"] = fm(4, Pp * 32)
+            w["vdn_mask"] = fmz(4, Pp * 32)
         if O > 0:
             w["z_feed"], w["bg_dists"], w["bg_mid"] = f(B, T), f(B, T), out("bg_mid")
             # zero-initialised: points the active list skips keep finite values (the compositor multiplies them by zero)
@@ -434,9 +453,9 @@ class TrainEngine:
         w["d_vdn"] = f(P, 96) if self.wdepth else None
         w["feat_scratch"] = f(B * (2 * T + N)) if self.wdepth else None        # VdnCompositeBwdArgs.feat_scratch
         w["d_var_partial"], w["d_variance"] = f(B), f(1)
-        w["col_dout"], w["col_dh"] = fs(Pp, 32), fs(4, Pp, 256)
+        w["col_dout"], w["col_dh"] = fsz(Pp, 32), fsz(4, Pp, 256)
         if self.wdepth:
-            w["vdn_dout"], w["vdn_dh"] = fs(Pp, 96), fs(4, Pp, 256)
+            w["vdn_dout"], w["vdn_dh"] = fsz(Pp, 96), fsz(4, Pp, 256)
         w["UB"], w["EX"], w["AB"] = fs(Pp * 2144), fs(8, Pp, 256), fs(Pp * 2336)
         if O > 0:
             w["d_bg_density"], w["d_bg_rgb"] = f(Q), f(Q, 3)
@@ -482,7 +501,10 @@ class TrainEngine:
         self.slab = torch.empty(max(slab_elems, 1), dtype=torch.float32, device=dev)
         self.colsum = torch.empty(max(cs_elems, 1), dtype=torch.float32, device=dev)
         # rows of the compact work lists (device scalars written by the forward)
-        self.dw_list_kind = ["bg" if e["net"] == "nerf" else "fg" for e in ent]
+        # ("heads": the colour / VDN heads' entries contract over the rows the heads evaluated, the first class of the foreground list.
+        # Their descriptors keep the list's length as P_dev - the tables are what they were - and every launch group caps them at
+        # the heads' row counter: DwGroup.cap below)
+        self.dw_list_kind = ["bg" if e["net"] == "nerf" else ("fg" if e["net"] == "sdf" else "heads") for e in ent]
         p_dev = [(w["bg_active"] if k == "bg" else w["fg_active"])[1].data_ptr() for k in self.dw_list_kind]
         dw, fin = dw_tables(ent, lay, self.nets, prec, self.slab, self.colsum, self.maps, p_dev, float(self.r.sdf_network.scale))
         wn, wn_net = weightnorm_table(self.nets)
@@ -508,6 +530,9 @@ class TrainEngine:
                 own = {e["net"] for e in ent[lo:hi]}         # a weight-normed matrix goes with its network's entries
                 self.groups[g] = dw_group(dw, fin, wn, lo, hi, wg, dev, vfin if lo == 0 else None,
                                           [i for i, k in enumerate(wn_net) if k in own], dw_dev)
+                c_lo, c_hi = max(lo, n_sdf) - lo, min(hi, n_heads_end) - lo          # the heads' entries inside this group
+                if c_hi > c_lo:
+                    self.groups[g].cap = (w["fg_inner"][1:2], c_lo, c_hi)
         self._param_ptrs = self._ptr_key()
 
     @property
@@ -608,6 +633,8 @@ class TrainEngine:
             tp = lib.VdnTrainPrepArgs()
             tp.rays_o, tp.rays_d, tp.z, tp.z_out, tp.z_feed = (t.data_ptr() for t in (rays_o, rays_d, z, z_out, w["z_feed"]))
             tp.B, tp.N, tp.T, tp.z_ld, tp.sample_dist, tp.fg_radius = B, N, T, z.stride(0), sample_dist, 1.2
+            if self._fg_compact:
+                tp.fg_inner_radius, tp.fg_n_inner = self._inner_radius(ray_grads), w["fg_inner"].data_ptr()
             if pending_merge is not None:
                 tp.new_z, tp.M_old = pending_merge[0].data_ptr(), pending_merge[1]
             tp.dists, tp.mid_z, tp.bg_dists, tp.bg_mid = (w[k].data_ptr() for k in ("dists", "mid_z", "bg_dists", "bg_mid"))
@@ -625,9 +652,10 @@ class TrainEngine:
                 fa = lib.VdnForegroundActiveArgs()
                 fa.rays_o, fa.rays_d, fa.mid_z, fa.B, fa.N, fa.radius = rays_o.data_ptr(), rays_d.data_ptr(), w["mid_z"].data_ptr(), B, N, 1.2
                 fa.active_idx, fa.n_active, fa.ray_counts = (t.data_ptr() for t in w["fg_active"])
+                fa.inner_radius, fa.n_inner = self._inner_radius(ray_grads), w["fg_inner"].data_ptr()
                 lib.call("vdn_foreground_active", fa, st)
         if not self._fg_compact:
-            w["fg_active"][1].fill_(self.P)               # the dW GEMM's device-side row count
+            self._fg_cnt.fill_(self.P)                    # the dW GEMM's device-side row counts (all three: no list, no classes)
         if O > 0:
             if not fused_prep:
                 a = lib.VdnSectionArgs()
@@ -673,7 +701,7 @@ class TrainEngine:
             c.P, c.d_out, c.squeeze_out = self.P, d_out, int(module.squeeze_out)
             if net == "color" and self.dbc:          # renderer.py:247-248
                 c.extra, c.save_extra = w["vdn_out"].data_ptr(), w["col_extra"].data_ptr()
-            lib.call("vdn_rendernet_fwd" + self.sfx, self._fg(c), st if stream is None else stream)
+            lib.call("vdn_rendernet_fwd" + self.sfx, self._fg_heads(c), st if stream is None else stream)
         if before_heads is not None:
             before_heads()
         vdn_beside = self.wdepth and self._side2 is not None and not self.dbc     # (depth_before_color: the colour head reads the VDN output)
@@ -727,6 +755,18 @@ class TrainEngine:
         if self._fg_compact:
             args.active_idx, args.n_active = self.w["fg_active"][0].data_ptr(), self.w["fg_active"][1].data_ptr()
         return args
+
+    def _fg_heads(self, args):
+        """... to a colour / VDN head's block: the same list, cut behind its first class (whole 128-row workgroups)."""
+        if self._fg_compact:
+            args.active_idx, args.n_active = self.w["fg_active"][0].data_ptr(), self.w["fg_inner"][1:2].data_ptr()
+        return args
+
+    def _inner_radius(self, ray_grads):
+        """Inner radius of the two-class foreground list. 1.0 = the compositor's inside_sphere test: where it fails the heads' outputs
+        are blended with weight 0. With ray gradients the heads stay on the whole list (inner radius = the list's own): their
+        backward then writes the point / direction adjoints of every listed row as before, instead of zero-filling rows."""
+        return 1.0 if (self._heads_inside and not ray_grads) else 1.2
 
     # ---- optional side stream for the background network (VDN_SIDE_STREAM=1; default: everything on the caller's stream)
     def _fork(self):
@@ -814,6 +854,10 @@ class TrainEngine:
         def launch():
             if fused:
                 cimg = self.nets["color"].img
+                if self._fg_compact:        # the head's planes and colours on the rows the separate launch would write
+                    lib.call("vdn_sdf_color_train_rows_bf16", self._fg(s), lib.ptr(cimg.blobs["c2"]), int(r.color_network.squeeze_out),
+                             lib.ptr(w["col_h"]), lib.ptr(w["col_small"]), lib.ptr(w["col_out"]), lib.ptr(w["fg_inner"][1:2]), _stream())
+                    return
                 lib.call("vdn_sdf_color_train_bf16", self._fg(s), lib.ptr(cimg.blobs["c2"]), int(r.color_network.squeeze_out),
                          lib.ptr(w["col_h"]), lib.ptr(w["col_small"]), lib.ptr(w["col_out"]), _stream())
                 return
@@ -834,7 +878,8 @@ class TrainEngine:
 
     def _dw_rows(self):
         """Rows each weight-gradient entry contracts over in the current step (the work lists of the last forward)."""
-        n = {"bg": int(self.w["bg_active"][1].item()) if "bg_active" in self.w else 0, "fg": int(self.w["fg_active"][1].item())}
+        cnt = self._fg_cnt.tolist()
+        n = {"bg": int(self.w["bg_active"][1].item()) if "bg_active" in self.w else 0, "fg": cnt[0], "heads": cnt[2]}
         tab = np.frombuffer(self.groups["all"].dw.cpu().numpy().tobytes(), dtype=lib.struct_dtype("VdnDwDesc"))
         return tab, [min(int(d["P"]), n[k]) for d, k in zip(tab, self.dw_list_kind)]
 
@@ -1021,7 +1066,11 @@ class TrainEngine:
             if rg:
                 b.rays_d, b.n_per_ray, b.acc_pts = rays_d.data_ptr(), self.N, int(accumulate)
                 b.d_pts, b.d_dirs = w["d_pts"].data_ptr(), w["d_dirs"].data_ptr()
-            lib.call("vdn_rendernet_bwd" + self.sfx, self._fg(b), st)
+            if self._fg_compact and not rg:
+                # rows behind the heads' prefix: zero output adjoint, so the launch that overwrites d_featvec stores zeros there
+                # (VdnRenderNetBwdArgs.n_rows_all); with ray gradients the heads cover the whole list (_inner_radius)
+                b.n_rows_all = w["fg_active"][1].data_ptr()
+            lib.call("vdn_rendernet_bwd" + self.sfx, self._fg_heads(b), st)
         if rg and self._fg_compact:
             # samples off the foreground work list enter the loss through exact zeros: their adjoints stay zero (the heads and
             # the SDF backward write the listed rows only)
