@@ -47,6 +47,7 @@ def _trainer(monkeypatch, mask, wdepth, B):
 @pytest.mark.gpu
 @pytest.mark.parametrize("wdepth,compact,B", [(False, True, 512), (True, True, 512), (False, False, 256), (True, True, 200)])
 def test_masked_step_is_bit_identical(monkeypatch, wdepth, compact, B):
+    """Two Trainers in lockstep, one built under VDN_RELU_MASK=0 (_trainer sets the switch), one under the default."""
     import torch
     from vdn_train import synth
     from vdn_hip import layout

@@ -44,6 +44,7 @@ EXACT = ("cdf_fine", "inside_sphere", "weights", "weight_sum", "weight_max", "s_
 
 @pytest.mark.parametrize("B,crop", [(1, None), (3, 420), (37, None), (512, None), (512, 420), (1000, 420)])
 def test_fused_shading_equals_the_separate_launches(B, crop):
+    """The fused launch against its VDN_SHADE_FUSED=0 arm (_render sets the switch) on one renderer and one batch."""
     from vdn_train import synth, factory
     dev = torch.device("cuda:0")
     rend = factory.build_renderer(device=dev, states=synth.make_all_states(0, variance=0.4), precision="bf16")

@@ -106,7 +106,7 @@ def test_fused_point_shading_equals_the_separate_launches(P):
     err = float((col - ref).abs().max())
     print("P = %d: fused colour vs separate launches, max abs %.3e" % (P, err))
     assert err < 2e-3
-    # the A/B switch runs exactly those launches
+    # the A/B switch (VDN_SHADE_POINTS_FUSED=0, set by _shade) runs exactly those launches
     sdf0, grad0, col0 = _shade(rend, x, False)
     assert torch.equal(sdf0, sdf1) and torch.equal(grad0, nrm1) and torch.equal(col0, ref)
     # a second call gives the same bits; small batches give the same bits as one launch

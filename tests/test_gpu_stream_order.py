@@ -145,7 +145,8 @@ _ARMS = [(name, arm) for name, cfg in sk.CONFIGS.items() for arm in ("none",) + 
 
 @pytest.mark.parametrize("cfg_name,arm", _ARMS, ids=["%s-%s" % a for a in _ARMS])
 def test_schedule_equals_the_serial_arm(cases, cfg_name, arm):
-    """T1 - T6 (stream_skew.CONFIGS) on the shipped default schedule: un-delayed, and with every launch of one stream delayed."""
+    """T1 - T6 (stream_skew.CONFIGS) on the shipped default schedule: un-delayed, and with every launch of one stream delayed,
+    against the VDN_SIDE_STREAM=0 arm."""
     spec = dict(kind="train", cfg=cfg_name, arm=arm)
     ref, got = cases.get(sk.ref_spec(spec)), cases.get(spec)
     _check_serial(ref, cfg_name)

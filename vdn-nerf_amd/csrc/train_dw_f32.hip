@@ -14,6 +14,12 @@ namespace vdn {
 // while the current one is multiplied; a lane's MFMA operand (k = h, feature = c) is one ds_read_b32.
 constexpr int kF32StagePts = 32;
 constexpr int kF32PanelBytes = kF32StagePts * 128 * 4;          // 16 KiB per operand per stage
+// An output element is a sequential fp32 accumulation over the rows of its K split, and the rounding error of such a chain grows
+// with its length. A chain is therefore cut every 2 048 rows - the rows of a default split (vdn_hip/train.py: _pts_per_split) - and
+// the pieces are added up in a second accumulator: a setting that makes few, long splits (VDN_DW_SPLIT_PTS_SDF / _REST) then sums
+// like the default partition does. A split of up to 2 048 rows is one piece and never touches the second accumulator: its bits
+// are what they always were.
+constexpr int kF32ChainStages = 2048 / kF32StagePts;
 
 __global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs, int n_desc, DwRowCap cap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [buffer(2)][operand(2)][32][128] fp32
@@ -71,6 +77,8 @@ __global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs
     };
     f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
     float cs0 = 0.0f, cs1 = 0.0f;
+    f32x16 tot00 = {0}, tot01 = {0}, tot10 = {0}, tot11 = {0};      // the finished pieces of a chain longer than kF32ChainStages
+    float ct0 = 0.0f, ct1 = 0.0f;
     const bool do_colsum = d.colsum != nullptr && tn == 0 && wn == 0 && !seg2;
     const long n_stages = (k_end - k_begin + kF32StagePts - 1) / kF32StagePts;
     if (n_stages > 0) issue(k_begin, 0);
@@ -101,6 +109,16 @@ __global__ __launch_bounds__(256, 2) void dw_gemm_f32_kernel(const DwDesc* descs
                 acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
             }
         }
+        if ((t + 1) % kF32ChainStages == 0 && t + 1 < n_stages) {      // a piece is complete and another one follows
+            tot00 += acc00; tot01 += acc01; tot10 += acc10; tot11 += acc11;
+            acc00 = f32x16{0}; acc01 = f32x16{0}; acc10 = f32x16{0}; acc11 = f32x16{0};
+            ct0 += cs0; ct1 += cs1;
+            cs0 = 0.0f; cs1 = 0.0f;
+        }
+    }
+    if (n_stages > kF32ChainStages) {
+        acc00 = tot00 + acc00; acc01 = tot01 + acc01; acc10 = tot10 + acc10; acc11 = tot11 + acc11;
+        cs0 = ct0 + cs0; cs1 = ct1 + cs1;
     }
     const int M = d.m_tiles * 32, N = d.n_tiles * 32;
     auto put = [&](const f32x16& acc, int mt, int nt) {
