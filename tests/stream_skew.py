@@ -271,10 +271,12 @@ def _cpu(t):
 # ------------------------------------------------------------------------------------------------------------------------
 # arms of the Trainer's step
 # ------------------------------------------------------------------------------------------------------------------------
-def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False):
+def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False, between_steps=None, env_extra=None):
     """One arm of configuration `cfg_name`: "ref" = the serial arm (VDN_SIDE_STREAM=0, the logging launches on the caller's stream
     as well, torch.cuda.synchronize() after every step), else the shipped schedule under the rule of `arm`.
-    no_forward_join: TrainEngine._join clears _pending WITHOUT waiting during forward() (the harness-bites case only)."""
+    no_forward_join: TrainEngine._join clears _pending WITHOUT waiting during forward() (the harness-bites case only).
+    between_steps(tr, it): called in front of every step it = 0 .. steps-1 and once more behind the last one (it = steps), on the arm's
+    stream (tests/test_gpu_workspace_poison.py: it joins, snapshots and poisons there). env_extra: more switches for both arms."""
     from vdn_train import factory
     from vdn_train.trainer import Trainer
     from vdn_hip.train import TrainEngine
@@ -282,6 +284,7 @@ def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False):
     serial = arm == "ref"
     env = dict(VDN_SDF_TAIL="0", VDN_SIDE_STREAM="0" if serial else "1")
     env.update(sw["env"])
+    env.update(env_extra or {})
     cycles = 0
     if _rule(arm) is not None:
         cycles = int(run_case(ref_spec(dict(kind="train", cfg=cfg_name, switch=switch)))["D_ms"] * cycles_per_ms())
@@ -322,6 +325,8 @@ def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False):
             with torch.cuda.stream(main), Skew(main, _rule(arm), cycles) as h:
                 for it in range(steps):
                     h.step = it
+                    if between_steps is not None:
+                        between_steps(tr, it)
                     if serial and it == 2:
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record()
@@ -340,6 +345,8 @@ def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False):
                         if it == 0:
                             w = tr.engine.w
                             counts = [int(w["fg_active"][1].item()), tr.engine.P, int(w["bg_active"][1].item()), tr.engine.Q]
+                if between_steps is not None:
+                    between_steps(tr, steps)
                 torch.cuda.synchronize()
                 res = dict(scalars=_cpu(torch.stack(scalars)), param_flat=_cpu(tr.param_flat), exp_avg=_cpu(tr.exp_avg),
                            exp_avg_sq=_cpu(tr.exp_avg_sq), grad_flat=_cpu(tr.engine.grad_flat), log=list(h.log), delays=h.delays)
@@ -357,17 +364,19 @@ def train_arm(cfg_name, arm, switch=None, steps=S, no_forward_join=False):
 # ------------------------------------------------------------------------------------------------------------------------
 # arms of the drop-in flow: NeuSRenderer.render under grad + loss.backward(), eager
 # ------------------------------------------------------------------------------------------------------------------------
-def dropin_arm(wdepth, split_dw, arm):
+def dropin_arm(wdepth, split_dw, arm, between_steps=None, env_extra=None, calls=DROPIN_CALLS):
+    """between_steps(rend, it): as train_arm's, with the renderer, in front of every call and once behind the last."""
     from vdn_train import factory
     serial = arm == "ref"
     env = dict(VDN_RENDER_GRAPHS="0", VDN_SDF_TAIL="0", VDN_SIDE_STREAM="0" if serial else "1")
     if not split_dw:
         env["VDN_BWD_SPLIT_DW"] = "0"
+    env.update(env_extra or {})
     cycles = 0
     if _rule(arm) is not None:
         cycles = int(run_case(ref_spec(dict(kind="dropin", wdepth=wdepth, split_dw=split_dw)))["D_ms"] * cycles_per_ms())
     main = torch.cuda.default_stream(DEV)
-    inputs, extra = _step_inputs(13, DROPIN_CALLS, "dropin", feats=wdepth)
+    inputs, extra = _step_inputs(13, calls, "dropin", feats=wdepth)
     bg = torch.ones(1, 3, device=DEV)
     with environ(**env):
         torch.manual_seed(0)
@@ -376,8 +385,10 @@ def dropin_arm(wdepth, split_dw, arm):
         torch.cuda.synchronize()
         outs, grads, t_step = [], [], None
         with torch.cuda.stream(main), Skew(main, _rule(arm), cycles) as h:
-            for it in range(DROPIN_CALLS):
+            for it in range(calls):
                 h.step = it
+                if between_steps is not None:
+                    between_steps(rend, it)
                 if serial and it == 1:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
@@ -401,6 +412,8 @@ def dropin_arm(wdepth, split_dw, arm):
                     torch.cuda.synchronize()
                     if it == 1:
                         t_step = e0.elapsed_time(e1)
+            if between_steps is not None:
+                between_steps(rend, calls)
             torch.cuda.synchronize()
             res = dict(outs=[{k: _cpu(v) for k, v in o_.items()} for o_ in outs], grads=[_cpu(g) for g in grads],
                        params=_cpu(torch.cat([p.detach().reshape(-1) for p in params])), log=list(h.log), delays=h.delays)

@@ -393,6 +393,11 @@ class TrainEngine:
         Pp, Qp = layout.rows(P, self.precision), layout.rows(Q, self.precision)
         self.Pp, self.Qp = Pp, Qp
         w = self.w = {}
+        # torch.empty / torch.zeros below do not state what a buffer may hold behind a step: tests/poison.py does, one row per key
+        # (DESIGN.md "Workspaces"). Of the zero-initialised ones only sdf, normals and the background outputs are `masked` (rows off
+        # the lists are read under an exact zero factor); the heads' outputs, saves, masks and deltas (fz / fsz / fmz) are
+        # `rewritten` - NaN in them between steps changes nothing - and no torch.empty buffer is `masked`. The flat gradient
+        # needs its zero fill only where a network has no weight-gradient entries (the background network with n_outside = 0)
         # ---- forward saves
         w["dists"] = f(B, N)
         # dense per-point outputs are zero-initialised: points a work list skips keep finite values, and the compositor only
