@@ -1470,6 +1470,39 @@ typedef struct {
     int32_t B, N, O, n_samples, n_importance, cam, n_cams, _pad;
 } VdnPoseAdjointArgs;
 int vdn_pose_adjoint(const VdnPoseAdjointArgs* args_host, void* stream);
+
+/* ---- image evaluation: L1, PSNR and SSIM of a rendered image against its ground truth ------------------------
+ * vdn_image_stats: the sums behind the image row of a results table, from `pred` and `gt` ([H][W][3] fp32, nominally in [0, 1])
+ * and an optional `mask` ([H][W][mask_ch] fp32, mask_ch 1 or 3, first channel used; a pixel is in the mask when mask > 0.1, NULL:
+ * every pixel is). All arithmetic is double on the widened fp32 inputs, without contraction; e = pred - gt.
+ *   result[0] = number of pixels in the mask          result[1] = sum |e| m       result[2] = sum e^2 m   (m = 1 in the mask, else 0)
+ *   result[3] = sum |e|                               result[4] = sum e^2         (all pixels; sums over the three channels)
+ *   result[5] = sum S over the valid window centres and the three channels        result[6] = number of valid centres
+ *   result[7] = the same sum over the valid centres whose centre pixel is in the mask    result[8] = their number
+ *   result[9] = H W
+ * S is the structural similarity of Wang et al. 2004 per channel: an 11-tap Gaussian window, sigma 1.5, taps exp(-k^2 / 4.5)
+ * normalised to sum 1, applied separably (along x, then along y, each an in-order sum k = -5..5) to x, y, x x, y y, x y;
+ *   vx = E[xx] - mx mx, vy = E[yy] - my my, vxy = E[xy] - mx my, C1 = 0.01^2, C2 = 0.03^2,
+ *   S = ((2 (mx my) + C1) (2 vxy + C2)) / (((mx mx + my my) + C1) ((vx + vy) + C2)),
+ * only where the whole window lies inside the image: centres (y + 5, x + 5), y < H - 10, x < W - 10. Identical images give S = 1
+ * exactly. ssim_map (or NULL) receives fp32(((S_0 + S_1) + S_2) / 3) per valid centre, [H - 10][W - 10].
+ * Two launches: one workgroup per tile of valid centres sums its share in a fixed order into partials[tile][9] (no atomics),
+ * one wave then adds the tiles in a fixed order: the result is bit-reproducible. `partials` holds partials_rows >=
+ * vdn_image_stats_tiles(H, W) rows of 9 doubles; it need not be initialised. Status -1: a null image or result, H < 11, W < 11,
+ * mask_ch outside {1, 3} with a mask, or a workspace that is too small; -10: H W beyond 32-bit indexing. */
+typedef struct {
+    const float* pred;             /* [H][W][3] */
+    const float* gt;               /* [H][W][3] */
+    const float* mask;             /* [H][W][mask_ch] or NULL */
+    double* partials;              /* [partials_rows][9] workspace */
+    double* result;                /* [10] out */
+    float* ssim_map;               /* [H - 10][W - 10] out, or NULL */
+    int64_t partials_rows;
+    int32_t H, W, mask_ch, _pad;
+} VdnImageStatsArgs;
+int vdn_image_stats(const VdnImageStatsArgs* args_host, void* stream);
+/* the number of workgroup tiles of an H x W image = the rows of `partials` vdn_image_stats needs (0: H < 11 or W < 11) */
+int vdn_image_stats_tiles(int32_t H, int32_t W);
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,24 @@ class RaysGenerator:
                                                   align_corners=False, antialias=False)[0].permute(1, 2, 0)
         return msk.cpu().numpy()
 
+    def image_at_device(self, idx, resolution_level=1):
+        """image_at's image where it lives: [H/l, W/l, 3] float32 in [0,1] on the device, the same bilinear resize, contiguous."""
+        img = self.images[int(idx)]
+        l = int(resolution_level)
+        if l != 1:
+            img = torch.nn.functional.interpolate(img.permute(2, 0, 1)[None], size=(self.H // l, self.W // l), mode="bilinear",
+                                                  align_corners=False, antialias=False)[0].permute(1, 2, 0)
+        return img.contiguous()
+
+    def mask_at_device(self, idx, resolution_level=1):
+        """mask_at's mask where it lives: [H/l, W/l, 1] float32 on the device, the same bilinear resize, contiguous."""
+        msk = self.masks[int(idx)][..., :1]
+        l = int(resolution_level)
+        if l != 1:
+            msk = torch.nn.functional.interpolate(msk.permute(2, 0, 1)[None], size=(self.H // l, self.W // l), mode="bilinear",
+                                                  align_corners=False, antialias=False)[0].permute(1, 2, 0)
+        return msk.contiguous()
+
     def gen_rays_between(self, ratio, idx_0, idx_1, resolution_level=1):
         """poses.py:214-252: rays of a camera interpolated between two views - translation linearly, rotation by Slerp, both
         on the world-to-camera side as the reference does - with the first camera's intrinsics. -> rays_o, rays_v [H/l, W/l, 3].
