@@ -206,7 +206,7 @@ ARMS = {
     "VDN_LIB": dict(values=(), relation=None, held_by=None, reason="loads another build of the library: not an arm of this one"),
     "VDN_BUILD_VARIANT": dict(values=(), relation=None, held_by=None, reason="builds and loads a side copy of the library with other flags: not an arm of this one"),
     # ---- read by the library (getenv, once per process): a fresh child per arm; which kernel a launch picked is not visible from Python
-    "VDN_SDF2_WARM": _matrix(("0",), ("step_bf16", "render_inf"), "child", None, native="csrc/k_sdf_fwd2.h:884"),
+    "VDN_SDF2_WARM": _matrix(("0",), ("step_bf16", "render_inf"), "child", None, native="csrc/k_sdf_fwd2.h:740"),
     "VDN_PLANE_PREFETCH": _matrix(("1",), ("step_fp32", "step_bf16_two_chain"), "child", None, native="csrc/k_sdf_bwd.h:285"),
     "VDN_SDF0_SPLIT_MAX": _matrix(("0",), ("render_inf", "step_bf16"), "child", None, native="csrc/sdf_bf16.hip:15"),
 }

@@ -19,12 +19,10 @@
 //   static constexpr int total;                      chunks in the stream
 //   static constexpr int kt(int c);                  k-tiles of chunk c (0 beyond the stream)
 //   static constexpr bool bias(int c);               chunk c initialises its accumulator from its bias block
-//   using Acc;                                       the accumulator: fill(bias, with_bias), mfma<S>(fragment, X), kBiasRows, quad(g, lane)
 //   static constexpr bool certifies(int c);          step c waits and synchronises for the chunk(s) behind it
 //   static constexpr int wait(int c);                the vmcnt immediate of that wait (derived from the user's issue order)
 //   static constexpr bool dma_burst(int c);          step c issues its DMA pieces in one burst behind the barrier (else one per group)
 //   static constexpr int kPre, kGroup;               fragments read ahead of their MFMA (the pipe's PRE); MFMAs per scheduling group
-//   static constexpr int abl;                        timing-only ablations (development harness): 2 no MFMA, 4 no weight DMA, 8 no chunk barrier
 #pragma once
 #include "mlp_engine.h"
 
@@ -37,22 +35,12 @@ VDN_DEV void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// DMA addressing (round 5): immediate offsets, one M0 write per chunk (vdn_common.h: glds16_imm*). VDN_SDF2_DMA_IMM=0: the A/B arm
-// with one scalar base and one M0 write per piece.
-#ifndef VDN_SDF2_DMA_IMM
-#define VDN_SDF2_DMA_IMM 1
-#endif
-VDN_DEV void glds16_saddr(const char* base_uniform, unsigned lane_off, char* lds_wave_base) {
-    const unsigned lds = (unsigned)(size_t)lds_wave_base;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" ::"v"(lane_off), "s"(lds), "s"(base_uniform) : "memory", "m0");
-}
-
-// the 32x32x16 accumulator: lane = c + 32 h owns point c; register t = feature (t&3) + 8 (t>>2) + 4 h (vdn_common.h)
+// accumulator registers 4 g .. 4 g + 3 of a lane are features 4 quad_of(g) .. + 3 of the tile's natural order
+VDN_DEV int quad_of(int g, int lane) { return 2 * g + (lane >> 5); }
+// the accumulator of a chunk step (v_mfma_f32_32x32x16_bf16): lane = c + 32 h owns point c; register t = feature (t&3) + 8 (t>>2) + 4 h
+// (vdn_common.h)
 struct Acc32 {
     f32x16 w;
-    static constexpr int kBiasRows = 4;
-    // accumulator registers 4 g .. 4 g + 3 of this lane are features 4 quad(g) .. + 3 of the tile's natural order
-    static VDN_DEV int quad(int g, int lane) { return 2 * g + (lane >> 5); }
     VDN_DEV float operator[](int t) const { return w[t]; }
     VDN_DEV void fill(const f32x4 (&bias)[4], bool with_bias) {
 #pragma unroll
@@ -60,7 +48,6 @@ struct Acc32 {
     }
     template <int S, class ActT>
     VDN_DEV void mfma(const bf16x8& a, const ActT& X) { w = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, X.r[S], w, 0, 0, 0); }
-    VDN_DEV void add(const Acc32& o) { w += o.w; }
 };
 
 constexpr int kNoSplit = 1 << 30;
@@ -78,7 +65,6 @@ struct Pipe {
     const char* g2;     // chunks from SPLIT on: the second stream
     char* lds;          // ring base
     int wave, lane;
-    unsigned lane16;    // lane * 16
     bf16x8 fr[PRE];     // opening fragments of the next chunk step (already read)
     f32x4 bias[4];      // its bias rows
     unsigned voff0;     // lane * 16 + this wave's first byte in a chunk + 4096 (the centre of the pieces' immediate offsets)
@@ -89,38 +75,32 @@ struct Pipe {
         lds = smem;
         wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         lane = threadIdx.x & 63;
-        lane16 = lane * 16;
-        voff0 = lane16 + wave * (kG * 1024) + 4096;
+        voff0 = lane * 16 + wave * (kG * 1024) + 4096;
         m0_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds + wave * (kG * 1024) + 4096);
     }
     // (the dump area of the warm-up's LDS-DMA: this wave's own first piece of ring slot 0 - vdn_common.h)
-    VDN_DEV char* warm_dump() const { return lds + wave * (VDN_SDF2_DMA_IMM ? kG * 1024 : 1024); }
+    VDN_DEV char* warm_dump() const { return lds + wave * (kG * 1024); }
     template <int C>
     VDN_DEV char* slot() const { return lds + (C % NSLOT) * STRIDE; }
-    // DMA piece I (of kG) of chunk C: 1 KiB, wave-uniform base + per-lane 32-bit offset (scalar-base addressing)
+    // DMA piece I (of kG) of chunk C: 1 KiB, wave-uniform base + per-lane 32-bit offset + immediate; one M0 write per chunk, by
+    // piece 0 (vdn_common.h: glds16_imm*)
     template <int C, int I>
     VDN_DEV void issue_piece() {
         constexpr long COFF = (C >= SPLIT ? (long)(C - SPLIT) : (long)C) * STRIDE;
         const char* base = C >= SPLIT ? g2 : g;
-#if VDN_SDF2_DMA_IMM
         static_assert(kG <= 8, "one group of immediate offsets");
         static_assert(COFF + STRIDE < (1L << 31), "32-bit chunk offsets");
         const unsigned voff = voff0 + (unsigned)COFF;
         if constexpr (I == 0) glds16_imm_m0add<(C % NSLOT) * STRIDE, glds_imm(I)>(base, voff, m0_wave);
         else glds16_imm<glds_imm(I)>(base, voff);
-#else
-        const int piece = wave + I * NWAVES;
-        glds16_saddr(base + (COFF + piece * 1024), lane16, slot<C>() + piece * 1024);
-#endif
     }
     template <int C>
     VDN_DEV void issue() {
         static_for<kG>([&](auto i_c) VDN_INL { issue_piece<C, decltype(i_c)::value>(); });
     }
-    template <class Acc>
     VDN_DEV void load_bias(const f32x4* b) {
 #pragma unroll
-        for (int q = 0; q < Acc::kBiasRows; ++q) bias[q] = b[Acc::quad(q, lane)];
+        for (int q = 0; q < 4; ++q) bias[q] = b[quad_of(q, lane)];
     }
     // reads that open chunk step C (its first fragments, and its bias rows)
     template <class PL, int C>
@@ -130,7 +110,7 @@ struct Pipe {
         const bf16x8* wa = reinterpret_cast<const bf16x8*>(w) + lane;
 #pragma unroll
         for (int s = 0; s < (PRE < 2 * KT ? PRE : 2 * KT); ++s) fr[s] = wa[s * 64];
-        if constexpr (PL::bias(C)) load_bias<typename PL::Acc>(reinterpret_cast<const f32x4*>(w + KT * 2048));
+        if constexpr (PL::bias(C)) load_bias(reinterpret_cast<const f32x4*>(w + KT * 2048));
     }
     // ring start: chunks 0 .. DEPTH-1 in flight, chunk 0 certified, its opening fragments read. Call it behind every ordinary
     // load / store of the prologue (nothing but counted operations may be younger than a DMA): it drains them first.
@@ -139,7 +119,7 @@ struct Pipe {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         static_for<DEPTH>([&](auto c_c) VDN_INL {
             constexpr int C = decltype(c_c)::value;
-            if constexpr (C < PL::total && !(PL::abl & 4)) issue<C>();
+            if constexpr (C < PL::total) issue<C>();
         });
         wait_vmcnt<(DEPTH - 1 < PL::total - 1 ? DEPTH - 1 : PL::total - 1) * kG>();
         __builtin_amdgcn_s_barrier();
@@ -152,18 +132,18 @@ struct Pipe {
 // of NG (kGroup MFMAs per group). Group 0 certifies; the DMA pieces of chunk C+DEPTH follow (in a burst, or one per group); the
 // tail reads the opening fragments of chunk C+1.
 template <class PL, int C, class PipeT, class ActT, class Group>
-VDN_DEV typename PL::Acc chunk_step(PipeT& pp, const ActT& X, Group&& group) {
+VDN_DEV Acc32 chunk_step(PipeT& pp, const ActT& X, Group&& group) {
     static_assert(PL::kPre == PipeT::kPre, "the pipe holds the opening fragments");
     constexpr int kPre = PL::kPre, kGroup = PL::kGroup, kG = PipeT::kG, DEPTH = PipeT::kDepth;
     constexpr int KT = PL::kt(C);
     constexpr int NS = KT * 2, NG = (NS + kGroup - 1) / kGroup;
     constexpr int KTN = PL::kt(C + 1);
     constexpr bool HAS_NEXT = C + 1 < PL::total;
-    constexpr bool HAS_DMA = C + DEPTH < PL::total && !(PL::abl & 4);
+    constexpr bool HAS_DMA = C + DEPTH < PL::total;
     const bf16x8* wa = reinterpret_cast<const bf16x8*>(pp.template slot<C>()) + pp.lane;
     const bf16x8* wn = reinterpret_cast<const bf16x8*>(pp.template slot<C + 1>()) + pp.lane;
     bf16x8 fr[NS];
-    typename PL::Acc acc;
+    Acc32 acc;
     constexpr int PF = kPre < NS ? kPre : NS;                       // fragments of this chunk read by the previous step
     constexpr int PFN = kPre < 2 * KTN ? kPre : 2 * KTN;            // fragments of the next chunk this step reads
     static_for<PF>([&](auto s_c) VDN_INL { fr[decltype(s_c)::value] = pp.fr[decltype(s_c)::value]; });
@@ -174,17 +154,12 @@ VDN_DEV typename PL::Acc chunk_step(PipeT& pp, const ActT& X, Group&& group) {
         constexpr int s0 = gi * kGroup, s1 = (gi + 1) * kGroup < NS ? (gi + 1) * kGroup : NS;
         static_for<s1 - s0>([&](auto j_c) VDN_INL {
             constexpr int s = s0 + decltype(j_c)::value;
-            if constexpr (PL::abl & 2) {
-                const bf16x8 keep = fr[s];
-                asm volatile("" ::"v"(keep));
-            } else {
-                acc.template mfma<s>(fr[s], X);
-            }
+            acc.template mfma<s>(fr[s], X);
         });
         if constexpr (gi == 0 && HAS_NEXT && PL::certifies(C)) {
             __builtin_amdgcn_sched_barrier(0);      // the step's first MFMAs are in the pipe while the wave waits
             wait_vmcnt<PL::wait(C)>();
-            if constexpr (!(PL::abl & 8)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -208,7 +183,7 @@ VDN_DEV typename PL::Acc chunk_step(PipeT& pp, const ActT& X, Group&& group) {
                 static_for<(PFN > PF ? PFN - PF : 0)>([&](auto e_c) VDN_INL { pp.fr[PF + decltype(e_c)::value] = wn[(PF + decltype(e_c)::value) * 64]; });
         });
         if constexpr (gi == NG - 1 && HAS_NEXT && KTN > 0 && PL::bias(C + 1)) {
-            pp.template load_bias<typename PL::Acc>(reinterpret_cast<const f32x4*>(pp.template slot<C + 1>() + KTN * 2048));
+            pp.load_bias(reinterpret_cast<const f32x4*>(pp.template slot<C + 1>() + KTN * 2048));
         }
         group(g_c, std::integral_constant<int, NG>{});
         __builtin_amdgcn_sched_barrier(0);

@@ -77,11 +77,7 @@ VDN_DEV void sdf_fwd_body(const SdfArgs& a, char* smem) {
                     o.hv[t] = a_;
                     o.sv[t] = b_;
                 } else {
-#if defined(VDN_ABLATE) && VDN_ABLATE == 1
-                    o.hv[t] = acc;
-#else
                     o.hv[t] = softplus100_fast(acc);
-#endif
                 }
             },
             [&D, l, S, Hs, PS, p, ok, h, derive](int nt, const HS& o, int) VDN_INL {

@@ -37,13 +37,6 @@ namespace sdf2 {
 #ifndef VDN_SDF2_GROUP
 #define VDN_SDF2_GROUP 2
 #endif
-#ifndef VDN_SDF2_ABL
-#define VDN_SDF2_ABL 0   // timing-only ablations (development harness), bit mask: 1 no epilogue math, 2 no MFMA, 4 no weight DMA, 8 no chunk barrier
-#endif
-#ifndef VDN_SDF2_S16
-#define VDN_SDF2_S16 0   // MFMA shape of the chunk steps: 0 = v_mfma_f32_32x32x16_bf16, 1 = v_mfma_f32_16x16x32_bf16 (same 32-point x 32-feature tile per wave)
-#endif
-constexpr bool kS16 = VDN_SDF2_S16 != 0;
 #ifndef VDN_SDF2_B2
 // Barrier cadence of instantiations whose ring has DEPTH + 2 slots (the others re-synchronise every chunk step): 1 = TWO chunks
 // certified per workgroup barrier, i.e. one barrier every second chunk step; 2 (default, round 6) = that in front of the sweep only;
@@ -63,45 +56,12 @@ constexpr float kC1 = 144.26950408889634f;    // 100 log2(e)
 constexpr float kVSave = kC1 / 255.0f;        // 255 sigma u -> saved V plane (100 log2(e) v)
 constexpr int kSTiles = 63;             // softplus' tiles per point block: 8 + 8 + 8 + 7 + 8 + 8 + 8 + 8
 
-// ---- the two MFMA shapes ------------------------------------------------------------------------------------------
-// Shape 0 (32x32x16): lane = c + 32 h owns point c; accumulator register t = feature (t&3) + 8 (t>>2) + 4 h (vdn_common.h).
-// Shape 1 (16x16x32, round 6: the shape on which the chip holds the higher clock - MI355X_MICROARCH.md, DVFS give-back item 7):
-// the wave's 32 x 32 tile is four 16 x 16 accumulators [ph][fh] (point half, feature half); lane = c16 + 16 q owns points c16 and
-// c16 + 16, and LOGICAL accumulator register t = 8 ph + 4 fh + i is MFMA row 4 q + i of feature half fh. The weight image
-// ("sdf2x" / "full2x" / "c2x", vdn_hip/images.py) assigns MFMA row 4 q + i of half fh to feature 16 (q>>1) + 8 fh + 4 (q&1) + i, so
-// that registers 8 ph .. 8 ph + 7 of lane (c16, q) are - as in shape 0 - one 16-byte unit of the PT32 plane layout
-// (mlp_engine.h): unit (k = q>>1, h = q&1) of point 16 ph + c16, and the B fragment of k-step T for point half ph IS tile T's
-// packed unit. Planes, bias blocks and tails are the same bytes in both shapes; the A fragments are a permutation of 16-byte units.
-// Per-point scalar work (encoding, its adjoint, outputs) stays on the "home" lanes of shape 0 (lane c + 32 h); operands cross
-// between the two lane geometries through a wave-private LDS scratch, three times per launch.
-#if VDN_SDF2_S16
-struct AccT {
-    f32x4 v[4];         // [2 ph + fh]
-    static constexpr int kBiasRows = 2;
-    static VDN_DEV int quad(int g, int lane) { return 4 * (lane >> 5) + 2 * (g & 1) + ((lane >> 4) & 1); }
-    VDN_DEV float operator[](int t) const { return v[t >> 2][t & 3]; }
-    VDN_DEV void fill(const f32x4 (&bias)[4], bool with_bias) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) v[g] = with_bias ? bias[g & 1] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    // fragment s of a chunk = (k-step s >> 1 of 32 inputs, feature half s & 1), against both point halves
-    template <int S, class ActT>
-    VDN_DEV void mfma(const bf16x8& a, const ActT& X) {
-        v[S & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, X.r[S & ~1], v[S & 1], 0, 0, 0);
-        v[2 + (S & 1)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, X.r[(S & ~1) + 1], v[2 + (S & 1)], 0, 0, 0);
-    }
-    VDN_DEV void add(const AccT& o) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) v[g] += o.v[g];
-    }
-};
-#else
-using AccT = cstream::Acc32;
-#endif
-// accumulator registers 4 g .. 4 g + 3 of this lane are features 4 quad_of(g) .. + 3 of the tile's natural order
-VDN_DEV int quad_of(int g, int lane) { return AccT::quad(g, lane); }
-// the point half a logical register pair belongs to
-constexpr int ph_of_pair(int pr) { return kS16 ? pr >> 2 : 0; }
+// ---- the MFMA shape ---------------------------------------------------------------------------------------------
+// v_mfma_f32_32x32x16_bf16: lane = c + 32 h owns point c; accumulator register t = feature (t&3) + 8 (t>>2) + 4 h (vdn_common.h),
+// so registers 8 k .. 8 k + 7 of a lane are one 16-byte unit of the PT32 plane layout (mlp_engine.h) and the B fragment of k-step
+// 2 T + k IS tile T's packed unit.
+using cstream::Acc32;
+using cstream::quad_of;
 
 // ---- compile-time program of the chunk stream -------------------------------------------------------------------
 // COL0 / COLH / COLOUT (MODE 2): the colour head behind the sweep (fields.py:148-176): first layer [feature (8 tiles) | points,
@@ -192,8 +152,7 @@ constexpr int wait_count(int c) {
 template <int MODE, bool SAVE, int NSLOT, int DEPTH>
 struct StepPolicy {
     using PG = Prog<MODE>;
-    using Acc = AccT;
-    static constexpr int total = PG::total, kPre = sdf2::kPre, kGroup = sdf2::kGroup, abl = VDN_SDF2_ABL;
+    static constexpr int total = PG::total, kPre = sdf2::kPre, kGroup = sdf2::kGroup;
     static constexpr int kt(int c) { return PG::kt_of(c); }
     static constexpr bool bias(int c) { return PG::bias_of(c); }
     // B2: with two spare ring slots the workgroup re-synchronises every SECOND step - the even step certifies chunks C+1 and C+2
@@ -208,49 +167,30 @@ struct StepPolicy {
     static constexpr bool dma_burst(int c) { return sdf2::dma_burst<MODE, SAVE>(c); }
 };
 
-#ifndef VDN_SDF2_SP
-#define VDN_SDF2_SP 1   // softplus form: 0 = max(t,0) + log2(1 + 2^-|t|), sigma from 2^-g;  1 = med3(log2(1 + 2^t), t, 25), sigma from 1 / (1 + 2^t)
-#endif
-// softplus in scaled units, t -> g = log2(1 + 2^t), and E = 2^-g = 1 - sigma(100 a) = 1 / (1 + 2^t).
-// Form 1 (one VALU instruction fewer per value, and E no longer waits for g): w = 1 + 2^t overflows to +inf from t = 128 on
+// softplus in scaled units, t -> g = log2(1 + 2^t), and E = 2^-g = 1 - sigma(100 a) = 1 / (1 + 2^t), as g = med3(log2(1 + 2^t), t, 25)
+// and E = 1 / (1 + 2^t) (one VALU instruction fewer per value than max(t,0) + log2(1 + 2^-|t|) with E = 2^-g, and E does not wait
+// for g): w = 1 + 2^t overflows to +inf from t = 128 on
 // (log2 -> +inf) and for t >= 25 the f32 value of log2(w) is t itself, so g = median(log2(w), t, 25) - one v_med3_f32 - is exact
 // on both sides: below 25 the logarithm lies between t and 25, from 25 on t lies between 25 and the (possibly infinite)
 // logarithm. For t <= -25 w rounds to 1 and g to 0 (true value < 2^-25 units = 2e-10 in h). E = 1/w: 0 at +inf, 1 at w = 1.
 struct SpE { float g, e; };
 VDN_DEV SpE softplus_sigma(float t) {
     SpE r;
-#if VDN_SDF2_ABL & 1
-    r.g = t; r.e = t;
-    return r;
-#endif
-#if VDN_SDF2_SP == 1
     const float w = 1.0f + __builtin_amdgcn_exp2f(t);
     r.g = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(w), t, 25.0f);
     r.e = __builtin_amdgcn_rcpf(w);
-#else
-    const float e = __builtin_amdgcn_exp2f(-fabsf(t));
-    r.g = relu0(t) + __builtin_amdgcn_logf(1.0f + e);
-    r.e = __builtin_amdgcn_exp2f(-r.g);
-#endif
     return r;
 }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef VDN_SDF2_WT_SAVES
-#define VDN_SDF2_WT_SAVES 1
-#endif
-// 16-byte store of a saved-plane piece. VDN_SDF2_WT_SAVES = 1: write-through (sc1), which does not keep the line in this XCD's
+// 16-byte store of a saved-plane piece: write-through (sc1), which does not keep the line in this XCD's
 // L2 - the planes are next read by other kernels, from HBM anyway, while the L2 is what feeds this kernel's weight stream
 // (development harness, 65 536 rows, variants interleaved: training launch 205.6 -> 196.8 us, inference launch 161.9 -> 157.1)
 VDN_DEV void plane_store16(unsigned short* p, const u32x4& v) {
-#if VDN_SDF2_WT_SAVES
 #if VDN_SAVE_NT             // non-temporal as well (vdn_common.h)
     asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 #else
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#endif
-#else
-    *reinterpret_cast<u32x4*>(p) = v;
 #endif
 }
 
@@ -356,8 +296,6 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     const bool ok = wr.ok;
     const long p = wr.row, pd = wr.point;
     const bool col_wg = MODE != 3 || ex.n_col_rows == nullptr || (long)blockIdx.x * (kWaves * 32) < (long)*ex.n_col_rows;     // (ShadeExtra::n_col_rows)
-    const int c16 = lane & 15, q4 = lane >> 4;      // shape 1: this lane's column of both 16-point halves, and its row quad
-    (void)c16; (void)q4;
 
     float xin[3];
     float px[3] = {0.0f, 0.0f, 0.0f}, dir[3] = {0.0f, 0.0f, 0.0f};     // MODE 2: the point and the view direction (the colour head's inputs)
@@ -391,19 +329,8 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     ST* feat = reinterpret_cast<ST*>(a.feat);
     const long PS = P::plane(a.P, 256);
     const long prow = (p >> 5) * (32L * 256) + h * 256 + (p & 31) * 8;       // PT32 offset of this lane's 16-byte pieces (mlp_engine.h)
-    // shape 1: the lane's unit (k = q4 >> 1, h = q4 & 1) of its two points, rows clamped as work_row clamps them
-    long prow2[2] = {0, 0};
-    if constexpr (kS16) {
-        const long n_rows = a.active_idx != nullptr ? (long)*a.n_active : (long)a.P;
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-            const long raw = ((long)blockIdx.x * kWaves + pp.wave) * 32 + 16 * ph + c16;
-            const long r = raw < n_rows ? raw : (n_rows > 0 ? n_rows - 1 : 0);
-            prow2[ph] = (r >> 5) * (32L * 256) + (q4 >> 1) * 512 + (q4 & 1) * 256 + (r & 31) * 8;
-        }
-    }
-    // element offset of 16-byte piece k of tile T in a [*, 256] PT32 plane: shape 0 k = the tile's k-step, shape 1 k = the point half
-    auto piece = [&](int T, int k) VDN_INL -> long { return kS16 ? prow2[k] + T * 1024 : prow + T * 1024 + 512 * k; };
+    // element offset of 16-byte piece k (the tile's k-step) of tile T in a [*, 256] PT32 plane
+    auto piece = [&](int T, int k) VDN_INL -> long { return prow + T * 1024 + 512 * k; };
     const float inv_scale = 1.0f / a.scale;
     // the input loads above have to be back first: the compiler waits for them with vmcnt(0), which would also wait for younger
     // warm-up loads; behind this wait the stream arrives in L2 while the encoding below is computed from registers
@@ -421,24 +348,6 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
     float col[3] = {0.0f, 0.0f, 0.0f};      // MODE 2: the sampled colour of this lane's point
     SStore<NLDS> SS;
     SS.lds = smem + kRing + kW8 + pp.wave * (NLDS * 1024) + lane * 16;
-    // shape 1: wave-private scratch for the crossings between home lanes and tile lanes. MODE >= 1: the wave's S region (not yet /
-    // no longer holding softplus' tiles when used); MODE 0: a piece of the ring's last slot, which no DMA touches before step 0
-    static_assert(!kS16 || MODE == 0 || NLDS * 1024 >= 32 * 272, "exchange scratch");
-    static_assert(!kS16 || NSLOT - 1 >= DEPTH, "the last ring slot is free at the start");
-    char* const xch = MODE >= 1 ? smem + kRing + kW8 + pp.wave * (NLDS * 1024) : smem + (NSLOT - 1) * kStride + pp.wave * 4096;
-    // NF fragments in home-lane form (unit (s, h, c) = lane c + 32 h of fragment s) -> the same units in tile-lane form:
-    // fragment 2 T + ph of lane (c16, q4) = unit (s = 2 T + (q4 >> 1), h = q4 & 1, c = 16 ph + c16)
-    auto to_tile_lanes = [&](bf16x8* fr, auto nf_c) VDN_INL {
-        constexpr int NF = decltype(nf_c)::value;
-#pragma unroll
-        for (int s = 0; s < NF; ++s) *reinterpret_cast<bf16x8*>(xch + s * 1024 + lane * 16) = fr[s];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NF; ++s)
-            fr[s] = *reinterpret_cast<const bf16x8*>(xch + ((s & ~1) + (q4 >> 1)) * 1024 + (q4 & 1) * 512 + (16 * (s & 1) + c16) * 16);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    };
-
     // positional encoding in scaled units: X tiles 0,1 (layer 0) and a copy for the skip input of layer 4 (tiles 7,8):
     // tile 8 of X is not touched by anything else, tile 7's copy waits in registers
     bf16x8 pe7[2];
@@ -463,48 +372,27 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                 for (int kt = 0; kt < 2; ++kt) P::store_tile(reinterpret_cast<ST*>(a.PE), p, 64, kt, h, vals_tile<64>(pe, h, kt), true);
             }
         }
-        if constexpr (kS16) to_tile_lanes(&X.r[0], std::integral_constant<int, 4>{});
         pe7[0] = X.r[0]; pe7[1] = X.r[1];
         X.r[16] = X.r[2]; X.r[17] = X.r[3];
     }
     // ring start, behind the PE stores: it drains the ordinary loads and stores above - nothing but DMA and counted stores from here on
     pp.template start<PL>();
 
-    AccT acc_prev;              // accumulator of the previous chunk's tile (its epilogue runs under this chunk's MFMAs)
+    Acc32 acc_prev;             // accumulator of the previous chunk's tile (its epilogue runs under this chunk's MFMAs)
     u32x4 sq_prev;              // 255 sigma of the previous chunk's tile: read by the sweep's epilogue, built by a hidden layer's
     u32x4 sq_v7;                // 255 sigma_7 tile while v7 is formed
     unsigned hold0 = 0, hold1 = 0;  // a pair's values waiting for their partners (one 4-value pack / one 16-byte store)
     unsigned fhold0 = 0, fhold1 = 0, vhold0 = 0, vhold1 = 0;    // first halves of 16-byte plane pieces (feature / V)
     f32x4 w8hold;               // W8 row 0 at the features of the pair being worked on
-    float sdf_dot[2] = {0.0f, 0.0f};    // this lane's part of  W8[0,:] . g8  (f32), per point half (shape 0: [0] only)
-    float nz2[2] = {0.0f, 0.0f};        // shape 1: nz of the lane's two points
-    AccT UPE[2];                // d sdf / d(PE) tiles (W4^T rows 7,8 and W0^T)
+    float sdf_dot = 0.0f;       // this lane's part of  W8[0,:] . g8  (f32)
+    Acc32 UPE[2];               // d sdf / d(PE) tiles (W4^T rows 7,8 and W0^T)
     float n[3] = {0.0f, 0.0f, 0.0f};
     auto pe_backward = [&](bool first) VDN_INL {      // n += J_PE^T u  (transpose Jacobian of the encoding)
         float u[39];
-#if VDN_SDF2_S16
-        {   // tile lanes -> home lanes through the scratch: f32 [32 points][68] (272-byte rows: the b128 reads of 32 rows spread over the banks)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<f32x4*>(xch + (16 * (g >> 1) + c16) * 272 + (32 * t + 4 * quad_of(g, lane)) * 4) = UPE[t].v[g];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 10; ++i) {
-                const f32x4 r = *reinterpret_cast<const f32x4*>(xch + c * 272 + i * 16);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (4 * i + j < 39) u[4 * i + j < 39 ? 4 * i + j : 0] = r[j];
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-#else
         {
             const f32x16 upe[2] = {UPE[0].w, UPE[1].w};
             tiles_vals<39, 2>(upe, h, u);
         }
-#endif
         // u = u_4[PE part] + u_0 for the ray adjoint (VdnSdfArgs.U_pe); vector-memory operations the wait counts do not
         // know of are harmless: they only make a counted wait return later
         if (a.U_pe != nullptr && ok && h == 0) {
@@ -541,7 +429,7 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                         // the sdf row of the last layer in f32 on the VALU, from the unrounded activations: 2 FMAs per pair on
                         // one layer's epilogue, and the output that the alpha multiplies by inv_s loses no bits to bf16
                         if constexpr ((pr & 1) == 0) w8hold = *(reinterpret_cast<const f32x4*>(pp.template slot<CP + 1>() + kTail) + (8 * T + quad_of(pr >> 1, lane)));
-                        sdf_dot[ph_of_pair(pr)] = fmaf(g0, w8hold[2 * (pr & 1)], fmaf(g1, w8hold[2 * (pr & 1) + 1], sdf_dot[ph_of_pair(pr)]));
+                        sdf_dot = fmaf(g0, w8hold[2 * (pr & 1)], fmaf(g1, w8hold[2 * (pr & 1) + 1], sdf_dot));
                     }
                     unsigned pk = pack_bf16x2(g0, g1);
                     asm volatile("" : "+v"(pk));
@@ -652,9 +540,8 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                     float a0 = acc_prev[2 * pr], a1 = acc_prev[2 * pr + 1];
                     if constexpr (L.kind == COL0) {
                         if constexpr ((pr & 1) == 0) w8hold = *(reinterpret_cast<const f32x4*>(pp.template slot<CP + 1>() + kTail) + (8 * T + quad_of(pr >> 1, lane)));
-                        const float nzp = kS16 ? nz2[ph_of_pair(pr)] : nz;
-                        a0 = fmaf(w8hold[2 * (pr & 1)], nzp, a0);
-                        a1 = fmaf(w8hold[2 * (pr & 1) + 1], nzp, a1);
+                        a0 = fmaf(w8hold[2 * (pr & 1)], nz, a0);
+                        a1 = fmaf(w8hold[2 * (pr & 1) + 1], nz, a1);
                     }
                     unsigned pk = pack_bf16x2(relu0(a0), relu0(a1));
                     asm volatile("" : "+v"(pk));
@@ -667,19 +554,8 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
             } else if constexpr (L.kind == COLOUT) {
                 // rows 0..2 of the output tile = registers 0..2 of the h = 0 lanes (fields.py:166-171)
                 if constexpr (PB == 0) {
-                    if constexpr (kS16) {
-                        // rows 0..2 = registers 0..2 of feature half 0 of the q4 = 0 lanes, per point half: home lane c takes its point's from
-                        // lane c & 15 (itself for c < 16)
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) {
-                            const float lo = acc_prev[j], hi = __shfl(acc_prev[8 + j], lane & 15);
-                            const float x = (lane & 16) ? hi : lo;
-                            col[j] = ex.squeeze_out ? sigmoidf_(x) : relu0(x);
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) col[j] = ex.squeeze_out ? sigmoidf_(acc_prev[j]) : relu0(acc_prev[j]);
-                    }
+                    for (int j = 0; j < 3; ++j) col[j] = ex.squeeze_out ? sigmoidf_(acc_prev[j]) : relu0(acc_prev[j]);
                 }
             }
         }
@@ -711,36 +587,24 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
             u32x4 sq_next;
             if constexpr (sweep_tile) sq_next = SS.template get<PG::s_tile0(L.l) + T>();
             const auto& Xin = L.kind == COL0 ? F : ((LI & 1) ? Y : X);
-            const AccT acc_cur = cstream::chunk_step<PL, C>(pp, Xin, [&](auto g_c, auto) VDN_INL {
+            const Acc32 acc_cur = cstream::chunk_step<PL, C>(pp, Xin, [&](auto g_c, auto) VDN_INL {
                 constexpr int gi = decltype(g_c)::value;
                 epilogue(std::integral_constant<int, CP>{}, std::integral_constant<int, pair_begin(gi, GA)>{},
                          std::integral_constant<int, pair_begin(gi + 1, GA)>{});
             });
             if constexpr (L.kind == SWEEP_SKIP && T >= 7) UPE[T - 7] = acc_cur;
-            if constexpr (L.kind == SWEEP_PE) {
-                // shape 1: ONE crossing to the home lanes, on u_4[PE part] + u_0 (the encoding's adjoint is linear)
-                if constexpr (kS16) UPE[T].add(acc_cur);
-                else UPE[T] = acc_cur;
-            }
+            if constexpr (L.kind == SWEEP_PE) UPE[T] = acc_cur;
             if constexpr (L.kind == LAST && T == L.nt - 1) {
                 // sdf = W8[0,:] . h8 + b8[0]: the f32 dot of layer 7's epilogue (g8 = 100 log2(e) h8), the bias from this
                 // chunk's bias block (row 0); the MFMA's own bf16 value of the row is not used
                 const float b0 = *reinterpret_cast<const float*>(pp.template slot<C>() + L.kt * 2048);
-                float dot;
-                if constexpr (kS16) {       // the four row quads of a point; home lane c + 32 h is a tile lane of point half (c >> 4)
-                    float d0 = sdf_dot[0], d1 = sdf_dot[1];
-                    d0 += __shfl_xor(d0, 16); d1 += __shfl_xor(d1, 16);
-                    d0 += __shfl_xor(d0, 32); d1 += __shfl_xor(d1, 32);
-                    dot = (lane & 16) ? d1 : d0;
-                } else {
-                    dot = sdf_dot[0] + __shfl_xor(sdf_dot[0], 32);
-                }
+                const float dot = sdf_dot + __shfl_xor(sdf_dot, 32);
                 sdf_keep = fmaf(dot, 1.0f / kC1, b0) * inv_scale;
                 if (ok && h == 0) a.sdf[sdf_idx] = sdf_keep;
             }
             acc_prev = acc_cur;
             if constexpr (sweep_tile) sq_prev = sq_next;
-            if constexpr ((!kS16 && L.kind == SWEEP_SKIP && T == 8) || (L.kind == SWEEP_PE && T == 1)) pe_backward(kS16 || L.kind == SWEEP_SKIP);
+            if constexpr ((L.kind == SWEEP_SKIP && T == 8) || (L.kind == SWEEP_PE && T == 1)) pe_backward(L.kind == SWEEP_SKIP);
             if constexpr (COL && L.kind == SWEEP_PE && T == 1) {
                 // the normal is complete: the colour head's small input tile [points (3), PE4(view) (27), normal x, y] (fields.py:154;
                 // k order of the "c2" stream), z component kept in f32
@@ -761,14 +625,6 @@ __global__ __launch_bounds__(kWaves * 64, MODE == 0 ? 2 : 1) void sdf_fwd2_kerne
                 small[31] = n[1] * a.scale;
                 nz = n[2] * a.scale;
                 F.set(8, vals_tile<32>(small, h, 0));
-                if constexpr (kS16) {
-                    to_tile_lanes(&F.r[16], std::integral_constant<int, 2>{});
-                    reinterpret_cast<float*>(xch)[c] = nz;
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    nz2[0] = reinterpret_cast<const float*>(xch)[c16];
-                    nz2[1] = reinterpret_cast<const float*>(xch)[16 + c16];
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
                 if constexpr (MODE == 3) {
                     // the colour head's 33 small inputs as rendernet_fwd_kernel saves them ([rows, 64]: the weight-gradient GEMM's operand).
                     // Uncounted vector-memory operations only make a counted wait return later (as the U_pe stores above)

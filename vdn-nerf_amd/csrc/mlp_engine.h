@@ -94,9 +94,7 @@ struct WStream {
         if (!all_issue) younger = 0;
         const int ahead = min(issued - cur - 1, DEPTH - 1);      // chunks after `cur` already in flight
         wait_vm(younger + ahead * G);
-#if !defined(VDN_ABLATE) || VDN_ABLATE != 3
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
         if (issued < total) issue_next();
         return lds + (cur % NSLOT) * STRIDE;
@@ -299,10 +297,6 @@ struct BF16 {
 #pragma unroll
             for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
         }
-#if defined(VDN_ABLATE) && VDN_ABLATE == 2
-        (void)wa;
-        return acc;
-#endif
         // Fragment reads are software-pipelined PRE deep under the MFMAs. Left to itself hipcc emits
         // {2 x ds_read_b128, s_waitcnt lgkmcnt(0), 2 x MFMA} x 8 per tile - a full LDS round trip exposed eight
         // times (measured ~1700 cycles per tile for 512 cycles of MFMA) - so the order is pinned with
@@ -406,16 +400,8 @@ struct BF16 {
     static VDN_DEV raw_tile load_raw(const unsigned short* base, long row, int ld, int tile, int h) {
         const unsigned short* p = base + (row >> 5) * (32L * ld) + tile * 1024 + h * 256 + (row & 31) * 8;
         raw_tile r;
-#ifdef VDN_PLANE_LD_NT          // (development A/B: the chain kernels read a saved plane once)
-        typedef unsigned nt_u32x4 __attribute__((ext_vector_type(4)));
-        const nt_u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4*>(p));
-        const nt_u32x4 b = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4*>(p + 512));
-        r.k[0] = make_uint4(a[0], a[1], a[2], a[3]);
-        r.k[1] = make_uint4(b[0], b[1], b[2], b[3]);
-#else
         r.k[0] = *reinterpret_cast<const uint4*>(p);
         r.k[1] = *reinterpret_cast<const uint4*>(p + 512);
-#endif
         return r;
     }
     static VDN_DEV f32x16 unpack(const raw_tile& t) {

@@ -36,8 +36,7 @@ using Pipe = cstream::Pipe<NWAVES, STRIDE, NSLOT, DEPTH, cstream::kNoSplit, kPre
 // The engine's policy of the chunk step (chunk_stream.h): the program PG on a pipe PipeT, every step certifies, every DMA is a burst
 template <class PG, class PipeT>
 struct Policy : PG {
-    using Acc = cstream::Acc32;
-    static constexpr int kPre = flow::kPre, kGroup = flow::kGroup, abl = 0;
+    static constexpr int kPre = flow::kPre, kGroup = flow::kGroup;
     static constexpr bool certifies(int) { return true; }
     static constexpr bool dma_burst(int) { return true; }
     // s_waitcnt vmcnt(N) that retires this wave's DMA of chunk c+1 in step c, before its barrier. Step j issues, in order: the

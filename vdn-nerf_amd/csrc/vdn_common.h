@@ -62,8 +62,8 @@ VDN_DEV int rho(int t, int h) { return (t & 3) + 8 * (t >> 2) + 4 * h; }
 #define VDN_DW_LD_NT 1
 #endif
 // ... and, in the SDF backward, of the loads that ARE the last reading: the V planes (read once) and the H planes' second reading
-// (fbar): 1 119 / 1 119 / 1 122 -> 1 113 / 1 115 / 1 112 us. The chain kernels' plane loads (mlp_engine.h: load_raw,
-// -DVDN_PLANE_LD_NT) as non-temporal: nothing (1 127 / 1 120 / 1 123).
+// (fbar): 1 119 / 1 119 / 1 122 -> 1 113 / 1 115 / 1 112 us. The chain kernels' plane loads (mlp_engine.h: load_raw)
+// as non-temporal: nothing (1 127 / 1 120 / 1 123).
 #ifndef VDN_BS_LDV_AUX
 #define VDN_BS_LDV_AUX 2
 #endif
