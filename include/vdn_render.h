@@ -1419,6 +1419,55 @@ typedef struct {
 } VdnTexProjectArgs;
 int vdn_tex_project(const VdnTexProjectArgs* args_host, void* stream);
 
+/* ---- textured meshes: texel colours from the photographs (csrc/mesh_photo.hip; vdn_hip/mesh.py: photo_colors, bake_texture(photos=)) ----
+ * vdn_tex_photo: one thread per texel point p visits the cameras k = 0 .. N - 1 in that order; no atomics, so every sum has one order
+ * and two runs - and two cell sizes of the grid - give the same bits. All arithmetic is double on the widened fp32 inputs, every
+ * product and sum rounded on its own (the file is built without contraction), sums left to right unless bracketed; only + - * / sqrt
+ * min max floor are used. x = points[p] is where the colour is looked up, y = anchors[p] (NULL: x) the texel's place on its triangle,
+ * f = face[p]. The unit normal n = g / sqrt((g0 g0 + g1 g1) + g2 g2), component by component: g = normals[p], one-sided; without
+ * `normals` g = e1 x e2 = (e1_1 e2_2 - e1_2 e2_1, e1_2 e2_0 - e1_0 e2_2, e1_0 e2_1 - e1_1 e2_0) of face f's record (e1 = b - a,
+ * e2 = c - a), two-sided. A normal whose length is zero or not finite sees no camera. Camera k, M = P_mat[k], c = centres[k],
+ * contributes iff, tested in this order:
+ *   1. in front: w = ((M20 x0 + M21 x1) + M22 x2) + M23 > 0; u and v are the rows 0 and 1 likewise, divided by w: the continuous pixel
+ *      position, pixel centres at integer coordinates (vdn_gen_rays' convention).
+ *   2. in frame: u >= 0, (W - 1) - u >= 0, v >= 0, (H - 1) - v >= 0 (NaN fails); m = min(min(u, (W - 1) - u), min(v, (H - 1) - v));
+ *      border b = min(1, m / feather) where feather > 0, else 1.
+ *   3. facing: r = c - x, cos = ((n0 r0 + n1 r1) + n2 r2) / sqrt((r0 r0 + r1 r1) + r2 r2), two-sided: cos = max(cos, -cos);
+ *      cos > cos_min; the weight w_k = (cos cos) b must be > 0.
+ *   4. unoccluded: the any-hit walk of vdn_ray_cast from o = c along d = y - c with the window 0 < t < 1 - eps, ignoring face f, finds
+ *      nothing. Ignoring the own face lets a lookup point that was moved a little under its coarse triangle keep its cameras; eps
+ *      keeps the neighbours across a shared edge from hiding the texel.
+ * Its colour is the bilinear value of image k at (u, v): x0 = floor(u), x1 = min(x0 + 1, W - 1), tx = u - x0, likewise in v, per
+ * channel col = ((1 - tx)(1 - ty) t00 + tx (1 - ty) t10) + ((1 - tx) ty t01 + tx ty t11), t10 the tap at (x1, y0). Then
+ * sum_c += w_k col, sum_w += w_k, and a w_k strictly greater than the best so far (0 at the start) makes k the best view - the lower
+ * index wins ties. blend = 0: colors = fp32(sum_c / sum_w), weight = fp32(sum_w); blend = 1: the best view's col and w_k. n_views
+ * counts the contributing cameras; best_view is the best in both modes. A texel no camera passes gets colour 0, weight 0, n_views 0,
+ * best_view -1. A face[p] outside [0, F) sets *error = 1 (the caller zeroes it first) and writes that row as unseen: nothing is
+ * indexed with it. The images are [N][H][W][3] fp32 in whatever channel order the caller holds; all image and record addressing is
+ * 64-bit. Status -1: a null pointer, P, N, F, H or W below 1, blend outside {0, 1}, cos_min or eps outside [0, 1), feather negative
+ * or not finite, a bad grid; -10: P, N, F, n_refs or the cell count beyond 32-bit indexing. */
+typedef struct {
+    const float* points;           /* [P][3] */
+    const float* anchors;          /* [P][3] or NULL (= points) */
+    const int32_t* face;           /* [P] */
+    const float* normals;          /* [P][3] or NULL (the faces' own, two-sided) */
+    const double* P_mat;           /* [N][3][4] row-major */
+    const double* centres;         /* [N][3] camera centres, -M^-1 p4 */
+    const float* images;           /* [N][H][W][3] in [0, 1] */
+    const float* records;          /* [F][12] */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1] */
+    const int32_t* refs;           /* [n_refs] */
+    float* colors;                 /* [P][3] out */
+    float* weight;                 /* [P] out */
+    int32_t* n_views;              /* [P] out */
+    int32_t* best_view;            /* [P] out */
+    int32_t* error;                /* [1] */
+    int64_t P, N, F, n_refs;
+    double lo_x, lo_y, lo_z, h, margin, cos_min, feather, eps;
+    int32_t nx, ny, nz, H, W, blend;
+} VdnTexPhotoArgs;
+int vdn_tex_photo(const VdnTexPhotoArgs* args_host, void* stream);
+
 
 /* ---- learnable poses in the training step: poses.py:16-47 + 168-212, dataset.py:111-118, renderer.py:335-359 ---------------
  * vdn_gen_rays_pose: vdn_gen_rays with the camera-to-world matrix made in the kernel from camera i's LearnPose parameters,

@@ -23,7 +23,8 @@ triangles that survive, count_simplified_faces is the count-only pass a face bud
 Textured meshes (csrc/mesh_texture.hip; the front door is vdn_train/mesh_texture.py): texture_layout gives every face a triangular
 patch of a per-face atlas, texel_points / project_points place a surface point under every texel, gather_atlas writes the shaded
 colours into the atlas, bake_texture is the three in a row; sample_texture looks an atlas up at points of the mesh and
-render_textured_view does that where rays hit."""
+render_textured_view does that where rays hit. photo_colors (csrc/mesh_photo.hip) colours the texel points from the photographs
+that see them instead of the colour network - bake_texture(photos=...)."""
 import math
 
 import numpy as np
@@ -1424,8 +1425,150 @@ def mean_edge_length(vertices, triangles):
     return float((p - p.roll(-1, dims=1)).norm(dim=2).mean())
 
 
+# ---- texel colours from the photographs (csrc/mesh_photo.hip) ---------------------------------------------------------
+# interface defaults, not measurements: the steepest viewing angle that still counts (cos 78 degrees), the width in pixels of the
+# band along an image's border over which its weight falls to zero, and visibility_votes' eps
+PHOTO_COS_MIN = 0.2
+PHOTO_FEATHER = 16.0
+PHOTO_EPS = 1e-4
+PHOTO_BLENDS = {"mean": 0, "best": 1}
+PHOTO_KEYS = ("P", "images", "cos_min", "feather", "eps", "blend", "fill")
+
+
+def _photo_scalars(cos_min, feather, eps, blend):
+    try:
+        c, fe, e = float(cos_min), float(feather), float(eps)
+    except (TypeError, ValueError):
+        raise ValueError("cos_min, feather and eps must be numbers, got %r, %r and %r" % (cos_min, feather, eps))
+    if not (0.0 <= c < 1.0):
+        raise ValueError("cos_min must be in [0, 1), got %r" % (cos_min,))
+    if not (fe >= 0.0 and fe < float("inf")):
+        raise ValueError("feather must be finite and not negative, got %r" % (feather,))
+    if not (0.0 <= e < 1.0):
+        raise ValueError("eps must be in [0, 1), got %r" % (eps,))
+    if blend not in PHOTO_BLENDS:
+        raise ValueError("blend must be one of %s, got %r" % (sorted(PHOTO_BLENDS), blend))
+    return c, fe, e, PHOTO_BLENDS[blend]
+
+
+def photo_colors(grid, points, face, P, images, normals=None, anchors=None, cos_min=PHOTO_COS_MIN, feather=PHOTO_FEATHER, eps=PHOTO_EPS,
+                 blend="mean"):
+    """The colour every texel point takes from the photographs that see it (vdn_tex_photo, include/vdn_render.h has the rules) ->
+    {"colors" fp32 [P,3], "weight" fp32 [P], "n_views" int32 [P], "best_view" int32 [P]} on the grid's device. grid: the MeshGrid of the
+    mesh; points [P,3] float CUDA: where the colour is looked up; face [P] int32 CUDA: the face of each point; P [N,3,4] (taken as
+    float64, as visibility_votes takes it); images [N,H,W,3] float32 contiguous on the grid's device, in [0, 1], in whatever channel
+    order the caller holds - the colours come back in it. Camera k colours a point iff the point is in front of it, inside its frame,
+    faces it (cos > cos_min against `normals` [P,3], one-sided - or against the face's own normal, two-sided, when None) and no face
+    but its own lies on the segment from the camera's centre to anchors[p] (default: the point), 0 < t < 1 - eps. The weight is
+    cos^2, scaled down linearly over the `feather` pixels next to the image's border. blend "mean": the weighted mean, weight = the
+    sum; "best": the camera with the largest weight (the lower index on a tie). A point no camera passes has colour 0, weight 0,
+    n_views 0, best_view -1. ValueError on CPU tensors, wrong shapes or dtypes, a singular camera, scalars out of range or a face
+    outside [0, F) (found on the device; one host read). Pass the points face-major, as texel_points gives them."""
+    if not isinstance(grid, MeshGrid):
+        raise ValueError("grid must be a MeshGrid of the mesh")
+    dev = grid.device
+    if not torch.is_tensor(points) or not torch.is_tensor(face):
+        raise ValueError("photo_colors needs points and face as CUDA tensors")
+    x = _rows("points", points)
+    n = x.shape[0]
+    if not (face.is_cuda and face.dtype == torch.int32 and tuple(face.shape) == (n,)):
+        raise ValueError("face must be an int32 [%d] CUDA tensor" % n)
+    nrm = anc = None
+    if normals is not None:
+        if not torch.is_tensor(normals):
+            raise ValueError("normals must be a float CUDA tensor [P,3]")
+        nrm = _rows("normals", normals, n)
+    if anchors is not None:
+        if not torch.is_tensor(anchors):
+            raise ValueError("anchors must be a float CUDA tensor [P,3]")
+        anc = _rows("anchors", anchors, n)
+    if any(q is not None and q.device != dev for q in (x, face, nrm, anc)):
+        raise ValueError("points, face, normals and anchors must be on the grid's device")
+    if not (torch.is_tensor(images) and images.device == dev and images.dtype == torch.float32 and images.dim() == 4 and images.shape[3] == 3
+            and images.is_contiguous()):
+        raise ValueError("images must be a contiguous float32 [N,H,W,3] tensor on the grid's device")
+    c_min, fe, e, mode = _photo_scalars(cos_min, feather, eps, blend)
+    centres = camera_centres(P)
+    N, H, W = images.shape[0], images.shape[1], images.shape[2]
+    if centres.shape[0] != N:
+        raise ValueError("%d cameras for %d images" % (centres.shape[0], N))
+    out = {"colors": torch.zeros(n, 3, dtype=torch.float32, device=dev), "weight": torch.zeros(n, dtype=torch.float32, device=dev),
+           "n_views": torch.zeros(n, dtype=torch.int32, device=dev), "best_view": torch.full((n,), -1, dtype=torch.int32, device=dev)}
+    if n == 0 or N == 0 or grid.F == 0:
+        return out
+    if H < 1 or W < 1:
+        raise ValueError("images must have at least one pixel, got %d x %d" % (H, W))
+    Pd = torch.as_tensor(P).detach().to(device=dev, dtype=torch.float64).contiguous()
+    cd = torch.from_numpy(centres).to(dev)
+    fc = face.contiguous()
+    with torch.cuda.device(dev):
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        a = grid._geometry(lib.VdnTexPhotoArgs())
+        a.points, a.anchors, a.face, a.normals = x.data_ptr(), (None if anc is None else anc.data_ptr()), fc.data_ptr(), (None if nrm is None else nrm.data_ptr())
+        a.P_mat, a.centres, a.images = Pd.data_ptr(), cd.data_ptr(), images.data_ptr()
+        a.colors, a.weight, a.n_views, a.best_view = (out[k].data_ptr() for k in ("colors", "weight", "n_views", "best_view"))
+        a.error = err.data_ptr()
+        a.P, a.N, a.H, a.W, a.cos_min, a.feather, a.eps, a.blend = n, N, H, W, c_min, fe, e, mode
+        _call_sized("vdn_tex_photo", a, lib.stream_handle())
+        if int(err.item()):                                   # one host read: the error flag
+            raise ValueError("a face index is outside [0, %d)" % grid.F)
+    return out
+
+
+def _check_photos(photos):
+    if not (isinstance(photos, dict) and "P" in photos and "images" in photos):
+        raise ValueError('photos must be a dict with "P" [N,3,4] and "images" [N,H,W,3]')
+    unknown = sorted(set(photos) - set(PHOTO_KEYS))
+    if unknown:
+        raise ValueError("photos has the unknown keys %s (known: %s)" % (unknown, ", ".join(PHOTO_KEYS)))
+    _photo_scalars(photos.get("cos_min", PHOTO_COS_MIN), photos.get("feather", PHOTO_FEATHER), photos.get("eps", PHOTO_EPS), photos.get("blend", "mean"))
+    try:
+        fill = [float(x) for x in photos.get("fill", (0.5, 0.5, 0.5))]
+        assert len(fill) == 3
+    except (TypeError, ValueError, AssertionError):
+        raise ValueError("photos['fill'] must be three numbers, got %r" % (photos.get("fill"),))
+
+
+def _bake_photos(renderer, v, t, layout, anchors, face, photos, project, max_offset, batch):
+    """bake_texture's photo path: the texel points on their triangles are the anchors; the projected points look the colours up; the
+    SDF gradient of the last shade_points call is the normal (none without a renderer: the faces' own, two-sided); texels no camera
+    sees take the network's colour, or photos["fill"] without a renderer."""
+    dev = v.device
+    images = photos["images"]
+    images = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
+    if images.dtype != torch.float32:
+        raise ValueError("photos['images'] must be float32 [N,H,W,3] in [0, 1], got %s" % images.dtype)
+    images = images.to(dev).contiguous()
+    points, normals, net = anchors, None, None
+    if renderer is not None:
+        for _ in range(project):
+            sdf, normals, _c = shade_points(renderer, points, batch=batch)
+            points = project_step(points, anchors, sdf, normals, max_offset)
+        if project == 0:
+            _s, normals, net = shade_points(renderer, points, batch=batch)      # (the one extra call: its colours are the network bake)
+    grid = MeshGrid(v, t)
+    kw = {k: photos[k] for k in ("cos_min", "feather", "eps", "blend") if k in photos}
+    got = photo_colors(grid, points, face, photos["P"], images, normals=normals, anchors=anchors, **kw)
+    colors, unseen = got["colors"], got["n_views"] == 0
+    if renderer is None:
+        fill = torch.tensor([float(x) for x in photos.get("fill", (0.5, 0.5, 0.5))], dtype=torch.float64, device=dev).float()
+        colors = torch.where(unseen[:, None], fill[None], colors)
+    else:
+        rows = torch.nonzero(unseen)[:, 0]
+        if net is None:
+            net = shade_points(renderer, points[rows], batch=batch)[2]           # only the rows no camera sees
+        else:
+            net = net[rows]
+        if net.shape[1] != 3:
+            raise ValueError("a texture needs a colour network with three outputs, got %d" % net.shape[1])
+        colors[rows] = net
+    coverage = (colors.shape[0] - int(unseen.sum())) / colors.shape[0]          # one host read
+    return {"texture": gather_atlas(colors, layout), "uv": texture_uv(layout), "layout": layout, "points": points,
+            "coverage": coverage, "n_views": got["n_views"]}
+
+
 def bake_texture(renderer, vertices, triangles, texture_size=2048, patch=None, project=TEXTURE_PROJECT_ROUNDS, max_offset=None,
-                 shade=None, batch=1 << 20):
+                 shade=None, batch=1 << 20, photos=None):
     """Bake the appearance of a mesh into a per-face atlas -> {"texture": uint8 [S,S,3] RGB, "uv": float64 [F,3,2] (numpy: OBJ vt per
     face corner), "layout": texture_layout's record, "points": fp32 [F T,3] the shaded points}; texture and points are device tensors.
     vertices [V,3] float, triangles [F,3] integers, object space, numpy arrays or tensors (moved to the renderer's device, or cuda).
@@ -1435,15 +1578,26 @@ def bake_texture(renderer, vertices, triangles, texture_size=2048, patch=None, p
     `shade`: a callable (points [P,3] cuda fp32, face [P] int32) -> colour [P,3] float BGR that stands in for the colour network,
     called with at most `batch` points; renderer may then be None when project is 0. patch / texture_size: texture_layout's; every
     face gets the same patch, which suits meshes whose faces are of one size. An empty mesh gives an all-zero atlas. Filtering is
-    safe at the base level only: mip levels mix neighbouring patches."""
+    safe at the base level only: mip levels mix neighbouring patches.
+    `photos`: {"P": [N,3,4] object-space projection matrices, "images": float32 [N,H,W,3] in [0, 1], BGR as the scene loader holds
+    them} plus, optionally, photo_colors' cos_min, feather, eps and blend, and "fill": the texels take their colour from the
+    photographs (photo_colors; layout, texel points and projection are the same). The points on the triangles are the occlusion
+    anchors, the projected points look the colours up; with a renderer the SDF gradient of the last shade_points call is the normal
+    (the last projection round's, or one extra call when project is 0) and a texel no camera sees takes the network's colour; without
+    one (project 0 only) the faces' own normals count, two-sided, and such a texel takes `fill` (default mid grey). The result gains
+    "coverage", the fraction of texels some camera sees, and "n_views" int32 [F T]. photos and shade together are a ValueError."""
     if int(project) != project or project < 0:
         raise ValueError("project must be a non-negative integer, got %r" % (project,))
     if int(batch) != batch or batch < 1:
         raise ValueError("batch must be at least 1")
     if shade is not None and not callable(shade):
         raise ValueError("shade must be callable")
-    if renderer is None and (shade is None or project > 0):
-        raise ValueError("bake_texture needs the renderer unless `shade` is given and project is 0")
+    if shade is not None and photos is not None:
+        raise ValueError("shade and photos both say where the colours come from: give one")
+    if photos is not None:
+        _check_photos(photos)
+    if renderer is None and ((shade is None and photos is None) or project > 0):
+        raise ValueError("bake_texture needs the renderer unless `shade` or `photos` is given and project is 0")
     if renderer is not None:
         dev = lib.first_param(renderer.sdf_network).device
     else:
@@ -1460,9 +1614,15 @@ def bake_texture(renderer, vertices, triangles, texture_size=2048, patch=None, p
         raise ValueError("max_offset must be finite and not negative, got %r" % (max_offset,))
     with torch.cuda.device(dev), torch.no_grad():
         if F == 0:
-            return {"texture": torch.zeros(layout["S"], layout["S"], 3, dtype=torch.uint8, device=dev), "uv": texture_uv(layout),
-                    "layout": layout, "points": torch.empty(0, 3, dtype=torch.float32, device=dev)}
+            res = {"texture": torch.zeros(layout["S"], layout["S"], 3, dtype=torch.uint8, device=dev), "uv": texture_uv(layout),
+                   "layout": layout, "points": torch.empty(0, 3, dtype=torch.float32, device=dev)}
+            if photos is not None:
+                res["coverage"], res["n_views"] = 0.0, torch.zeros(0, dtype=torch.int32, device=dev)
+            return res
         points, face = texel_points(v, t, layout)
+        if photos is not None:
+            r = mean_edge_length(v, t) if max_offset is None and project > 0 else float(max_offset or 0.0)
+            return _bake_photos(renderer, v, t, layout, points, face, photos, int(project), r, batch)
         if project > 0:
             r = mean_edge_length(v, t) if max_offset is None else float(max_offset)
             points = project_points(renderer, points, rounds=project, max_offset=r, batch=batch)

@@ -169,7 +169,8 @@ def validate_mesh(renderer, bound_min, bound_max, out_path, resolution=256, thre
     `texture` (a dict of vdn_hip.mesh.bake_texture's keyword arguments - texture_size, patch, project, ... - or None: nothing beyond
     the PLY) bakes a per-face atlas of the mesh that reaches the file, after `clean` and `simplify`, in object space, and writes
     <stem>.obj, <stem>.mtl and <stem>.png beside the PLY (vdn_train.meshio.write_obj), the vertices mapped as the PLY's are. The PLY
-    and the return value are what they are without it."""
+    and the return value are what they are without it. A "photos" entry ({"P": object-space cameras, "images": ...}, bake_texture's)
+    colours the atlas from the photographs instead of the colour network."""
     from vdn_train import meshio
     if texture is not None and not isinstance(texture, dict):
         raise ValueError("texture must be a dict of bake_texture's keyword arguments, got %r" % (texture,))
@@ -227,7 +228,9 @@ def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simpl
     meshes/<iter_step, 8 digits>.ply under `out_dir` (dpt_runner.py:700-711). A `clean` dict with a true "use_masks" entry gets
     the scene's object-space cameras and its masks (cleaning happens in object space); a true "use_cameras" entry gets the cameras
     and the image size without the masks - what a "visibility" entry needs (either of the two satisfies it). `simplify` is
-    validate_mesh's, in object-space units, and so is `texture`: meshes/<iter_step>.obj, .mtl and .png beside the PLY."""
+    validate_mesh's, in object-space units, and so is `texture`: meshes/<iter_step>.obj, .mtl and .png beside the PLY. A `texture`
+    dict with "photos": True (or a dict of photo_colors' options - cos_min, feather, eps, blend, fill) colours the atlas from the
+    scene's own photographs: its object-space cameras and its decoded images are filled in (vdn_hip.mesh.bake_texture(photos=))."""
     if clean is not None:
         clean = dict(clean)
         use_masks, use_cameras = clean.pop("use_masks", False), clean.pop("use_cameras", False)
@@ -235,6 +238,14 @@ def validate_scene_mesh(renderer, scene, out_dir, iter_step=0, clean=None, simpl
             clean.update(cameras=scene.projection_matrices(world_space=False), masks=scene.masks)
         elif use_cameras:
             clean.update(cameras=scene.projection_matrices(world_space=False), image_size=(int(scene.H), int(scene.W)))
+    if isinstance(texture, dict) and texture.get("photos") is not None and texture["photos"] is not False:
+        photos = {} if texture["photos"] is True else texture["photos"]
+        if not isinstance(photos, dict):
+            raise ValueError("texture['photos'] must be True or a dict of bake_texture's photo options, got %r" % (photos,))
+        photos = dict(photos)
+        photos.setdefault("P", scene.projection_matrices(world_space=False))
+        photos.setdefault("images", scene.images)
+        texture = dict(texture, photos=photos)
     bound_min = torch.tensor(scene.object_bbox_min, dtype=torch.float32)
     bound_max = torch.tensor(scene.object_bbox_max, dtype=torch.float32)
     return validate_mesh(renderer, bound_min, bound_max, os.path.join(out_dir, "meshes", "{:0>8d}.ply".format(iter_step)),
