@@ -1552,6 +1552,50 @@ typedef struct {
 int vdn_image_stats(const VdnImageStatsArgs* args_host, void* stream);
 /* the number of workgroup tiles of an H x W image = the rows of `partials` vdn_image_stats needs (0: H < 11 or W < 11) */
 int vdn_image_stats_tiles(int32_t H, int32_t W);
+
+/* ---- mesh alignment: one round of ICP against a scanned cloud (csrc/mesh_align.hip; vdn_hip/nn.py: icp) ----------
+ * vdn_icp_round: one lane per source point p = src[order[t]] (order: any visiting order, or NULL). With the 3 x 4 similarity
+ * M = [sR | t] (m00 .. m23, row-major, double)
+ *   y_r = fp32(((m_r0 p_x + m_r1 p_y) + m_r2 p_z) + m_r3)     the products and sums in double, in this order, without contraction;
+ * the nearest record of y on the target's grid by vdn_nn_query's own search (the same shells, stop rule, tie rule and
+ * d = sqrtf(d2) <= max_dist test: csrc/k_nn.h), and where that is a hit q (the record's fp32 coordinates) the pair's terms, in
+ * double from the widened fp32 values, go into the 19 sums of `result`:
+ *   [VDN_ICP_N]        1                              [VDN_ICP_P + c]   p_c                 [VDN_ICP_Q + c]   q_c
+ *   [VDN_ICP_PP]       (p_x p_x + p_y p_y) + p_z p_z  [VDN_ICP_QQ]      the same of q
+ *   [VDN_ICP_QP + 3 r + c]   q_r p_c                  [VDN_ICP_RES]     (e_x e_x + e_y e_y) + e_z e_z, e = y - q (from the fp32 y)
+ * p is the UNTRANSFORMED point: a solve on the sums gives the whole transform source -> target, not an increment on M.
+ * dist / idx (each optional) receive vdn_nn_query's outputs for the query y: dist[i], idx[i] of source point i, +inf / -1 for a miss.
+ * Two launches, no atomics: the 64 lanes of a wave add by a butterfly (every step adds the same two numbers in both lanes), a
+ * workgroup's four waves in wave order into partials[block][19], and one workgroup then adds the blocks (thread j takes blocks
+ * j, j + 256, .. in order, then the same butterfly and wave order): two calls on the same arguments give the same bits. A round
+ * that matches nothing gives 19 zeros. `partials` holds partials_rows >= vdn_icp_round_blocks(N) rows; it need not be initialised.
+ * Status -1: a null src / ref / cell_start / partials / result, N or R < 1, a bad grid (vdn_nn_query's checks), a non-finite M,
+ * or a workspace that is too small; -10: N, R or the cell count do not fit 32-bit indexing. */
+#define VDN_ICP_N 0
+#define VDN_ICP_P 1
+#define VDN_ICP_Q 4
+#define VDN_ICP_PP 7
+#define VDN_ICP_QQ 8
+#define VDN_ICP_QP 9
+#define VDN_ICP_RES 18
+#define VDN_ICP_SUMS 19
+typedef struct {
+    const float* src;              /* [N][3] the source points, untransformed */
+    const float* ref;              /* [R][4] the target's sorted packed records (VdnNnArgs.ref) */
+    const int32_t* cell_start;     /* [nx*ny*nz + 1] */
+    const int32_t* order;          /* [N] or NULL */
+    float* dist;                   /* [N] out, or NULL */
+    int64_t* idx;                  /* [N] out, or NULL */
+    double* partials;              /* [partials_rows][19] workspace */
+    double* result;                /* [19] out */
+    double m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23;
+    int64_t N, R, partials_rows;
+    float lo_x, lo_y, lo_z, h, margin, max_dist;
+    int32_t nx, ny, nz, _pad;
+} VdnIcpArgs;
+int vdn_icp_round(const VdnIcpArgs* args_host, void* stream);
+/* the number of workgroups of a round over N source points = the rows of `partials` it needs (0: N < 1 or beyond 32-bit indexing) */
+int vdn_icp_round_blocks(int64_t N);
 #ifdef __cplusplus
 }
 #endif

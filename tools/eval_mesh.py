@@ -9,7 +9,12 @@ binary little-endian PLY whose first element is `vertex` with x, y, z. The DTU p
     ... --thin 0.2 --obs-mask ObsMask24_10.mat --plane Plane24.mat [--patch 60]
 
 --thin R thins the mesh samples to pairwise more than R apart, --obs-mask FILE (.npz or .mat with ObsMask, BB, Res) leaves unobserved
-samples out of the accuracy, --plane FILE (.npz or .mat with P) leaves the scan's table out of the completeness. Prints one JSON line."""
+samples out of the accuracy, --plane FILE (.npz or .mat with P) leaves the scan's table out of the completeness.
+
+    ... --align [--scale] [--trim F] [--cameras-est pose.npy|pnf.pth --cameras-ref cameras_sphere.npz]
+
+--align registers the mesh to the scan first (tools/align_mesh.py's options; INTEGRATION.md "Mesh alignment") and evaluates the
+aligned mesh; the result gains the key `align` (the transform, the rounds, and with cameras the pose errors). Prints one JSON line."""
 import argparse
 import os
 import sys
@@ -32,10 +37,25 @@ def main():
     ap.add_argument("--plane", default=None, metavar="FILE", help=".npz / .mat with P (the DTU ground plane)")
     ap.add_argument("--patch", type=float, default=60.0, metavar="X", help="the band around the observation mask's box")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--align", action="store_true", help="register the mesh to the scan by ICP before evaluating it")
+    ap.add_argument("--align-max-dist", type=float, default=None, metavar="D", help="the registration's match distance (default: --max-dist)")
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import align_mesh as align_tool
+    align_tool.add_align_arguments(ap)
     a = ap.parse_args()
     from vdn_train import mesh_eval
+    align, cams = None, None
+    if a.align:
+        init, cams = align_tool.camera_start(a)
+        align = {"init": init, "scale": a.scale, "trim": a.trim, "max_rounds": a.max_rounds, "tol": a.tol, "thin": a.thin}
+        if a.align_max_dist is not None:
+            align["max_dist"] = a.align_max_dist
     res = mesh_eval.evaluate_ply(a.mesh, a.ground_truth, a.spacing, a.max_dist, a.thresholds, device=a.device,
-                                 thin=a.thin, obs_mask=a.obs_mask, patch=a.patch, plane=a.plane)
+                                 thin=a.thin, obs_mask=a.obs_mask, patch=a.patch, plane=a.plane, align=align)
+    if cams is not None:
+        import numpy as np
+        al = res["align"]
+        res["align"] = dict(al, pose_errors=align_tool.pose_report(cams, (al["s"], np.array(al["R"]), np.array(al["t"]))))
     print(mesh_eval.to_json(dict(res, mesh=a.mesh, ground_truth=a.ground_truth, spacing=a.spacing, max_dist=a.max_dist)))
 
 

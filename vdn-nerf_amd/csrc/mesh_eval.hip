@@ -2,12 +2,13 @@
 // triangle mesh, exact nearest neighbours on a uniform grid - the two halves of an accuracy / completeness / Chamfer figure against a
 // scanned point cloud (vdn_train/mesh_eval.py) - and greedy radius thinning of a cloud on the same grid. Gather-bound integer / float
 // work, no LDS: one thread per triangle, per sample, per point or per query. The prefix sum, the stable sorts and the cell-start
-// table between the passes are the caller's torch ops.
+// table between the passes are the caller's torch ops. The grid search itself is in k_nn.h, shared with mesh_align.hip.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <climits>
 #include "vdn_render.h"
 #include "k_tri.h"
+#include "k_nn.h"
 
 namespace vdn {
 
@@ -57,12 +58,6 @@ __global__ void surf_emit_kernel(VdnSurfArgs a) {
 }
 
 // ---- nearest neighbour on a uniform grid ------------------------------------------------------------------------------------------
-// cell coordinate along one axis: floor((p - lo) / h) in fp32, clamped into the grid (a point outside, or NaN, lands in a border cell)
-__device__ inline int nn_axis(float p, float lo, float h, int n) {
-    const float t = (p - lo) / h;
-    return (int)fminf(fmaxf(floorf(t), 0.0f), (float)(n - 1));
-}
-
 __global__ void nn_bin_kernel(VdnNnArgs a) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)a.N) return;
@@ -71,56 +66,15 @@ __global__ void nn_bin_kernel(VdnNnArgs a) {
     a.cell[i] = (cz * a.ny + cy) * a.nx + cx;
 }
 
-struct NnBest {
-    float d2;
-    int idx;
-};
-
-// the records of cells [c0, c1] of one x-row (contiguous in the sorted reference), against the query
-__device__ inline void nn_scan(const VdnNnArgs& a, int c0, int c1, float qx, float qy, float qz, NnBest& b) {
-    const int begin = max(a.cell_start[c0], 0), end = min(a.cell_start[c1 + 1], (int)a.R);
-    const float4* rec = (const float4*)a.ref;
-    for (int r = begin; r < end; ++r) {
-        const float4 p = rec[r];                       // one 16-byte load: x, y, z, original index
-        const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-        const float d2 = dx * dx + dy * dy + dz * dz;
-        const int id = __float_as_int(p.w);
-        // ties go to the lower original index, so the answer does not depend on the order cells are visited in
-        if (d2 < b.d2 || (d2 == b.d2 && id < b.idx)) { b.d2 = d2; b.idx = id; }
-    }
-}
-
 __global__ void nn_query_kernel(VdnNnArgs a) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)a.N) return;
     const long q = a.order != nullptr ? (long)a.order[t] : t;
     const float qx = a.pts[q * 3 + 0], qy = a.pts[q * 3 + 1], qz = a.pts[q * 3 + 2];
-    const int cx = nn_axis(qx, a.lo_x, a.h, a.nx), cy = nn_axis(qy, a.lo_y, a.h, a.ny), cz = nn_axis(qz, a.lo_z, a.h, a.nz);
-    // the last shell that still touches the grid
-    const int k_last = max(max(max(cx, a.nx - 1 - cx), max(cy, a.ny - 1 - cy)), max(cz, a.nz - 1 - cz));
-    NnBest b = {INFINITY, INT_MAX};
-    int k = 0;
-    for (;; ++k) {
-        // Chebyshev shell k: rows (y, z) on the shell's y / z faces take the whole x-range, the others its two end cells
-        const int x0 = max(cx - k, 0), x1 = min(cx + k, a.nx - 1);
-        for (int z = max(cz - k, 0); z <= min(cz + k, a.nz - 1); ++z) {
-            for (int y = max(cy - k, 0); y <= min(cy + k, a.ny - 1); ++y) {
-                const int row = (z * a.ny + y) * a.nx;
-                if (abs(z - cz) == k || abs(y - cy) == k) {
-                    nn_scan(a, row + x0, row + x1, qx, qy, qz, b);
-                } else {
-                    if (cx - k >= 0) nn_scan(a, row + cx - k, row + cx - k, qx, qy, qz, b);
-                    if (cx + k < a.nx) nn_scan(a, row + cx + k, row + cx + k, qx, qy, qz, b);
-                }
-            }
-        }
-        if (k >= k_last) break;
-        // every point in a cell at index distance >= k + 1 is at least k h away, less the fp32 rounding of the binning: `margin`
-        const float r = (float)k * a.h - a.margin;
-        if (r > 0.0f && (b.d2 <= r * r || r >= a.max_dist)) break;
-    }
-    const float d = sqrtf(b.d2);
-    const bool hit = b.idx != INT_MAX && d <= a.max_dist;
+    NnBest b;
+    const int k = nn_search(a, qx, qy, qz, b);           // (k_nn.h, shared with mesh_align.hip)
+    float d;
+    const bool hit = nn_hit(b, a.max_dist, &d);
     a.dist[q] = hit ? d : INFINITY;
     a.idx[q] = hit ? (int64_t)b.idx : (int64_t)-1;
     if (a.rings != nullptr) a.rings[q] = k + 1;

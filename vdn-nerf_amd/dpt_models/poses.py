@@ -70,6 +70,16 @@ class LearnableRays:
         self.pose_net, self.intrin_net, self.pixels = pose_net, intrin_net, pixels
         self.H, self.W, self.device = pixels.H, pixels.W, pixels.device
 
+    def current_poses(self):
+        """[N,4,4]: every camera's current pose (vdn_train.mesh_align.current_poses)."""
+        from vdn_train import mesh_align
+        return mesh_align.current_poses(self.pose_net)
+
+    def store_current_pose(self, base_exp_dir, iter_step):
+        """dpt_runner.py:403-415: cam_poses/pose_{iter_step:0>6d}.npy under base_exp_dir (vdn_train.mesh_align)."""
+        from vdn_train import mesh_align
+        return mesh_align.store_current_pose(self.pose_net, base_exp_dir, iter_step)
+
     def _rays(self, img_idx, px, py):
         pose = self.pose_net(img_idx)
         intrinsic_inv = torch.inverse(self.intrin_net())

@@ -27,7 +27,7 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", INCL
 PER_FILE_FLAGS = {"rays.hip": ["-ffp-contract=off"], "train_rays.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
                   "mesh_ray.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"],
                   "mesh_texture.hip": ["-ffp-contract=off"], "mesh_photo.hip": ["-ffp-contract=off"],
-                  "image_eval.hip": ["-ffp-contract=off"],
+                  "image_eval.hip": ["-ffp-contract=off"], "mesh_align.hip": ["-ffp-contract=off"],
                   # k_sdf_fwd2.h: no SLP packing of the epilogue into v_pk_*_f32, MFMA accumulators in arch VGPRs
                   "sdf_bf16.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                   "shade_bf16.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],

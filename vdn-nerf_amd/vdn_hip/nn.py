@@ -9,6 +9,10 @@ and, on the same grid construction, greedy radius thinning of a cloud to a fixed
 
     keep = thin_points(points, radius)    # keep [N] bool: kept points are pairwise more than `radius` apart
 
+and registration against the grid's cloud (vdn_icp_round, csrc/mesh_align.hip): one launch pair per ICP round
+
+    res = icp(src, grid, max_dist=d)      # res["s"], res["R"], res["t"]: src -> the cloud; solve_sim3, IcpRound on their own
+
 The kernels bin and search; the stable sorts and the cell-start table between them are torch ops on the device (the convention of
 vdn_hip/mesh.py). The cell size changes the speed only, never a result (the stopping rule and its margin)."""
 import math
@@ -226,3 +230,171 @@ def thin_points(points, radius, cell_size=None, max_cells=1 << 24, return_rounds
         keep = torch.empty(N, dtype=torch.bool, device=dev)
         keep[grid.records.view(torch.int32)[:, 3].long()] = state == 1
     return (keep, rounds) if return_rounds else keep
+
+
+# ---- registration: one ICP round on the device, the closed-form solve, the loop ---------------------------------
+ICP_SUMS = 19
+# the slots of vdn_icp_round's result (include/vdn_render.h: VDN_ICP_*)
+ICP_N, ICP_P, ICP_Q, ICP_PP, ICP_QQ, ICP_QP, ICP_RES = 0, 1, 4, 7, 8, 9, 18
+
+
+def sim3_matrix(s, R, t):
+    """(s, R, t) -> the 3 x 4 float64 matrix [sR | t] vdn_icp_round takes."""
+    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64).reshape(3)
+    if R.shape != (3, 3):
+        raise ValueError("R must be 3 x 3")
+    M = np.empty((3, 4))
+    M[:, :3], M[:, 3] = float(s) * R, t
+    if not np.isfinite(M).all():
+        raise ValueError("the transform is not finite")
+    return M
+
+
+def query_order(grid, y):
+    """The visiting order PointGrid.query uses for the queries y [N,3] fp32: their stable sort by cell, int32 [N]."""
+    with torch.cuda.device(grid.device):
+        return torch.sort(grid._bin(y), stable=True)[1].to(torch.int32)
+
+
+class IcpRound:
+    """One registration round as an operator (vdn_icp_round): src [N,3] float CUDA against the PointGrid `grid` of the target.
+
+        sums = IcpRound(src, grid)(M, max_dist)          # [19] float64 on the device: see ICP_* and include/vdn_render.h
+
+    order: an int32 [N] visiting order (query_order) or None; with_dist / with_idx keep vdn_nn_query's per-point outputs of the
+    last call in .dist [N] fp32 / .idx [N] int64. The workspace is allocated once; every call is two launches and no host read."""
+
+    def __init__(self, src, grid, order=None, with_dist=False, with_idx=False):
+        if not isinstance(grid, PointGrid):
+            raise ValueError("grid must be a PointGrid")
+        src = _check_points(src, "src")
+        if src.device != grid.device:
+            raise ValueError("src must be on the target's device")
+        N = src.shape[0]
+        if N == 0:
+            raise ValueError("the source cloud is empty")
+        if order is not None and not (torch.is_tensor(order) and order.dtype == torch.int32 and order.shape == (N,) and
+                                      order.device == src.device and order.is_contiguous()):
+            raise ValueError("order must be a contiguous int32 [N] tensor on the source's device")
+        self.src, self.grid, self.order, self.N = src, grid, order, N
+        dev = src.device
+        blocks = lib.call_value("vdn_icp_round_blocks", N)
+        if blocks < 1:
+            raise ValueError("vdn_icp_round: the sizes do not fit 32-bit indexing")
+        self.partials = torch.empty(blocks, ICP_SUMS, dtype=torch.float64, device=dev)
+        self.result = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+        self.dist = torch.empty(N, dtype=torch.float32, device=dev) if with_dist else None
+        self.idx = torch.empty(N, dtype=torch.int64, device=dev) if with_idx else None
+        a = self.args = lib.VdnIcpArgs()
+        a.src, a.ref, a.cell_start = src.data_ptr(), grid.records.data_ptr(), grid.cell_start.data_ptr()
+        a.order = order.data_ptr() if order is not None else None
+        a.dist = self.dist.data_ptr() if with_dist else None
+        a.idx = self.idx.data_ptr() if with_idx else None
+        a.partials, a.result, a.partials_rows = self.partials.data_ptr(), self.result.data_ptr(), blocks
+        a.N, a.R = N, grid.R
+        a.lo_x, a.lo_y, a.lo_z, a.h, a.margin = grid.lo[0], grid.lo[1], grid.lo[2], grid.h, grid.margin
+        a.nx, a.ny, a.nz = grid.dims
+
+    def __call__(self, M, max_dist):
+        M = np.asarray(M, np.float64)
+        if M.shape != (3, 4) or not np.isfinite(M).all():
+            raise ValueError("M must be a finite 3 x 4 matrix")
+        if not (float(max_dist) >= 0.0):
+            raise ValueError("max_dist must be >= 0, got %r" % (max_dist,))
+        a = self.args
+        (a.m00, a.m01, a.m02, a.m03, a.m10, a.m11, a.m12, a.m13, a.m20, a.m21, a.m22, a.m23) = [float(x) for x in M.reshape(-1)]
+        a.max_dist = _fp32_at_most(float(max_dist))
+        with torch.cuda.device(self.src.device):
+            _call_sized("vdn_icp_round", a, lib.stream_handle())
+        return self.result
+
+
+def solve_sim3(sums, scale=True):
+    """The 19 sums of a round (ICP_*: n, sum p, sum q, sum p.p, sum q.q, sum q p^T, the residual) -> (s, R, t), float64 numpy: the
+    similarity q ~ s R p + t that minimises sum |s R p + t - q|^2 over the pairs, by Umeyama's closed form:
+        mp, mq = sum p / n, sum q / n;   C = sum q p^T / n - mq mp^T;   vp = sum p.p / n - |mp|^2;   C = U D V^T
+        S = diag(1, 1, sign(det U det V))  (the reflection guard: det R = +1 always);   R = U S V^T
+        s = trace(D S) / vp (1 when scale=False);   t = mq - s R mp
+    ValueError when fewer than 3 pairs matched, or when the pairs' covariance C has rank < 2 (its second singular value <= 1e-12 of
+    the first: source or matches on a line or in a point - the rotation about that line is not determined)."""
+    x = np.asarray(sums.detach().cpu() if torch.is_tensor(sums) else sums, dtype=np.float64).reshape(-1)
+    if x.shape[0] != ICP_SUMS:
+        raise ValueError("sums must hold %d numbers" % ICP_SUMS)
+    n = x[ICP_N]
+    if not (n >= 3):
+        raise ValueError("fewer than 3 pairs matched (%d)" % int(n))
+    mp, mq = x[ICP_P:ICP_P + 3] / n, x[ICP_Q:ICP_Q + 3] / n
+    C = x[ICP_QP:ICP_QP + 9].reshape(3, 3) / n - np.outer(mq, mp)
+    vp = x[ICP_PP] / n - float(mp @ mp)
+    U, D, Vt = np.linalg.svd(C)
+    if not (D[0] > 0.0 and D[1] > 1e-12 * D[0] and vp > 0.0):
+        raise ValueError("the matched pairs are degenerate (covariance of rank < 2): no rotation is determined")
+    S = np.array([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0.0 else -1.0])
+    R = (U * S) @ Vt
+    s = float((D * S).sum() / vp) if scale else 1.0
+    return s, R, mq - s * (R @ mp)
+
+
+def _corner_motion(corners, A, B):
+    """the largest displacement of the corners [8,3] between the transforms A and B ((s, R, t) each)"""
+    ya = A[0] * corners @ A[1].T + A[2]
+    yb = B[0] * corners @ B[1].T + B[2]
+    return float(np.sqrt(((ya - yb) ** 2).sum(1)).max())
+
+
+def icp(src, target, init=None, max_dist=float("inf"), scale=False, max_rounds=50, tol=1e-7, trim=None):
+    """Point-to-point ICP from src [N,3] (float CUDA) to `target` (a PointGrid, or a [R,3] CUDA tensor a grid is built of), one way.
+    init: (s, R, t) or None for the identity. Every round is one vdn_icp_round at the current transform T (transform, nearest
+    target point within the round's threshold, the pairs' 19 moments), one host read of the 19 doubles and one solve_sim3 on them,
+    which gives the next T whole (the moments are of the untransformed source: no chain of increments).
+      threshold  round 0: max_dist. With trim = f (0 < f <= 1), round k >= 1: min(max_dist, the ceil(f n)-th smallest of the n
+                 finite distances of round k - 1) (torch.kthvalue on the device; one more host read per round)
+      converged  when the 8 corners of the source's bounding box move by <= tol x the box's diagonal between consecutive transforms
+    -> dict: s, R [3,3], t [3], matrix [4,4] (float64 numpy), rounds, converged, and per round the lists n_pairs, rms
+    (sqrt(residual sum / n_pairs), at the round's T) and threshold.
+    ValueError for a round that matches fewer than 3 points (it names max_dist) or degenerate pairs. The samples are visited in
+    the cell order of the initial transform (it changes the speed only)."""
+    grid = target if isinstance(target, PointGrid) else PointGrid(_check_points(target, "target"))
+    src = _check_points(src, "src")
+    if src.shape[0] == 0:
+        raise ValueError("the source cloud is empty")
+    if not (float(max_dist) >= 0.0):
+        raise ValueError("max_dist must be >= 0, got %r" % (max_dist,))
+    if trim is not None and not (0.0 < float(trim) <= 1.0):
+        raise ValueError("trim must be in (0, 1], got %r" % (trim,))
+    if int(max_rounds) < 1 or not (float(tol) >= 0.0):
+        raise ValueError("max_rounds must be >= 1 and tol >= 0")
+    T = (1.0, np.eye(3), np.zeros(3)) if init is None else (float(init[0]), np.asarray(init[1], np.float64), np.asarray(init[2], np.float64).reshape(3))
+    M = sim3_matrix(*T)
+    box = torch.stack([src.amin(0), src.amax(0)]).double().cpu().numpy()
+    if not np.isfinite(box).all():
+        raise ValueError("the source cloud has non-finite coordinates")
+    corners = np.array([[box[(c >> d) & 1, d] for d in range(3)] for c in range(8)])
+    diag = float(np.linalg.norm(box[1] - box[0]))
+    with torch.cuda.device(src.device):
+        y0 = (src.double() @ torch.from_numpy(M[:, :3].T.copy()).to(src.device) + torch.from_numpy(M[:, 3].copy()).to(src.device)).float()
+        op = IcpRound(src, grid, order=query_order(grid, y0), with_dist=trim is not None)
+        del y0
+    out = {"n_pairs": [], "rms": [], "threshold": [], "converged": False}
+    thr = float(max_dist)
+    for k in range(int(max_rounds)):
+        x = op(M, thr).cpu().numpy()
+        n = int(x[ICP_N])
+        out["n_pairs"].append(n)
+        out["rms"].append(math.sqrt(x[ICP_RES] / n) if n > 0 else float("nan"))
+        out["threshold"].append(thr)
+        if n < 3:
+            raise ValueError("round %d matched %d points within max_dist = %r (threshold %r): fewer than 3" % (k, n, max_dist, thr))
+        T_new = solve_sim3(x, scale=scale)
+        moved = _corner_motion(corners, T, T_new)
+        T, M = T_new, sim3_matrix(*T_new)
+        if trim is not None:
+            kth = int(math.ceil(float(trim) * n))
+            thr = min(float(max_dist), float(torch.kthvalue(op.dist, max(kth, 1)).values.item()))
+        if moved <= float(tol) * diag:
+            out["converged"] = True
+            break
+    out["rounds"] = len(out["n_pairs"])
+    out["s"], out["R"], out["t"] = T
+    out["matrix"] = np.vstack([M, [0.0, 0.0, 0.0, 1.0]])
+    return out

@@ -81,7 +81,8 @@ def above_plane(points, plane):
     return pl[0] * p[:, 0] + pl[1] * p[:, 1] + pl[2] * p[:, 2] + pl[3] > 0
 
 
-def evaluate_mesh(vertices, triangles, gt_points, spacing, max_dist, thresholds=(), thin=None, obs_mask=None, patch=60.0, plane=None):
+def evaluate_mesh(vertices, triangles, gt_points, spacing, max_dist, thresholds=(), thin=None, obs_mask=None, patch=60.0, plane=None,
+                  align=None):
     """vertices [V,3], triangles [F,3] (or None: `vertices` is evaluated as a bare cloud), gt_points [G,3], all CUDA tensors ->
     dict of
       n_mesh_samples, n_gt
@@ -100,12 +101,28 @@ def evaluate_mesh(vertices, triangles, gt_points, spacing, max_dist, thresholds=
       plane     (a, b, c, d): completeness runs from gt_points[above_plane(gt_points, plane)] only
     precision / recall are then shares of those two query sets (samples[observed], gt above the plane), max_dist stays inclusive.
     Further keys: n_thinned (samples the thinning removed), thin_rounds, n_inbound, n_observed, n_gt_above_plane; n_mesh_samples
-    counts the samples after thinning. ValueError when a filter leaves a side empty."""
+    counts the samples after thinning. ValueError when a filter leaves a side empty.
+
+    align (vdn_train/mesh_align.py): None, or what brings the mesh into the ground truth's frame BEFORE it is sampled - a transform
+    (s, R, t) applied to the vertices, or a dict of align_mesh options (init, scale, thin, max_rounds, tol, trim, and spacing /
+    max_dist where the registration's differ from the evaluation's): the mesh is registered to gt_points by ICP first. The dict
+    then gains the key `align`: s, R, t, matrix, and with a registration rounds, converged and the last round's n_pairs / rms."""
     from vdn_hip import mesh as hmesh, nn
     thresholds = _check_args(spacing, max_dist, thresholds)
     for x, what in ((vertices, "vertices"), (gt_points, "gt_points")):
         if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.shape[1] == 3):
             raise ValueError("%s must be a [N,3] CUDA tensor" % what)
+    aligned = None
+    if align is not None:
+        from . import mesh_align
+        if isinstance(align, dict):
+            opts = dict(align)
+            res = mesh_align.align_mesh(vertices, triangles, gt_points, opts.pop("spacing", spacing), opts.pop("max_dist", max_dist), **opts)
+            vertices, aligned = res["vertices"], mesh_align.summary(res)
+        else:
+            vertices = mesh_align.apply_sim3(vertices, align)
+            s_, R_, t_ = mesh_align._sim3(align)
+            aligned = {"s": s_, "R": R_.tolist(), "t": t_.tolist(), "matrix": np.vstack([np.c_[s_ * R_, t_], [0.0, 0.0, 0.0, 1.0]]).tolist()}
     if triangles is None:
         samples = vertices.detach().float().contiguous()
     else:
@@ -149,14 +166,17 @@ def evaluate_mesh(vertices, triangles, gt_points, spacing, max_dist, thresholds=
         p, r = int((d_acc <= t32).sum().item()) / acc_from.shape[0], int((d_comp <= t32).sum().item()) / comp_from.shape[0]
         out["precision"][t], out["recall"][t] = p, r
         out["fscore"][t] = 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+    if aligned is not None:
+        out["align"] = aligned
     return out
 
 
-def evaluate_ply(mesh_path, gt_path, spacing, max_dist, thresholds=(), device="cuda:0", thin=None, obs_mask=None, patch=60.0, plane=None):
+def evaluate_ply(mesh_path, gt_path, spacing, max_dist, thresholds=(), device="cuda:0", thin=None, obs_mask=None, patch=60.0, plane=None,
+                 align=None):
     """evaluate_mesh on files: a mesh written by vdn_train.meshio.write_ply (validate_mesh(world_space=True) leaves one in the
     ground truth's frame) against the vertex positions of a scanned-cloud PLY (meshio.read_points_ply). obs_mask and plane may be
     paths of DTU auxiliary files (meshio.read_dtu_aux: ObsMask, BB and Res from the first, P from the second) or what
-    evaluate_mesh takes."""
+    evaluate_mesh takes; align is evaluate_mesh's."""
     from . import meshio
     _check_args(spacing, max_dist, thresholds)
     if isinstance(obs_mask, (str, os.PathLike)):
@@ -174,10 +194,11 @@ def evaluate_ply(mesh_path, gt_path, spacing, max_dist, thresholds=(), device="c
     dev = torch.device(device)
     return evaluate_mesh(torch.from_numpy(np.ascontiguousarray(m["vertices"])).to(dev), torch.from_numpy(np.ascontiguousarray(m["triangles"])).to(dev),
                          torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32)).to(dev), spacing, max_dist, thresholds,
-                         thin=thin, obs_mask=obs_mask, patch=patch, plane=plane)
+                         thin=thin, obs_mask=obs_mask, patch=patch, plane=plane, align=align)
 
 
 def to_json(result):
     """One JSON line of an evaluate_mesh result (threshold keys as strings, nan as null)."""
     clean = lambda v: None if isinstance(v, float) and not math.isfinite(v) else v
-    return json.dumps({k: ({repr(t): clean(x) for t, x in v.items()} if isinstance(v, dict) else clean(v)) for k, v in result.items()})
+    return json.dumps({k: (v if k == "align" else {repr(t): clean(x) for t, x in v.items()} if isinstance(v, dict) else clean(v))
+                       for k, v in result.items()})
